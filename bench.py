@@ -2,7 +2,7 @@
 """Benchmark of the MI355X-native DiffBindFR sampler (BASELINE.json metric: poses/sec).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|1] [--batch-poses B] [--scaling weak|strong]
-                    [--jobs J] [--store device|host] [--gather all|root]
+                    [--jobs J] [--store device|host] [--gather all|root] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no torchrun environment: the script spawns its own N ranks (one process per GPU, LOCAL_RANK -> cuda:LOCAL_RANK,
 rendezvous on 127.0.0.1), relays rank 0's ONE JSON line and returns the ranks' worst exit code; under `python -m torch.distributed.run
@@ -22,6 +22,8 @@ ONE ligand record (forward screen / target fishing).  Per-complex records are re
 (uploaded once per ligand / pocket); fp32 arithmetic throughout (the reference runs fp32).  Rank 0 prints ONE JSON line.
 After the timed region (N = 1) the script measures the dominant kernel's HBM traffic itself: two child runs of one batch under
 `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (`--no-pmc` skips them), then the latency cases and the CPU-oracle baseline.
+`--dump-outputs DIR` writes the poses of the last timed step as DIR/<name>.npy (see dump_outputs): the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import copy
@@ -315,6 +317,27 @@ class BoardSampler:
                 "source": f"{self.dir}/power1_input, freq1_input, twice a second during the timed region (rank 0's board)"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, res, shards, reps, batch_poses):
+    """--dump-outputs: what the timed path computed in its last step, i.e. the last batch of every rank (dist.plan_batches: the plan
+    run_sharded follows), as run_sharded's caller receives it -- per job (lig [P, N_l, 3], atom14 [P, N_r, 14, 3]) -- with the batch's
+    poses concatenated in job order: lig_pos.npy [sum N_l, 3] and atom14_pos.npy [sum N_r, 14, 3], float32.  Beyond DUMP_MAX_BYTES
+    a fixed seeded sample of whole poses is written instead.  Returns {name: shape}."""
+    last = sorted(u for s in shards if s for u in ddist.plan_batches([(j, reps[j]) for j in s], batch_poses)[-1])
+    poses = [(j, p) for j, p0, n in last for p in range(p0, p0 + n)]
+    size = [4 * (3 * res[j][0].shape[1] + 42 * res[j][1].shape[1]) for j, _ in poses]
+    if sum(size) > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).permutation(len(poses))[:DUMP_MAX_BYTES // max(size)])
+        poses = [poses[i] for i in keep]
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"lig_pos": torch.cat([res[j][0][p] for j, p in poses]), "atom14_pos": torch.cat([res[j][1][p] for j, p in poses])}
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    return {name: list(t.shape) for name, t in out.items()}
+
+
 def latency_leg(samp, dev, lib, model):
     """BASELINE configs[0] literally, as predict.py is used: ONE complex of the 3DBS shape x 4 poses x 20 steps
     (records resident, assemble + init + sample + status sync timed), predict.py's `-bs 16` of the cfg-2 shape, and the shape of the
@@ -428,7 +451,13 @@ def main():
     ap.add_argument("--no-speed-shard", action="store_true", help="N > 1: shard the job table evenly instead of by the ranks' measured speed")
     ap.add_argument("--gather", choices=("all", "root"), default=None, help="dist.run_sharded: every rank receives every pose, or rank 0 only (default: all; root for "
                                                                           "the screening configs 3 / 4 on more than one GPU: 10 k ligands x 40 poses are written out by one rank)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the poses of the last one as DIR/<name>.npy "
+                                                                         "(float32, at most 64 MB: a fixed seeded sample of the poses beyond that)")
     args = ap.parse_args()
+    ppc = synthetic.CONFIGS[args.config]["poses"]
+    if args.jobs is None and args.batch_poses < ppc:
+        ap.error(f"--batch-poses {args.batch_poses} < the {ppc} poses of a config-{args.config} job: a job would be cut over several "
+                 f"batches and --steps would not be the number of timed batches (give --jobs instead)")
     screen = args.config in (3, 4) and args.gpus > 1
     if args.store is None:
         args.store = "host" if screen else "device"
@@ -451,7 +480,6 @@ def main():
     torch.cuda.set_device(dev)
     lib = L.load()
     cfg = synthetic.CONFIGS[args.config]
-    ppc = cfg["poses"]
     B = args.batch_poses
     jobs_per_batch = max(1, B // ppc)
 
@@ -527,6 +555,7 @@ def main():
                                      torch.cuda.max_memory_allocated(dev) / 2 ** 30, t_up, asm_s[0],
                                      (len(warm) * ppc / calib_s) if calib_s else 0.0], dev)
     n_steps = max(int(v[3]) for v in per_rank) if args.jobs else args.steps      # --jobs: a step is still one batch; the slowest rank's count
+    assert world > 1 or len(done) == n_steps, f"{len(done)} batches timed for {n_steps} steps"
     counters = (C.c_int64 * 8)()
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     L.check(lib.dbfr_status_sync(C.c_void_p(model.workspace_of(dev).data_ptr()), stream, counters))
@@ -535,6 +564,7 @@ def main():
     poses = sum(reps)
     if args.gather == "all" or rank == 0:
         assert sum(int(r[0].shape[0]) for r in res) == poses
+    dumped = dump_outputs(args.dump_outputs, res, shards, reps, B) if args.dump_outputs and rank == 0 else None
 
     def read_roofline(elapsed_s, mode):
         """The dominant kernel's line from the library's own HIP events (recorded on the stream the kernel runs on)."""
@@ -684,6 +714,8 @@ def main():
         }
         if native is not None:
             line["native_f32"] = native
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if args.config == 2 and world == 1:
             # BASELINE.json configs[1] literally (128 complexes x 40 poses = 5120 poses), whatever --steps is: the rate over the first
             # batches that add up to it

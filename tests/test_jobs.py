@@ -418,6 +418,33 @@ def test_bench_line_through_rccl_on_one_rank():
 
 
 @pytest.mark.gpu
+def test_bench_dumps_the_poses_of_its_last_step(tmp_path):
+    """`bench.py --steps 2 --dump-outputs DIR`: two batches timed, `ms_per_step` covers them, DIR holds the last batch's poses (jobs 2 and 3 of
+    the seeded table, 40 poses each) as float32 .npy files, and a second run with the same arguments writes the same arrays bit for bit."""
+    import json
+    import bench
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--batch-poses", "80",
+           "--no-profile", "--no-cpu-baseline", "--no-latency", "--no-board"]
+    jobs = bench.make_jobs(2, 4, seed=1)
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run(cmd + ["--dump-outputs", str(tmp_path / name)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-4000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])
+        c = line["config"]
+        assert line["steps"] == 2 and c["batches_this_rank"] == 2 and c["poses_total"] == 160
+        assert line["ms_per_step"] * 2 >= 1e3 * sum(c["batch_seconds_this_rank"]) - 2
+        z = {k: np.load(tmp_path / name / f"{k}.npy") for k in ("lig_pos", "atom14_pos")}
+        assert sorted(os.listdir(tmp_path / name)) == ["atom14_pos.npy", "lig_pos.npy"]
+        assert z["lig_pos"].shape == (40 * (jobs[2].n_l + jobs[3].n_l), 3) and z["atom14_pos"].shape == (40 * (jobs[2].n_r + jobs[3].n_r), 14, 3)
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in z.values())
+        assert line["dumped_outputs"]["shapes"] == {k: list(a.shape) for k, a in z.items()}
+        runs.append(z)
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+
+
+@pytest.mark.gpu
 def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it (the driver's own command form): the script starts its two ranks itself
     (LOCAL_RANK -> device, rendezvous on 127.0.0.1), rank 0's ONE line comes back through the parent, and the line shows that the

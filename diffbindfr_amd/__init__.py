@@ -8,5 +8,6 @@ registered into its registries as well.
 from .registry import INTERACTION, MLDOCK_BUILDER, register_into_druglib  # noqa: F401
 from .score_model import TensorProductModelHIP  # noqa: F401
 from .sampler import DiffBindFRHIP  # noqa: F401
+from . import vina  # noqa: F401
 
 register_into_druglib()

@@ -95,13 +95,24 @@ class PdbTopology(C.Structure):
                 ("remark", C.c_char_p)]
 
 
+class VinaIn(C.Structure):
+    _fields_ = [("batch", C.c_void_p), ("lig_type", C.c_void_p), ("rec_type", C.c_void_p), ("pair_ptr", C.c_void_p),
+                ("pair_ij", C.c_void_p), ("n_pairs", C.c_int32), ("ext_ptr", C.c_void_p), ("ext_pos", C.c_void_p),
+                ("ext_type", C.c_void_p), ("max_tor", C.c_int32), ("max_ext", C.c_int32)]
+
+
+class VinaOpts(C.Structure):
+    _fields_ = [("max_iters", C.c_int32), ("grad_tol", C.c_float), ("margin", C.c_float)]
+
+
 # every symbol include/dbfr.h declares (tests check that the library exports all of them)
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
            "dbfr_init_poses", "dbfr_extract_templates", "dbfr_status_sync", "dbfr_abi_version", "dbfr_build_id", "dbfr_last_error", "dbfr_wigner3j", "dbfr_conv_paths", "dbfr_test_pack_f16_tiles", "dbfr_test_pack_f16_rows", "dbfr_test_chunk_table", "dbfr_test_pack_f16_depth", "dbfr_probe_mfma_f16",
            "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
-           "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features"]
+           "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
+           "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize"]
 
 _lib = None
 
@@ -174,6 +185,10 @@ def load():
     lib.dbfr_mdn_workspace_bytes.argtypes = [C.POINTER(MdnBatch), C.POINTER(C.c_size_t)]
     lib.dbfr_mdn_pocket_features.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.dbfr_mdn_forward.argtypes = [vp, C.POINTER(MdnBatch), vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_vina_workspace_bytes.argtypes = [C.POINTER(VinaIn), C.POINTER(C.c_size_t)]
+    lib.dbfr_vina_score.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_vina_score_at.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_vina_minimize.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), vp, vp, vp, vp, C.c_size_t, vp]
     if lib.dbfr_abi_version() != 6:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

@@ -195,8 +195,18 @@ class SdfTemplate:
         self._arr = arr
         return L.SdfTemplate(self.n_atoms, self.header.encode(), arr, self.trailer.encode())
 
-    def format(self, pos):
-        """Text of one pose (pos [n_atoms,3])."""
+    def with_data(self, items):
+        """The same template with SD data items appended to the record (after the existing ones, before ``$$$$``):
+        items = {tag: value text}, written as ``> <tag>`` / value / blank line."""
+        add = "".join(f"> <{k}>\n{v}\n\n" for k, v in items.items())
+        t = self.trailer
+        cut = t.rindex("$$$$")
+        return SdfTemplate(self.header, self.atom_tails, t[:cut] + add + t[cut:])
+
+    def format(self, pos, data=None):
+        """Text of one pose (pos [n_atoms,3]); data = optional {tag: value text} items of this pose (``with_data``)."""
+        if data:
+            return self.with_data(data).format(pos)
         from . import lib as L
         import ctypes as C
         lib = L.load()
@@ -209,14 +219,21 @@ class SdfTemplate:
         lib.dbfr_sdf_format(C.byref(t), a.ctypes.data_as(C.c_void_p), buf, need)
         return buf.raw.decode()
 
-    def write_poses(self, pos, paths, threads=0):
-        """pos [n_pose, n_atoms, 3] -> paths[i], on library threads."""
+    def write_poses(self, pos, paths, threads=0, data=None):
+        """pos [n_pose, n_atoms, 3] -> paths[i], on library threads.  data = optional {tag: [value text per pose]}: SD data
+        items of each pose (``with_data``); without it the output is unchanged."""
         from . import lib as L
         import ctypes as C
         lib = L.load()
         a = np.ascontiguousarray(np.asarray(pos, np.float32))
         if a.ndim != 3 or a.shape[1:] != (self.n_atoms, 3) or a.shape[0] != len(paths):
             raise L.DbfrError(f"pose array {a.shape} for {len(paths)} paths of a {self.n_atoms}-atom ligand")
+        if data:
+            if any(len(v) != len(paths) for v in data.values()):
+                raise L.DbfrError(f"data items need one value per pose ({len(paths)})")
+            for i, p in enumerate(paths):
+                self.with_data({k: v[i] for k, v in data.items()}).write_poses(a[i:i + 1], [p], threads=1)
+            return
         t = self._c()
         arr = (C.c_char_p * len(paths))(*[str(x).encode() for x in paths])
         L.check(lib.dbfr_sdf_write_files(C.byref(t), a.ctypes.data_as(C.c_void_p), len(paths), arr, int(threads)))

@@ -34,7 +34,8 @@ extern "C" {
                                 3: + dbfr_model_set_edge_log, dbfr_model_fallback_convs, dbfr_test_pack_f16_depth, dbfr_probe_mfma_f16 (additions only);
                                 4: + DBFR_GEMM_REDUCE_FIRST (the new default), dbfr_profile_executed_flops; dbfr_model_set_edge_log takes the graph capacity; DBFR_GEMM_SPLIT_BF16_L1 (k_conv2s) retired; dbfr_test_conv2's message rows in that mode hold segment sums;
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
-                                6: + dbfr_profile_useful_flops, dbfr_model_set_tie_log, dbfr_test_reduce_ln2; dbfr_model_set_edge_log accepts batches with fewer graphs than its capacity; an unknown DBFR_GEMM value fails dbfr_model_create */
+                                6: + dbfr_profile_useful_flops, dbfr_model_set_tie_log, dbfr_test_reduce_ln2; dbfr_model_set_edge_log accepts batches with fewer graphs than its capacity; an unknown DBFR_GEMM value fails dbfr_model_create;
+                                   later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize */
 
 typedef enum {
   DBFR_OK = 0,
@@ -403,6 +404,62 @@ int dbfr_mdn_pocket_features(int32_t n_graph, int32_t n_res, const int32_t* res_
                              const int32_t* aatype, const float* atom14_pos, int32_t topk, float* node_s, float* node_v,
                              int32_t* edge_src, int32_t* edge_dst, int32_t* in_ptr, float* edge_s, float* edge_v,
                              void* hip_stream);
+
+/* ---- Vina-function refinement of sampled poses (the error-correction stage the reference delegates to `smina --minimize`,
+ * DiffBindFR/app/predict.py:156-191; built here as a specified refinement, numeric parity with smina is not pinned).
+ * The AutoDock Vina scoring function (Trott & Olson, J. Comput. Chem. 2010) on a rigid receptor, heavy atoms only, XS atom
+ * types 0..15 = C_H C_P N_P N_D N_A N_DA O_P O_D O_A O_DA S_P P_P F_H Cl_H Br_H I_H, any other value = DUMMY (takes part in
+ * no term).  Pairs with r < 8 A, d = r - R_i - R_j:  gauss1 exp(-(d/0.5)^2) x -0.035579, gauss2 exp(-((d-3)/2)^2) x -0.005156,
+ * repulsion d^2 (d < 0) x 0.840245, hydrophobic (both hydrophobic: 1 below 0.5, linear to 0 at 1.5) x -0.035069, hbond (donor
+ * with acceptor, either way: 1 below -0.7, linear to 0 at 0) x -0.587439.  E_inter over (ligand, receptor) pairs, E_intra
+ * over the listed ligand pairs; objective = E_inter + E_intra; affinity = E_inter / (1 + 0.05846 N_rot), N_rot = the graph's
+ * torsions (tor_ptr).  diffbindfr_amd/vina.py types the atoms and builds the pair lists; docs/vina.md states it all.
+ * Receptor atoms of a pose = its pocket atoms in `batch` (rec_pos, rec_type) + optional extra atoms (ext_*).           */
+typedef struct {
+  const dbfr_batch* batch;   /* host struct of device pointers: lig_ptr, lig_pos, bond_src/dst, tor_ptr, tor_bond, rot_mask(_off), atm_ptr, rec_pos */
+  const int8_t*  lig_type;   /* [NL] XS type of every ligand atom                                                       */
+  const int8_t*  rec_type;   /* [NA] XS type of every pocket atom                                                       */
+  const int32_t* pair_ptr;   /* [G+1] CSR of the intra-ligand pairs by graph                                           */
+  const int32_t* pair_ij;    /* [n_pairs, 2] global ligand atom indices, each unordered pair once                       */
+  int32_t        n_pairs;
+  const int32_t* ext_ptr;    /* [G+1] extra receptor atoms per graph, or NULL = none                                    */
+  const float*   ext_pos;    /* [n_ext, 3] in the frame of lig_pos                                                      */
+  const int8_t*  ext_type;   /* [n_ext]                                                                                 */
+  int32_t        max_tor;    /* host-known maxima over the graphs: torsions (<= 58), extra atoms                         */
+  int32_t        max_ext;
+} dbfr_vina_in;
+
+typedef struct {
+  int32_t max_iters;         /* BFGS iterations (accepted steps), default 100                                           */
+  float   grad_tol;          /* stop once max |dE/dq| < grad_tol, default 1e-3                                          */
+  float   margin;            /* receptor candidates within 8 A + margin; collected again after a move of margin / 2 (2)  */
+} dbfr_vina_opts;
+
+/* Device workspace (receptor candidate lists): G x (max_na + max_ext) x 16 bytes.  Refuses (DBFR_ERR_ARG) ligands of more than
+ * 256 atoms or 58 torsions (the minimiser's (6 + n_tor)^2 inverse Hessian is held in LDS) and pockets of more than 8192 atoms.  A
+ * graph whose counts exceed the stated maxima, or whose torsion bond lies outside its atoms, gets NaN terms and iters = -1 and
+ * is not touched.                                                                                         */
+int dbfr_vina_workspace_bytes(const dbfr_vina_in* in, size_t* bytes);
+/* At the poses in batch->lig_pos: terms [G,8] = {gauss1, gauss2, repulsion, hydrophobic, hbond (weighted inter terms), E_intra,
+ * objective, affinity}; grad_rigid [G,6] = {sum_i dE/dx_i, sum_i (x_i - c) x dE/dx_i} (c = ligand centroid); grad_tor [NTOR]:
+ * sum over the rot_node_mask row of (a x (x_i - x_v)) . dE/dx_i, a = unit (x_u - x_v), (u, v) = (bond_src, bond_dst) of the
+ * torsion's bond -- the sign conventions of the sampler's ligand update.  Any output may be NULL.  One workgroup per pose.    */
+int dbfr_vina_score(const dbfr_vina_in* in, float* terms, float* grad_rigid, float* grad_tor, void* workspace,
+                    size_t workspace_bytes, void* hip_stream);
+/* The same at the pose the minimiser builds from the variables q: q_rigid [G,6] = (translation, rotation vector), q_tor [NTOR]
+ * torsion angles (radians), either may be NULL = 0; the positions are rebuilt from batch->lig_pos as in dbfr_vina_minimize and
+ * written to lig_pos_out [NL,3] (may be NULL); grad_rigid / grad_tor receive dE/dq -- the gradient the minimiser follows (at
+ * q = 0 it is the generalised gradient above).                                                                              */
+int dbfr_vina_score_at(const dbfr_vina_in* in, const float* q_rigid, const float* q_tor, float* lig_pos_out, float* terms,
+                       float* grad_rigid, float* grad_tor, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* BFGS over q = (translation, rotation vector, torsions) with a backtracking (Armijo) line search whose first trial moves no
+ * variable by more than 0.3 (A or rad: a local search); positions are rebuilt from
+ * batch->lig_pos for every trial q: torsions in tor_bond order about the current bond axis (pivot x_v), then the rotation
+ * about the centroid, then the translation.  lig_pos_out [NL,3] (may be NULL; equal to batch->lig_pos = in place) receives
+ * the final poses, terms [G,8] their terms as above, iters [G] the accepted steps.  A pose stops at max |dE/dq| < grad_tol,
+ * after max_iters steps, or when not even a steepest-descent step lowers the objective any more.  opts NULL = defaults.     */
+int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* terms, int32_t* iters,
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Synchronises the stream and returns the device-side status word of the last
  * dbfr_score / dbfr_sample issued with this workspace (DBFR_OK, DBFR_ERR_CAPACITY,

@@ -9,5 +9,6 @@ from .registry import INTERACTION, MLDOCK_BUILDER, register_into_druglib  # noqa
 from .score_model import TensorProductModelHIP  # noqa: F401
 from .sampler import DiffBindFRHIP  # noqa: F401
 from . import vina  # noqa: F401
+from . import modes  # noqa: F401
 
 register_into_druglib()

@@ -105,6 +105,17 @@ class VinaOpts(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("grad_tol", C.c_float), ("margin", C.c_float)]
 
 
+class PoseRmsdIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("pose_ptr", C.c_void_p), ("atom_ptr", C.c_void_p), ("perm_ptr", C.c_void_p),
+                ("pos", C.c_void_p), ("perms", C.c_void_p), ("heavy_mask", C.c_void_p), ("max_pose", C.c_int32),
+                ("max_atom", C.c_int32), ("path", C.c_int32), ("tile_rows", C.c_int32)]
+
+
+class ModesOpts(C.Structure):
+    _fields_ = [("num_modes", C.c_int32), ("higher_is_better", C.c_int32), ("min_rmsd", C.c_float), ("cluster_rmsd", C.c_float),
+                ("energy_range", C.c_float)]
+
+
 # every symbol include/dbfr.h declares (tests check that the library exports all of them)
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
@@ -112,7 +123,8 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
-           "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize"]
+           "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
+           "dbfr_pose_rmsd_matrix", "dbfr_select_modes"]
 
 _lib = None
 
@@ -189,6 +201,8 @@ def load():
     lib.dbfr_vina_score.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_vina_score_at.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_vina_minimize.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_pose_rmsd_matrix.argtypes = [C.POINTER(PoseRmsdIn), vp, vp]
+    lib.dbfr_select_modes.argtypes = [C.POINTER(PoseRmsdIn), vp, vp, C.POINTER(ModesOpts), vp, vp, vp, vp]
     if lib.dbfr_abi_version() != 6:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

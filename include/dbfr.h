@@ -35,7 +35,8 @@ extern "C" {
                                 4: + DBFR_GEMM_REDUCE_FIRST (the new default), dbfr_profile_executed_flops; dbfr_model_set_edge_log takes the graph capacity; DBFR_GEMM_SPLIT_BF16_L1 (k_conv2s) retired; dbfr_test_conv2's message rows in that mode hold segment sums;
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
                                 6: + dbfr_profile_useful_flops, dbfr_model_set_tie_log, dbfr_test_reduce_ln2; dbfr_model_set_edge_log accepts batches with fewer graphs than its capacity; an unknown DBFR_GEMM value fails dbfr_model_create;
-                                   later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize */
+                                   later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize,
+                                   dbfr_pose_rmsd_in, dbfr_modes_opts, dbfr_pose_rmsd_matrix, dbfr_select_modes */
 
 typedef enum {
   DBFR_OK = 0,
@@ -460,6 +461,52 @@ int dbfr_vina_score_at(const dbfr_vina_in* in, const float* q_rigid, const float
  * after max_iters steps, or when not even a steepest-descent step lowers the objective any more.  opts NULL = defaults.     */
 int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* terms, int32_t* iters,
                        void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- Distinct binding modes of sampled poses (csrc/modes.hip; docs/modes.md).  A batch of G groups (one group = the poses
+ * of one ligand in one pocket frame), group g holding P_g poses of N_g atoms and n_perm_g automorphisms (identity included):
+ *   R_g[i, j] = min over sigma of sqrt( (1/|H|) sum_{a in H} |x_i[sigma(a)] - x_j[a]|^2 )
+ * without superposition (the pocket frame fixes the pose): the lig_rmsd of dbfr_pose_metrics with pose i as the pose and
+ * pose j as the target.  H = the heavy atoms (heavy_mask, NULL = all atoms).  Only i < j is computed; R_g[j, i] holds the same
+ * bits and the diagonal an exact 0.  Every (pose pair, automorphism) sum runs serially over the atoms in index order, so a
+ * group's matrix is bitwise the same alone or in any batch, whatever the path and tiling.  Groups of at most 4096 poses
+ * and 1024 atoms.                                                                                                           */
+typedef struct {
+  int32_t        n_group;
+  const int32_t* pose_ptr;   /* [G+1] first pose of every group (P_g = pose_ptr[g+1] - pose_ptr[g])                       */
+  const int32_t* atom_ptr;   /* [G+1] first atom of every group (N_g); heavy_mask is indexed by atom_ptr[g] + a           */
+  const int32_t* perm_ptr;   /* [G+1] first automorphism of every group (n_perm_g >= 1)                                   */
+  const float*   pos;        /* group by group [P_g, N_g, 3]: group g starts at float 3 * sum_{h<g} P_h N_h              */
+  const int32_t* perms;      /* group by group [n_perm_g, N_g]: group g starts at sum_{h<g} n_perm_h N_h; atom perms[p][a]
+                                of pose i is compared with atom a of pose j (the convention of dbfr_pose_metrics_in)       */
+  const int32_t* heavy_mask; /* [atom_ptr[G]] 0/1, or NULL = every atom counts                                            */
+  int32_t        max_pose;   /* host-known maxima over the groups (<= 4096 poses, <= 1024 atoms); a group above them gets */
+  int32_t        max_atom;   /*   NaN everywhere in its matrix (and -1 / 0 in the selection outputs)                     */
+  int32_t        path;       /* 0 = by group (a lane per pose pair below 32 automorphisms, a wave per pair from 32 on);
+                                1 / 2 = always the lane / wave path (same bits; for tests and tuning)                       */
+  int32_t        tile_rows;  /* poses per LDS tile, 0 = as many as fit (same bits whatever the value; for tests)         */
+} dbfr_pose_rmsd_in;
+
+/* rmsd_out [sum_g P_g^2]: R_g row-major at out_off[g] = sum_{h<g} P_h^2.  One launch for the whole batch.                */
+int dbfr_pose_rmsd_matrix(const dbfr_pose_rmsd_in* in, float* rmsd_out, void* hip_stream);
+
+typedef struct {
+  int32_t num_modes;         /* at most this many modes per group, 0 = unlimited (default 9)                              */
+  int32_t higher_is_better;  /* 0: lower score is better (Vina affinity), 1: higher is better (MDN score)                  */
+  float   min_rmsd;          /* a kept mode lies at least this far from every better mode, > 0 (default 1 A)             */
+  float   cluster_rmsd;      /* a pose joins its nearest mode within this RMSD, >= min_rmsd (default 2 A)                 */
+  float   energy_range;      /* keep only modes scoring within this of the best (lower is better only); < 0 = off        */
+} dbfr_modes_opts;
+
+/* Per group, on one workgroup: the poses ordered by score (ties by pose index, NaN scores last); a greedy walk keeps a pose
+ * when its RMSD to every mode kept so far is >= min_rmsd (NaN RMSD: not kept) and its score lies within energy_range of the
+ * best, and stops after num_modes modes or at the first NaN score (never kept); every pose then joins the kept mode of
+ * smallest RMSD (ties: the better-ranked mode) if that RMSD is <= cluster_rmsd.  rmsd = dbfr_pose_rmsd_matrix's output
+ * for the same `in` (only n_group and pose_ptr / max_pose are read), score [pose_ptr[G]].  Outputs (device): mode_rank
+ * [pose_ptr[G]] = the pose's rank among the modes or -1, mode_id [pose_ptr[G]] = the rank of the mode whose cluster the
+ * pose joined or -1, cluster_size [pose_ptr[G]]: entry pose_ptr[g] + r = the poses in the cluster of mode r of group g
+ * (0 from the number of modes on).  Groups of at most 4096 poses (max_pose above that: DBFR_ERR_ARG).  opts NULL = defaults. */
+int dbfr_select_modes(const dbfr_pose_rmsd_in* in, const float* rmsd, const float* score, const dbfr_modes_opts* opts,
+                      int32_t* mode_rank, int32_t* mode_id, int32_t* cluster_size, void* hip_stream);
 
 /* Synchronises the stream and returns the device-side status word of the last
  * dbfr_score / dbfr_sample issued with this workspace (DBFR_OK, DBFR_ERR_CAPACITY,

@@ -10,5 +10,6 @@ from .score_model import TensorProductModelHIP  # noqa: F401
 from .sampler import DiffBindFRHIP  # noqa: F401
 from . import vina  # noqa: F401
 from . import modes  # noqa: F401
+from . import posecheck  # noqa: F401
 
 register_into_druglib()

@@ -116,6 +116,23 @@ class ModesOpts(C.Structure):
                 ("energy_range", C.c_float)]
 
 
+class PoseCheckIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "pocket_ptr", "pocket_pos_off",
+                                          "pocket_pos", "pocket_rad", "static_ptr", "static_pos", "static_rad", "pair_ptr", "pair_ij",
+                                          "flat_ptr", "flat_atoms", "stereo_ptr", "stereo_atoms", "stereo_sign")] + \
+               [(n, C.c_int32) for n in ("max_lig", "max_pair", "max_flat", "max_stereo", "cand_cap")]
+
+
+class PoseCheckOpts(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("clash_ratio", "max_distance", "vol_scale", "vol_overlap", "internal_ratio", "flat_tol", "grid")]
+
+
+class PoseCheckOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("min_dist", "min_ratio", "n_clash", "vol_lig", "vol_overlap", "int_min_ratio", "n_int_clash",
+                                          "flat_dev", "n_stereo_flip", "passed")]
+
+
 # every symbol include/dbfr.h declares (tests check that the library exports all of them)
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
@@ -124,7 +141,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
-           "dbfr_pose_rmsd_matrix", "dbfr_select_modes"]
+           "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check"]
 
 _lib = None
 
@@ -203,6 +220,7 @@ def load():
     lib.dbfr_vina_minimize.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_pose_rmsd_matrix.argtypes = [C.POINTER(PoseRmsdIn), vp, vp]
     lib.dbfr_select_modes.argtypes = [C.POINTER(PoseRmsdIn), vp, vp, C.POINTER(ModesOpts), vp, vp, vp, vp]
+    lib.dbfr_pose_check.argtypes = [C.POINTER(PoseCheckIn), C.POINTER(PoseCheckOpts), C.POINTER(PoseCheckOut), vp]
     if lib.dbfr_abi_version() != 6:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

@@ -36,7 +36,8 @@ extern "C" {
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
                                 6: + dbfr_profile_useful_flops, dbfr_model_set_tie_log, dbfr_test_reduce_ln2; dbfr_model_set_edge_log accepts batches with fewer graphs than its capacity; an unknown DBFR_GEMM value fails dbfr_model_create;
                                    later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize,
-                                   dbfr_pose_rmsd_in, dbfr_modes_opts, dbfr_pose_rmsd_matrix, dbfr_select_modes */
+                                   dbfr_pose_rmsd_in, dbfr_modes_opts, dbfr_pose_rmsd_matrix, dbfr_select_modes,
+                                   dbfr_pose_check_in, dbfr_pose_check_opts, dbfr_pose_check_out, dbfr_pose_check */
 
 typedef enum {
   DBFR_OK = 0,
@@ -507,6 +508,83 @@ typedef struct {
  * (0 from the number of modes on).  Groups of at most 4096 poses (max_pose above that: DBFR_ERR_ARG).  opts NULL = defaults. */
 int dbfr_select_modes(const dbfr_pose_rmsd_in* in, const float* rmsd, const float* score, const dbfr_modes_opts* opts,
                       int32_t* mode_rank, int32_t* mode_id, int32_t* cluster_size, void* hip_stream);
+
+/* ---- PoseBusters-style physical validity checks of poses (csrc/posecheck.hip; docs/posecheck.md).  A batch of G groups (one
+ * group = the frames of one ligand in one complex), group g holding F_g frames of N_g ligand heavy atoms (L), M_g pocket atoms
+ * per frame and S_g static receptor atoms shared by its frames; R = pocket + static atoms.  r = van der Waals radii (given per
+ * atom).  Per frame:
+ *   min_dist    d_min = min over a in L, b in R of d_ab                     (protein-ligand_maximum_distance: d_min <= max_distance)
+ *   min_ratio   rho = min d_ab / (r_a + r_b); n_clash = pairs with ratio < clash_ratio (minimum_distance_to_protein: rho >= clash_ratio)
+ *   vol_lig, vol_overlap  on the lattice {grid * k, k in Z^3}: V_L = points p with |p - x_a| < vol_scale * r_a for some a in L,
+ *               V_R the same over R; |V_L| and |V_L n V_R|           (volume_overlap_with_protein: |V_L n V_R| / |V_L| <= vol_overlap)
+ *   int_min_ratio  min d / (r_a + r_b) over the listed internal pairs (+inf: none); n_int_clash = pairs below internal_ratio
+ *                                                                       (internal_steric_clash: int_min_ratio >= internal_ratio)
+ *   flat_dev    over the listed flatness bonds: the largest distance of a bond's atoms from their least-squares plane (0: none)
+ *                                                                       (double_bond_flatness: flat_dev <= flat_tol)
+ *   n_stereo_flip  stereo bonds (s_u, u, v, s_v) whose sign of cos(dihedral) differs from the given input sign
+ *                                                                       (double_bond_stereochemistry: n_stereo_flip == 0)
+ * Every reduction is a minimum, a maximum or an integer count, so a frame's outputs are bitwise the same alone or in any batch.
+ * Limits: N_g <= 256 ligand atoms, <= 32640 internal pairs, <= 64 flatness and <= 64 stereo bonds per group (max_* above them:
+ * DBFR_ERR_ARG).  Receptor atoms are not limited; the receptor atoms close enough to a ligand atom to share a lattice point with
+ * it (d_ab < vol_scale (r_a + r_b) + 0.01) are compacted into LDS, at most 2048 per frame: beyond that the lattice pass of the
+ * frame tests every receptor atom from memory instead (same bits, slower).                                                 */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; outputs are indexed by frame                          */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_rad (N_g = lig_ptr[g+1] - lig_ptr[g], >= 1)       */
+  const int64_t* lig_pos_off;    /* [G] first row of group g in lig_pos: frame k of g at rows lig_pos_off[g] + k N_g           */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const float*   lig_rad;        /* [lig_ptr[G]] radii in (0, 4]                                                            */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_rad (M_g atoms per frame, may be 0)     */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                         */
+  const float*   pocket_pos;
+  const float*   pocket_rad;
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / static_rad, or NULL = none              */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of lig_pos                                              */
+  const float*   static_rad;
+  const int32_t* pair_ptr;       /* [G+1] internal pairs of every group                                                     */
+  const int32_t* pair_ij;        /* [pair_ptr[G], 2] local ligand atom indices                                              */
+  const int32_t* flat_ptr;       /* [G+1] flatness bonds of every group                                                     */
+  const int32_t* flat_atoms;     /* [flat_ptr[G], 8] local atom indices of the fitted atoms (>= 4), -1 padded               */
+  const int32_t* stereo_ptr;     /* [G+1] stereo bonds of every group                                                       */
+  const int32_t* stereo_atoms;   /* [stereo_ptr[G], 4] (s_u, u, v, s_v) local atom indices                                  */
+  const int8_t*  stereo_sign;    /* [stereo_ptr[G]] +1 / -1: sign of cos(dihedral) in the input conformer                    */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 32640, 64, 64); a group above them gets NaN    */
+  int32_t        max_pair;       /*   outputs, -1 counts and passed = 0                                                     */
+  int32_t        max_flat;
+  int32_t        max_stereo;
+  int32_t        cand_cap;       /* receptor candidates kept in LDS per frame, 0 = 2048 (same bits whatever the value; tests) */
+} dbfr_pose_check_in;
+
+typedef struct {
+  float clash_ratio;             /* minimum_distance_to_protein threshold, default 0.75                                     */
+  float max_distance;            /* protein-ligand_maximum_distance threshold (A), default 5.0                              */
+  float vol_scale;               /* sphere radius = vol_scale * r for the lattice, (0, 2], default 0.8                       */
+  float vol_overlap;             /* volume_overlap_with_protein threshold, default 0.075                                    */
+  float internal_ratio;          /* internal_steric_clash threshold, default 0.7                                            */
+  float flat_tol;                /* double_bond_flatness threshold (A), default 0.25                                        */
+  float grid;                    /* lattice spacing h (A), [0.05, 1], default 0.25                                           */
+} dbfr_pose_check_opts;
+
+typedef struct {                 /* device arrays [n_frame]; any may be NULL                                                */
+  float*   min_dist;
+  float*   min_ratio;
+  int32_t* n_clash;
+  int32_t* vol_lig;
+  int32_t* vol_overlap;
+  float*   int_min_ratio;
+  int32_t* n_int_clash;
+  float*   flat_dev;
+  int32_t* n_stereo_flip;
+  int32_t* passed;               /* bit k = check k passed, in the order minimum_distance_to_protein, protein-ligand_maximum_
+                                    distance, volume_overlap_with_protein, internal_steric_clash, double_bond_flatness,
+                                    double_bond_stereochemistry; bit 6 = all six (pb_valid)                                 */
+} dbfr_pose_check_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_pose_check(const dbfr_pose_check_in* in, const dbfr_pose_check_opts* opts, const dbfr_pose_check_out* out,
+                    void* hip_stream);
 
 /* Synchronises the stream and returns the device-side status word of the last
  * dbfr_score / dbfr_sample issued with this workspace (DBFR_OK, DBFR_ERR_CAPACITY,

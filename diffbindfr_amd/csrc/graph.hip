@@ -648,8 +648,11 @@ void launch_edge_log(const GraphArgs& A0, int* log_row, int stride, hipStream_t 
 // Diagnostic (dbfr_model_set_tie_log; never on the data path): per graph and edge set, the number of candidate pairs whose distance lies within `tol` of
 // the set's hard cutoff -- the pairs at which two runs that differ by rounding may build different graphs (the reference's radius graphs have no soft
 // edge).  Distances as the edge builder forms them (d2_rn of the staged coordinates, the cross sets in units of the graph's dynamic cutoff, pseudotorque
-// sets from the bond mid-point); a pair counts when |d - cutoff| <= tol, i.e. |d2 - cut2| <= 2 cutoff tol (+ tol^2).  One workgroup per (graph, set);
-// the cross sets 2 and 3 hold the same pairs.  The 32-neighbour caps (by index, not by distance) have no ties.
+// sets from the bond mid-point); a pair counts when |d - cutoff| <= tol, i.e. (cutoff - tol)^2 <= d2 <= (cutoff + tol)^2: d2 - cut2 at most
+// 2 cutoff tol + tol^2 above and 2 cutoff tol - tol^2 below (one symmetric bound of 2 cutoff tol + tol^2 would reach tol^2 / cutoff below the window).
+// One workgroup per (graph, set); the cross sets 2 and 3 hold the same pairs.  Candidates: every ligand pair, bonded ones included (the reference's
+// ligand set is the bonds AND a radius graph over all pairs); ligand x pocket pairs except CA / CB atoms (edges whatever their distance); no
+// 32-neighbour cap (a cap keeps in-range points by index, so pairs it drops are counted too: the read-out may over-flag there, never under-flag).
 __global__ void k_edge_ties(GraphArgs A, int* log, int stride, float tol) {
   const int g = blockIdx.x, k = blockIdx.y;
   const EdgeSet& S = A.set[k];
@@ -661,7 +664,10 @@ __global__ void k_edge_ties(GraphArgs A, int* log, int stride, float tol) {
     const int l0 = A.b.lig_ptr[g], nl = A.b.lig_ptr[g + 1] - l0, a0 = A.b.atm_ptr[g], na = A.b.atm_ptr[g + 1] - a0;
     const float* LP = A.b.lig_pos;
     const float* RP = A.b.rec_pos;
-    auto near = [&](float d2, float cut2, float t) { const float cut = sqrtf(cut2); return fabsf(d2 - cut2) <= 2.f * cut * t + t * t; };
+    auto near = [&](float d2, float cut2, float t) {
+      const float cut = sqrtf(cut2), e = d2 - cut2;
+      return e <= 2.f * cut * t + t * t && (t >= cut || -e <= 2.f * cut * t - t * t);
+    };
     if (k == SET_LL || k == SET_AA) {
       const float* P = k == SET_LL ? LP : RP;
       const int p0 = k == SET_LL ? l0 : a0, np = k == SET_LL ? nl : na;

@@ -283,9 +283,10 @@ class TensorProductModelHIP(nn.Module):
 
     def tie_log(self, device, n_steps, G, tol=1e-5):
         """The companion of ``edge_log`` (``dbfr_model_set_tie_log``): device int32 tensor [n_steps, 6, G] = per step, edge set and graph the number of
-        candidate pairs within ``tol`` Angstrom of the set's hard cutoff -- where two runs that differ by rounding (another GEMM mode, the reference
-        on another batch) may build different graphs.  All-zero rows: the step's graphs are decided by margins above ``tol``.  ``n_steps = 0``
-        switches it off."""
+        candidate pairs with ``|d - cutoff| <= tol`` (Angstrom) for the set's hard cutoff -- where two runs that differ by rounding (another GEMM
+        mode, the reference on another batch) may build different graphs.  Candidates as include/dbfr.h states them: bonded ligand pairs count,
+        CA / CB atoms never count in the cross sets, neighbour caps are ignored (over-flags past a cap, never under-flags).  All-zero rows: the
+        step's graphs are decided by margins above ``tol``.  ``n_steps = 0`` switches it off."""
         dev = torch.device(device)
         if not isinstance(getattr(self, "_tie_log", None), dict):
             self._tie_log = {}

@@ -212,11 +212,15 @@ int dbfr_capacity_report(void* workspace, void* hip_stream, int32_t* first_faile
  * coordinates differ in the 5th decimal build different graphs exactly where a pair sits within rounding distance of a cutoff
  * (tests/test_examples.py).                                                                                                        */
 int dbfr_model_set_edge_log(dbfr_model* m, int32_t* log_dev, int32_t n_steps_cap, int32_t n_graphs_cap);
-/* (ABI 6) The companion read-out: ties[(s * 6 + k) * n_graphs_cap + g] = the number of candidate pairs of graph g in edge set k whose distance lies within
- * `tol` (Angstrom, > 0) of the set's hard cutoff at step s -- the pairs at which two runs that differ by rounding (another DBFR_GEMM mode, another
- * batch of the reference) may build different graphs.  A zero row means the step's graph is decided by margins above tol; tools/validate_checkpoint.py
- * and tests/test_examples.py read it next to the edge counts.  Diagnostic: its kernel is launched only while a log is attached.  Same layout, capacity
- * rule and switch-off (log == NULL) as dbfr_model_set_edge_log.                                                                                */
+/* (ABI 6) The companion read-out: ties[(s * 6 + k) * n_graphs_cap + g] = the number of candidate pairs of graph g in edge set k whose distance d
+ * satisfies |d - cutoff| <= `tol` (Angstrom, > 0) for the set's hard cutoff at step s -- the pairs at which two runs that differ by rounding (another
+ * DBFR_GEMM mode, another batch of the reference) may build different graphs.  Candidates: set 0 every ligand pair, BONDED PAIRS INCLUDED (the
+ * reference's ligand set is the bond edges concatenated with a radius graph over all pairs, so a bonded pair across 5 A changes the edge count
+ * too); set 1 every pocket pair; sets 2 and 3 (the same pairs) ligand x pocket atoms other than CA / CB (edges at any distance), in units of the
+ * graph's dynamic cutoff 0.2 tr_sigma + 5; sets 4 and 5 the bond mid-point x every atom of the graph.  The neighbour caps are ignored: pairs past
+ * a cap count too, so the log may over-flag there but never under-flag.  A zero row means the step's graph is decided by margins above tol;
+ * tests/test_examples.py reads it next to the edge counts.  Diagnostic: its kernel is launched only while a log is attached.  Same layout,
+ * capacity rule and switch-off (log == NULL) as dbfr_model_set_edge_log.                                                                    */
 int dbfr_model_set_tie_log(dbfr_model* m, int32_t* log_dev, int32_t n_steps_cap, int32_t n_graphs_cap, float tol);
 
 /* ---- pose initialisation, on the device.

@@ -17,8 +17,8 @@
                   rounding flips it and ends 1e-2 .. 5e-1 A away -- eight seeds in a row were rejected by the robustness search of `cfg_trajectory`
                   (second oracle run from coordinates moved by N(0, 1e-5 A): 2e-2 .. 6e-1 A apart after 20 steps; round 6, 2.3 CPU hours).  Held step
                   by step the comparison does not amplify: tests/test_gpu_parity.py::test_cfg5_batch_scores_step_by_step feeds the library the oracle's
-                  state and compares the scores graph by graph, with the library's own near-tie read-out (dbfr_model_set_tie_log) deciding which
-                  graphs of which step sit at a cutoff.
+                  state and compares the scores graph by graph.  At the four kept states no candidate pair lies within 1e-5 A of its cutoff (float64;
+                  the test checks this first): a fixture regenerated with other seeds must keep that, or keep other steps that do.
 """
 import copy
 import os

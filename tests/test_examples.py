@@ -36,7 +36,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import GOLDEN
+from tests.helpers import GOLDEN, HIP_SETS, SETS, oracle_counts as _oracle_counts
 
 FIXTURES = ["real_forward15_traj.npz", "real_reverse_traj.npz"]
 LIG_KEYS = ("lig_node", "lig_pos", "lig_edge_index", "lig_edge_feat", "tor_edge_mask", "rot_node_mask")
@@ -112,42 +112,11 @@ def _deviation(z, pb, lig, a14):
     return [float(dl[:, lp[g]:lp[g + 1]].max()) for g in range(G)], [float(da[rp[g]:rp[g + 1]].max()) for g in range(G)]
 
 
-SETS = ("lig", "atom", "cross", "tor", "sc")        # the reference's five per-step edge sets (fixture order)
-HIP_SETS = (0, 1, 2, 4, 5)                          # the library's six: {lig, atom, cross lig<-atom, cross atom<-lig, tor, sc}
-
-
 def _per_step_deviation(z, pb, lig):
     """[G, 20]: largest ligand-atom deviation from the reference of graph g in frame s (= after step s)."""
     dl = (lig.cpu() - torch.from_numpy(z["traj_lig"])).norm(dim=-1)
     lp = pb.lig_ptr_host.tolist()
     return np.stack([dl[:, lp[g]:lp[g + 1]].max(dim=1).values.numpy() for g in range(len(lp) - 1)])
-
-
-def _oracle_counts(pb, g, lig_xyz, rec_xyz, tr_sigma):
-    """The five edge counts of graph g for the given coordinates by the oracle's restated torch_cluster calls, as the reference's
-    builders make them (tpscore.py:586, 613, 655-660, 721, 747)."""
-    from oracle.cluster import radius, radius_graph
-    t = {k: v.cpu() for k, v in pb.t.items() if k in ("lig_ptr", "atm_ptr", "bond_src", "bond_dst", "bond_ptr", "tor_ptr", "tor_bond",
-                                                     "sc_ptr", "sc_bond", "pocket_feat")}
-    l0, l1, a0, a1 = int(t["lig_ptr"][g]), int(t["lig_ptr"][g + 1]), int(t["atm_ptr"][g]), int(t["atm_ptr"][g + 1])
-    n_bond = int(t["bond_ptr"][l1] - t["bond_ptr"][l0])
-    lig = int(radius_graph(lig_xyz, 5.0).shape[1]) + n_bond
-    atom = int(radius_graph(rec_xyz, 4.0, max_num_neighbors=1000).shape[1])
-    a37 = t["pocket_feat"][a0:a1, 0].long()
-    cab = (a37 == 1) | (a37 == 3)
-    c = torch.tensor(tr_sigma, dtype=torch.float32) * 0.2 + 5
-    cross = (l1 - l0) * int(cab.sum()) + int(radius(rec_xyz[~cab] / c, lig_xyz / c, 1, max_num_neighbors=10000).shape[1])
-    tb = t["tor_bond"][int(t["tor_ptr"][g]):int(t["tor_ptr"][g + 1])].long()
-    tor = 0
-    if len(tb):
-        mid = (lig_xyz[t["bond_src"][tb].long() - l0] + lig_xyz[t["bond_dst"][tb].long() - l0]) / 2
-        tor = int(radius(lig_xyz, mid, 5.0).shape[1])
-    sb = t["sc_bond"].view(-1, 2)[int(t["sc_ptr"][g]):int(t["sc_ptr"][g + 1])].long() - a0
-    sc = 0
-    if len(sb):
-        mid = (rec_xyz[sb[:, 0]] + rec_xyz[sb[:, 1]]) / 2
-        sc = int(radius(rec_xyz, mid, 4.0).shape[1])
-    return [lig, atom, cross, tor, sc]
 
 
 def _oracle_rerun(z, samp, jobs, tapes, raws, g, s0, dev):

@@ -2,7 +2,7 @@
 """Benchmark of the MI355X-native DiffBindFR sampler (BASELINE.json metric: poses/sec).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|1] [--batch-poses B] [--scaling weak|strong]
-                    [--jobs J] [--store device|host] [--gather all|root] [--dump-outputs DIR]
+                    [--jobs J] [--store device|host] [--gather all|root] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no torchrun environment: the script spawns its own N ranks (one process per GPU, LOCAL_RANK -> cuda:LOCAL_RANK,
 rendezvous on 127.0.0.1), relays rank 0's ONE JSON line and returns the ranks' worst exit code; under `python -m torch.distributed.run
@@ -20,8 +20,11 @@ BASELINE.json configs[1] (128 complexes x 40 poses = 5120 poses); with any K >= 
 the rate over the first 5120 poses.  --config 3 / 4: every job shares ONE receptor /
 ONE ligand record (forward screen / target fishing).  Per-complex records are resident in HBM before the timed region
 (uploaded once per ligand / pocket); fp32 arithmetic throughout (the reference runs fp32).  Rank 0 prints ONE JSON line.
-After the timed region (N = 1) the script measures the dominant kernel's HBM traffic itself: two child runs of one batch under
-`rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (`--no-pmc` skips them), then the latency cases and the CPU-oracle baseline.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; its `roofline` comes from the library's
+own events of the timed steps (`traffic`: the PMC constant of profiles/ where one fits the workload).  `--full` (N = 1) adds what takes runs of its own
+after the timed region: the dominant kernel's HBM traffic measured by two child runs of one batch under `rocprofv3 --pmc FETCH_SIZE` /
+`--pmc WRITE_SIZE`, the bare matrix-pipe probe (split_f16), one batch through the fp32-instruction kernels, the latency cases and the
+CPU-oracle baseline with its parity check; `--no-pmc`, `--no-probe`, `--no-native`, `--no-latency` and `--no-cpu-baseline` drop single legs of it.
 `--dump-outputs DIR` writes the poses of the last timed step as DIR/<name>.npy (see dump_outputs): the inputs are seeded, so two
 builds run with the same arguments can be compared output for output.
 """
@@ -453,7 +456,11 @@ def main():
                                                                           "the screening configs 3 / 4 on more than one GPU: 10 k ligands x 40 poses are written out by one rank)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the poses of the last one as DIR/<name>.npy "
                                                                          "(float32, at most 64 MB: a fixed seeded sample of the poses beyond that)")
+    ap.add_argument("--full", action="store_true", help="after the line's own measurement, also run the legs that take runs of their own (one GPU): PMC "
+                                                        "passes, matrix-pipe probe, fp32-instruction batch, latency cases, CPU baseline and parity")
     args = ap.parse_args()
+    if not args.full:       # a plain run does what its headline needs and no more
+        args.no_pmc = args.no_probe = args.no_native = args.no_latency = args.no_cpu_baseline = True
     ppc = synthetic.CONFIGS[args.config]["poses"]
     if args.jobs is None and args.batch_poses < ppc:
         ap.error(f"--batch-poses {args.batch_poses} < the {ppc} poses of a config-{args.config} job: a job would be cut over several "
@@ -589,7 +596,7 @@ def main():
             # kernel: 3 x 2 x 144 x (144 + vector-output rows) per edge; k_convz: the matrix instructions it issues x 16384)
             ex = exe.value / (ms.value * 1e-3) / 1e12
         traffic, tsrc, traw = None, "no PMC pass for this workload", None
-        live, why = (None, "--no-pmc") if (args.no_pmc or world != 1 or mode != main_mode) else measure_traffic(mode, args)
+        live, why = (None, "--no-pmc" if args.full else "no PMC pass (a run without --full)") if (args.no_pmc or world != 1 or mode != main_mode) else measure_traffic(mode, args)
         if live is not None:
             traffic = 2.0 * live["FETCH_SIZE"] + live["WRITE_SIZE"]
             traw = {"fetch_size_raw": live["FETCH_SIZE"], "write_size": live["WRITE_SIZE"], "dispatches": live["dispatches"]}

@@ -445,6 +445,21 @@ def test_bench_dumps_the_poses_of_its_last_step(tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_runs_only_what_its_line_needs():
+    """`bench.py` without `--full`: the line carries the headline and the roofline read from its own timed steps, and none of the legs
+    that take runs of their own (PMC child passes, the fp32-instruction batch, the latency cases, the CPU baseline)."""
+    import json
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--batch-poses", "80"],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][0])
+    assert line["value"] > 0 and line["steps"] == 1 and line["config"]["poses_total"] == 80
+    assert not {"native_f32", "latency", "cpu_baseline"} & set(line), sorted(line)
+    roof = line["roofline"]
+    assert roof["launches"] > 0 and roof["traffic_counters"] is None and roof["traffic_source"].startswith("no PMC pass (a run without --full)")
+
+
+@pytest.mark.gpu
 def test_bench_spawns_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it (the driver's own command form): the script starts its two ranks itself
     (LOCAL_RANK -> device, rendezvous on 127.0.0.1), rank 0's ONE line comes back through the parent, and the line shows that the

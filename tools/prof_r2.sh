@@ -7,10 +7,10 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r2prof
 mkdir -p $OUT
 cd $R
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-for c in 3 4; do timeout 200 python bench.py --config $c --steps 2 --no-cpu-baseline --no-latency > $OUT/bench_cfg$c.json 2>/dev/null; done
-timeout 200 python bench.py --config 5 --steps 2 --batch-poses 160 --no-cpu-baseline --no-latency > $OUT/bench_cfg5.json 2>/dev/null
-timeout 300 python bench.py --config 2 --steps 2 --scaling strong --no-cpu-baseline --no-latency > $OUT/bench_strong1.json 2>/dev/null
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+for c in 3 4; do timeout 200 python bench.py --config $c --steps 2 --no-cpu-baseline --no-latency --full > $OUT/bench_cfg$c.json 2>/dev/null; done
+timeout 200 python bench.py --config 5 --steps 2 --batch-poses 160 --no-cpu-baseline --no-latency --full > $OUT/bench_cfg5.json 2>/dev/null
+timeout 300 python bench.py --config 2 --steps 2 --scaling strong --no-cpu-baseline --no-latency --full > $OUT/bench_strong1.json 2>/dev/null
 # the N>1 path on one GPU: 2 ranks share cuda:0, records staged through the host for the gloo gather
 DBFR_DIST_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
   bench.py --gpus 2 --steps 1 --warmup 0 --batch-poses 320 --no-profile > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err
@@ -30,7 +30,7 @@ done
 python $R/tools/pmc_summary.py "$OUT/p*/*counter_collection.csv" | head -80 > $OUT/pmc_summary_b640.txt
 python $R/tools/pmc_to_json.py $OUT/pmc_summary_b640.txt k_conv2r $OUT/pmc_k_conv2r.json
 # the fp32-instruction kernels for the record (the bench line's native_f32 leg is one batch; this is the whole default command)
-cd $R; DBFR_GEMM=f32 timeout 400 python bench.py --no-cpu-baseline --no-latency > $OUT/bench_gemm_f32.json 2>/dev/null; DBFR_GEMM=split_l1 timeout 400 python bench.py --steps 2 --no-cpu-baseline --no-latency --no-native > $OUT/bench_gemm_split_l1.json 2>/dev/null
+cd $R; DBFR_GEMM=f32 timeout 400 python bench.py --no-cpu-baseline --no-latency --full > $OUT/bench_gemm_f32.json 2>/dev/null; DBFR_GEMM=split_l1 timeout 400 python bench.py --steps 2 --no-cpu-baseline --no-latency --no-native > $OUT/bench_gemm_split_l1.json 2>/dev/null
 rm -rf $OUT/p[0-9]
 head -30 $OUT/pmc_summary_b640.txt
 head -6 $OUT/kernel_stats_steps2_b640.csv

@@ -32,11 +32,11 @@ stats() {  # stats <tag> <bench args...>
 Q="--no-cpu-baseline --no-latency --no-native --no-pmc"
 if [ $WHAT = all ] || [ $WHAT = lines ]; then
   cd $R
-  timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   for c in 3 4; do timeout 300 python bench.py --config $c --steps 2 $Q > $OUT/bench_cfg$c.json 2>/dev/null; done
   timeout 400 python bench.py --gpus 1 --steps 20 --warmup 1 > $OUT/bench_driver_style_steps20.json 2> $OUT/bench_driver_style_steps20.err
   timeout 300 python bench.py --config 2 --steps 2 --scaling strong $Q > $OUT/bench_strong1.json 2>/dev/null
-  timeout 300 python bench.py --config 1 --batch-poses 4 --steps 1 --no-native --no-latency > $OUT/bench_cfg1_1x4.json 2>/dev/null
+  timeout 300 python bench.py --config 1 --batch-poses 4 --steps 1 --no-native --no-latency --full > $OUT/bench_cfg1_1x4.json 2>/dev/null
   # the N>1 path on one GPU: 2 ranks share cuda:0, records staged through the host for the gloo gather
   DBFR_DIST_BACKEND=gloo HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 \
     bench.py --gpus 2 --steps 1 --warmup 0 --batch-poses 320 --no-profile > $OUT/bench_2rank_gloo.json 2> $OUT/bench_2rank_gloo.err
@@ -67,7 +67,7 @@ if [ $WHAT = all ] || [ $WHAT = cfg2 ]; then
   pmc cfg2 --steps 1 --warmup 0 --batch-poses 640 --no-profile $Q
 fi
 if [ $WHAT = all ] || [ $WHAT = cfg5 ]; then
-  cd $R; timeout 900 python bench.py --config 5 --steps 4 --warmup 1 --batch-poses 640 --no-latency --no-native --cpu-batched-steps 0 > $OUT/bench_cfg5_64x40.json 2> $OUT/bench_cfg5_64x40.err; cd /tmp
+  cd $R; timeout 900 python bench.py --config 5 --steps 4 --warmup 1 --batch-poses 640 --no-latency --no-native --cpu-batched-steps 0 --full > $OUT/bench_cfg5_64x40.json 2> $OUT/bench_cfg5_64x40.err; cd /tmp
   tail -c 600 $OUT/bench_cfg5_64x40.err
   stats cfg5 --config 5 --steps 1 --warmup 1 --batch-poses 640 $Q
   pmc cfg5 --config 5 --steps 1 --warmup 0 --batch-poses 640 --no-profile $Q

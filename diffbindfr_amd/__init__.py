@@ -11,5 +11,6 @@ from .sampler import DiffBindFRHIP  # noqa: F401
 from . import vina  # noqa: F401
 from . import modes  # noqa: F401
 from . import posecheck  # noqa: F401
+from . import trajectory  # noqa: F401
 
 register_into_druglib()

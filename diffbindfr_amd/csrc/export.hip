@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -418,6 +419,37 @@ inline void pad80(std::string& out, const char* s, int n) {
   out.push_back('\n');
 }
 
+// The walk over the records of one structure, shared by the text writer and the XTC atom map (dbfr_pdb_atom_map), so that
+// both list the same atoms in the same order.  on_atom(i, a, row, slot, p): ATOM record of atom37 slot a of residue i; row >= 0:
+// the coordinate is atom14 slot `slot` of pos14 row `row`, else p points to the static coordinate the record prints.
+// on_ter(i): the TER record behind residue i.
+template <class OnAtom, class OnTer>
+void walk_structure(const dbfr_pdb_topology& t, const std::vector<int>& row_of, bool any_rows, OnAtom on_atom, OnTer on_ter) {
+  for (int i = 0; i < t.n_res; ++i) {
+    const int aa = t.aatype[i];
+    for (int a = 0; a < 37; ++a) {
+      if (t.atom37_mask[(size_t)i * 37 + a] < 0.5f) continue;
+      // Protein.pos_update with an atom14 array: atom37 slot a reads atom14 slot kAtom37ToAtom14[aa][a] (slot 0 for atoms
+      // outside the residue type's atom14 set, e.g. OXT).  Residues the pose does not cover went through
+      // Protein.to_pos14(True) first (export.py:262): masked by the type's atom14 set, so 'UNK' residues come out at 0.
+      float via14[3];
+      const float* p = nullptr;
+      const int slot = host_tables::kAtom37ToAtom14[aa][a];
+      if (row_of[i] < 0) {
+        if (!any_rows) p = t.atom37_pos + ((size_t)i * 37 + a) * 3;
+        else {
+          const int a37 = host_tables::kAtom14ToAtom37[aa][slot];
+          const float m = (float)host_tables::kAtom14Mask[aa][slot] * t.atom37_mask[(size_t)i * 37 + a37];
+          for (int c = 0; c < 3; ++c) via14[c] = t.atom37_pos[((size_t)i * 37 + a37) * 3 + c] * m;
+          p = via14;
+        }
+      }
+      on_atom(i, a, row_of[i], slot, p);
+    }
+    if (i == t.n_res - 1 || t.chain_index[i] != t.chain_index[i + 1]) on_ter(i);
+  }
+}
+
 // The text of one structure.  Coordinates are float32 values printed through double ("%8.3f" of the exactly converted
 // value, correctly rounded by glibc like Python's float formatting the reference relies on).
 void format_structure(const dbfr_pdb_topology& t, const std::vector<int>& row_of, const float* pos14, int model, int add_end,
@@ -427,43 +459,26 @@ void format_structure(const dbfr_pdb_topology& t, const std::vector<int>& row_of
   char line[192];
   if (t.remark) pad80(out, t.remark, (int)strlen(t.remark));
   long serial = 1;
-  const bool any_rows = pos14 != nullptr;
-  for (int i = 0; i < t.n_res; ++i) {
+  walk_structure(t, row_of, pos14 != nullptr, [&](int i, int a, int row, int slot, const float* p) {
     const int aa = t.aatype[i];
     const std::string tag = chain_tag(t.chain_index[i]);
     const char* rn = host_tables::kRestypeNames3[aa];
-    const int ri = t.residue_index[i];
-    const float* src14 = row_of[i] >= 0 ? pos14 + (size_t)row_of[i] * 42 : nullptr;
-    for (int a = 0; a < 37; ++a) {
-      if (t.atom37_mask[(size_t)i * 37 + a] < 0.5f) continue;
-      const char* atn = host_tables::kAtom37Names[a];
-      // Protein.pos_update with an atom14 array: atom37 slot a reads atom14 slot kAtom37ToAtom14[aa][a] (slot 0 for atoms
-      // outside the residue type's atom14 set, e.g. OXT).  Residues the pose does not cover went through
-      // Protein.to_pos14(True) first (export.py:262): masked by the type's atom14 set, so 'UNK' residues come out at 0.
-      float via14[3];
-      const float* p;
-      if (src14) p = src14 + 3 * host_tables::kAtom37ToAtom14[aa][a];
-      else if (!any_rows) p = t.atom37_pos + ((size_t)i * 37 + a) * 3;
-      else {
-        const int slot = host_tables::kAtom37ToAtom14[aa][a], a37 = host_tables::kAtom14ToAtom37[aa][slot];
-        const float m = (float)host_tables::kAtom14Mask[aa][slot] * t.atom37_mask[(size_t)i * 37 + a37];
-        for (int c = 0; c < 3; ++c) via14[c] = t.atom37_pos[((size_t)i * 37 + a37) * 3 + c] * m;
-        p = via14;
-      }
-      char name[8];
-      if (strlen(atn) == 4) snprintf(name, sizeof name, "%s", atn);
-      else snprintf(name, sizeof name, " %s", atn);
-      int n = snprintf(line, sizeof line, "ATOM  %5ld %-4s %3s %1s%4d    %8.3f%8.3f%8.3f%6.2f%6.2f          %2c  ", serial, name, rn,
-                       tag.c_str(), ri, (double)p[0], (double)p[1], (double)p[2], 1.0, t.b_factors[(size_t)i * 37 + a], atn[0]);
-      pad80(out, line, n);
-      ++serial;
-    }
-    if (i == t.n_res - 1 || t.chain_index[i] != t.chain_index[i + 1]) {
-      int n = snprintf(line, sizeof line, "TER   %5ld      %3s %1s%4d", serial, rn, tag.c_str(), ri);
-      pad80(out, line, n);
-      ++serial;
-    }
-  }
+    const char* atn = host_tables::kAtom37Names[a];
+    if (row >= 0) p = pos14 + (size_t)row * 42 + 3 * slot;
+    char name[8];
+    if (strlen(atn) == 4) snprintf(name, sizeof name, "%s", atn);
+    else snprintf(name, sizeof name, " %s", atn);
+    int n = snprintf(line, sizeof line, "ATOM  %5ld %-4s %3s %1s%4d    %8.3f%8.3f%8.3f%6.2f%6.2f          %2c  ", serial, name, rn,
+                     tag.c_str(), t.residue_index[i], (double)p[0], (double)p[1], (double)p[2], 1.0, t.b_factors[(size_t)i * 37 + a], atn[0]);
+    pad80(out, line, n);
+    ++serial;
+  }, [&](int i) {
+    const std::string tag = chain_tag(t.chain_index[i]);
+    int n = snprintf(line, sizeof line, "TER   %5ld      %3s %1s%4d", serial, host_tables::kRestypeNames3[t.aatype[i]], tag.c_str(),
+                     t.residue_index[i]);
+    pad80(out, line, n);
+    ++serial;
+  });
   if (model >= 0) pad80(out, "ENDMDL", 6);
   if (add_end) pad80(out, "END", 3);
 }
@@ -546,6 +561,168 @@ extern "C" int dbfr_pdb_write_files(const dbfr_pdb_topology* topo, int32_t n_row
   }
 }
 
+
+extern "C" int64_t dbfr_pdb_atom_map(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, int32_t* code, float* static_pos,
+                                     int64_t cap, int64_t* n_static) {
+  try {
+    std::vector<int> row_of;
+    static const float dummy = 0.f;                      // the map needs the rows, not a pose
+    int rc = check_topology(topo, n_rows, rows, n_rows > 0 ? &dummy : nullptr, row_of);
+    if (rc) return rc;
+    int64_t n = 0, ns = 0;
+    walk_structure(*topo, row_of, n_rows > 0, [&](int, int, int row, int slot, const float* p) {
+      const bool room = code && n < cap;
+      if (row >= 0) {
+        if (room) code[n] = DBFR_XTC_POCKET(row, slot);
+      } else {
+        if (room) {
+          code[n] = DBFR_XTC_STATIC((int32_t)ns);
+          if (static_pos) for (int c = 0; c < 3; ++c) static_pos[ns * 3 + c] = p[c];
+        }
+        ++ns;
+      }
+      ++n;
+    }, [](int) {});
+    if (n_static) *n_static = ns;
+    if (n > (int64_t)0x3fffffff) { dbfr_set_error("too many atoms"); return DBFR_ERR_ARG; }
+    return n;
+  } catch (const std::exception& e) {
+    dbfr_set_error(std::string("dbfr_pdb_atom_map: ") + e.what());
+    return DBFR_ERR_ARG;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ protein-ligand complex
+// PLComplex.to_pdb() (druglib/utils/obj/complex.py:165-191): '\n'.join(plines[:remark_cut] + llines[:connect_cut] +
+// plines[remark_cut:] + llines[connect_cut:] + ['\n']) with plines / llines the splitlines() of the protein / ligand texts,
+// remark_cut = the leading lines that contain 'REMARK', connect_cut = the ligand lines before the first one that contains 'CONECT'.
+static int check_ligand(const dbfr_pdb_ligand* l, const float* pos) {
+  if (!l || !pos || l->n_atoms < 0 || !l->head || !l->tail || (l->n_atoms > 0 && !l->atom_line)) {
+    dbfr_set_error("null argument (ligand PDB block)");
+    return DBFR_ERR_ARG;
+  }
+  for (int i = 0; i < l->n_atoms; ++i)
+    if (!l->atom_line[i] || strlen(l->atom_line[i]) < 54) { dbfr_set_error("ligand atom record shorter than 54 columns"); return DBFR_ERR_ARG; }
+  return DBFR_OK;
+}
+
+static void split_lines(const std::string& s, std::vector<std::pair<size_t, size_t>>& out) {      // str.splitlines() on '\n' text
+  out.clear();
+  size_t b = 0;
+  while (b < s.size()) {
+    size_t e = s.find('\n', b);
+    if (e == std::string::npos) e = s.size();
+    out.emplace_back(b, e - b);
+    b = e + 1;
+  }
+}
+
+static void format_complex(const dbfr_pdb_topology& t, const std::vector<int>& row_of, const float* pos14, const dbfr_pdb_ligand& l,
+                           const float* lig_pos, std::string& prot, std::string& lig, std::string& out) {
+  format_structure(t, row_of, pos14, -1, 1, prot);
+  lig.clear();
+  lig += l.head;
+  char buf[32];
+  for (int i = 0; i < l.n_atoms; ++i) {
+    const char* a = l.atom_line[i];
+    lig.append(a, 30);
+    snprintf(buf, sizeof buf, "%8.3f%8.3f%8.3f", (double)lig_pos[3 * i], (double)lig_pos[3 * i + 1], (double)lig_pos[3 * i + 2]);
+    lig.append(buf, 24);                                   // (a coordinate wider than 8 columns shifts the line, as in the reference)
+    lig += a + 54;
+    lig += '\n';
+  }
+  lig += l.tail;
+  std::vector<std::pair<size_t, size_t>> pl, ll;
+  split_lines(prot, pl);
+  split_lines(lig, ll);
+  size_t rc = 0;
+  while (rc < pl.size() && std::string(prot, pl[rc].first, pl[rc].second).find("REMARK") != std::string::npos) ++rc;
+  size_t cc = 0;
+  while (cc < ll.size() && std::string(lig, ll[cc].first, ll[cc].second).find("CONECT") == std::string::npos) ++cc;
+  out.clear();
+  out.reserve(prot.size() + lig.size() + 8);
+  bool first = true;
+  auto put = [&](const std::string& src, const std::pair<size_t, size_t>& r) {
+    if (!first) out += '\n';
+    first = false;
+    out.append(src, r.first, r.second);
+  };
+  for (size_t k = 0; k < rc; ++k) put(prot, pl[k]);
+  for (size_t k = 0; k < cc; ++k) put(lig, ll[k]);
+  for (size_t k = rc; k < pl.size(); ++k) put(prot, pl[k]);
+  for (size_t k = cc; k < ll.size(); ++k) put(lig, ll[k]);
+  if (!first) out += '\n';
+  out += '\n';
+}
+
+extern "C" int64_t dbfr_complex_pdb_format(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, const float* pos14,
+                                           const dbfr_pdb_ligand* lig, const float* lig_pos, char* out, int64_t cap) {
+  try {
+    std::vector<int> row_of;
+    int rc = check_topology(topo, n_rows, rows, pos14, row_of);
+    if (rc) return rc;
+    if (check_ligand(lig, lig_pos)) return DBFR_ERR_ARG;
+    std::string p, l, s;
+    format_complex(*topo, row_of, n_rows > 0 ? pos14 : nullptr, *lig, lig_pos, p, l, s);
+    if (out && (int64_t)s.size() <= cap) memcpy(out, s.data(), s.size());
+    return (int64_t)s.size();
+  } catch (const std::exception& e) {
+    dbfr_set_error(std::string("dbfr_complex_pdb_format: ") + e.what());
+    return DBFR_ERR_ARG;
+  }
+}
+
+// host threads of the trajectory writers: the caller's count, else OMP_NUM_THREADS, else 16 (never the machine's core count)
+static int writer_threads(int requested, int n_items) {
+  int nt = requested;
+  if (nt <= 0) {
+    const char* e = getenv("OMP_NUM_THREADS");
+    nt = e ? atoi(e) : 0;
+    if (nt <= 0) nt = 16;
+  }
+  return std::max(1, std::min(nt, n_items));
+}
+
+extern "C" int dbfr_complex_pdb_write_files(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, const float* pos14,
+                                            const dbfr_pdb_ligand* lig, const float* lig_pos, int32_t n_file, const char* const* paths,
+                                            int32_t n_threads) {
+  try {
+    std::vector<int> row_of;
+    int rc = check_topology(topo, n_rows, rows, pos14, row_of);
+    if (rc) return rc;
+    if (check_ligand(lig, lig_pos)) return DBFR_ERR_ARG;
+    if (n_file < 0 || (n_file > 0 && !paths)) { dbfr_set_error("paths missing"); return DBFR_ERR_ARG; }
+    if (n_file == 0) return DBFR_OK;
+    const int nt = writer_threads(n_threads, n_file);
+    std::atomic<int> next(0), failed(-1);
+    auto work = [&]() noexcept {
+      try {
+        std::string p, l, s;
+        for (;;) {
+          int i = next.fetch_add(1);
+          if (i >= n_file) break;
+          format_complex(*topo, row_of, n_rows > 0 ? pos14 + (size_t)i * n_rows * 42 : nullptr, *lig,
+                         lig_pos + (size_t)i * lig->n_atoms * 3, p, l, s);
+          FILE* f = fopen(paths[i], "wb");
+          bool ok = f && fwrite(s.data(), 1, s.size(), f) == s.size();
+          if (f) ok = (fclose(f) == 0) && ok;
+          if (!ok) { int e = -1; failed.compare_exchange_strong(e, i); }
+        }
+      } catch (...) { int e = -1; failed.compare_exchange_strong(e, 0); }
+    };
+    std::vector<std::thread> th;
+    for (int k = 1; k < nt; ++k) {
+      try { th.emplace_back(work); } catch (...) { break; }
+    }
+    work();
+    for (auto& x : th) x.join();
+    if (failed.load() >= 0) { dbfr_set_error(std::string("cannot write ") + paths[failed.load()]); return DBFR_ERR_ARG; }
+    return DBFR_OK;
+  } catch (const std::exception& e) {
+    dbfr_set_error(std::string("dbfr_complex_pdb_write_files: ") + e.what());
+    return DBFR_ERR_ARG;
+  }
+}
 
 // ------------------------------------------------------------------------------------------------ ligand SD files
 // lig_final.sdf of every pose (DiffBindFR/evaluation/export.py:97-103,236-244: Ligand3D.pos_update + Chem.SDWriter): the

@@ -133,6 +133,20 @@ class PoseCheckOut(C.Structure):
                                           "flat_dev", "n_stereo_flip", "passed")]
 
 
+class PdbLigand(C.Structure):
+    _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
+
+
+class XtcIn(C.Structure):
+    _fields_ = [(n, i32) for n in ("n_frame", "n_file", "n_src", "n_lig", "n_res", "n_static", "n_map", "max_atoms")] + \
+               [(n, vp) for n in ("lig", "pos14", "center", "static_pos", "map_ptr", "atom_map", "file_map", "frame_file",
+                                  "frame_src", "frame_step")]
+
+
+class XtcOpts(C.Structure):
+    _fields_ = [("precision", f32), ("dt", f32), ("first_step", i32), ("box", f32 * 9)]
+
+
 # every symbol include/dbfr.h declares (tests check that the library exports all of them)
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
@@ -141,7 +155,8 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
-           "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check"]
+           "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
+           "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode"]
 
 _lib = None
 
@@ -221,6 +236,14 @@ def load():
     lib.dbfr_pose_rmsd_matrix.argtypes = [C.POINTER(PoseRmsdIn), vp, vp]
     lib.dbfr_select_modes.argtypes = [C.POINTER(PoseRmsdIn), vp, vp, C.POINTER(ModesOpts), vp, vp, vp, vp]
     lib.dbfr_pose_check.argtypes = [C.POINTER(PoseCheckIn), C.POINTER(PoseCheckOpts), C.POINTER(PoseCheckOut), vp]
+    lib.dbfr_pdb_atom_map.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.dbfr_pdb_atom_map.restype = C.c_int64
+    lib.dbfr_complex_pdb_format.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, C.POINTER(PdbLigand), vp, vp, C.c_int64]
+    lib.dbfr_complex_pdb_format.restype = C.c_int64
+    lib.dbfr_complex_pdb_write_files.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, C.POINTER(PdbLigand), vp, i32,
+                                                 C.POINTER(C.c_char_p), i32]
+    lib.dbfr_xtc_workspace_bytes.argtypes = [C.POINTER(XtcIn), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
+    lib.dbfr_xtc_encode.argtypes = [C.POINTER(XtcIn), C.POINTER(XtcOpts), vp, C.c_int64, vp, vp, C.c_size_t, vp]
     if lib.dbfr_abi_version() != 6:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

@@ -237,3 +237,74 @@ class SdfTemplate:
         t = self._c()
         arr = (C.c_char_p * len(paths))(*[str(x).encode() for x in paths])
         L.check(lib.dbfr_sdf_write_files(C.byref(t), a.ctypes.data_as(C.c_void_p), len(paths), arr, int(threads)))
+
+
+_V2000_CHARGE = {1: 3, 2: 2, 3: 1, 5: -1, 6: -2, 7: -3}          # atom-block charge field (ccc) of the CTfile V2000 layout
+
+
+class PdbLigandTemplate:
+    """The ligand's PDB block, prepared once per ligand for the complex PDB files of the trajectory export
+    (``PLComplex.to_pdb``, druglib/utils/obj/complex.py:165-191, which takes ``Chem.MolToPDBBlock`` of the heavy-atom ligand).
+
+    Built from the heavy-atom V2000 block ``SdfTemplate`` already holds, in the layout RDKit's PDB writer uses for a mol without
+    residue information: an optional ``COMPND`` line (the record's title); one ``HETATM`` record per atom, residue ``UNL 1``, atom
+    name = element + per-element counter (``C1``, ``C2``, ``N1`` ...), occupancy 1.00, B-factor 0.00, element in columns 77-78
+    and the formal charge (``1+`` / ``2-`` ...) in 79-80; ``CONECT`` records from the bond block (an atom's bonded atoms in
+    increasing order, a double bond listed twice and a triple bond three times, at most four per record); ``END``.  The formal
+    charges come from the ``M  CHG`` lines when the record has any, else from the atom block.
+    Byte parity with RDKit's ``MolToPDBBlock`` is NOT pinned (RDKit is absent offline; RDKit lists a bond it perceives as
+    aromatic once).  The XTC bytes do not depend on this text: only the atom order (SD order) matters there."""
+
+    def __init__(self, head, atom_lines, tail):
+        self.head, self.atom_lines, self.tail = head, list(atom_lines), tail
+        self.n_atoms = len(self.atom_lines)
+
+    @classmethod
+    def from_sdf_template(cls, t):
+        hdr = t.header.split("\n")
+        title = hdr[0].strip()
+        nb = int(hdr[3][3:6])
+        tr = t.trailer.split("\n")
+        bonds = [(int(b[0:3]) - 1, int(b[3:6]) - 1, int(b[6:9])) for b in tr[:nb]]
+        chg = [_V2000_CHARGE.get(int(a[6:9]) if a[6:9].strip() else 0, 0) for a in t.atom_tails]
+        mchg = [l for l in tr[nb:] if l.startswith("M  CHG")]
+        if mchg:
+            chg = [0] * t.n_atoms
+            for l in mchg:
+                for k in range(int(l[6:9])):
+                    chg[int(l[9 + 8 * k:13 + 8 * k]) - 1] = int(l[13 + 8 * k:17 + 8 * k])
+        count, lines = {}, []
+        for i, a in enumerate(t.atom_tails):
+            sym = a[1:4].strip()
+            at1, at2 = (" ", sym[0]) if len(sym) == 1 else ((sym[0], sym[1].upper()) if sym else (" ", "X"))
+            count[sym] = count.get(sym, 0) + 1
+            n = count[sym]
+            name = at1 + at2 + (str(n) if n < 1000 else "***").ljust(3)
+            c = chg[i]
+            ch = f"{abs(c)}{'+' if c > 0 else '-'}" if c and abs(c) < 10 else "  "
+            lines.append(f"HETATM{i + 1:5d} {name}UNL     1    " + " " * 24 + "  1.00  0.00          " + at1 + at2 + ch)
+        nbr = [[] for _ in range(t.n_atoms)]
+        for i, j, order in bonds:
+            k = order if order in (2, 3) else 1
+            nbr[i] += [j] * k
+            nbr[j] += [i] * k
+        conect = []
+        for i in range(t.n_atoms):
+            v = sorted(nbr[i])
+            for s in range(0, len(v), 4):
+                conect.append(f"CONECT{i + 1:5d}" + "".join(f"{x + 1:5d}" for x in v[s:s + 4]))
+        head = f"COMPND    {title}\n" if title else ""
+        return cls(head, lines, "".join(l + "\n" for l in conect) + "END\n")
+
+    def _c(self):
+        from . import lib as L
+        import ctypes as C
+        self._keep = [l.encode() for l in self.atom_lines]
+        self._arr = (C.c_char_p * max(self.n_atoms, 1))(*self._keep)
+        return L.PdbLigand(self.n_atoms, self.head.encode(), self._arr, self.tail.encode())
+
+    def format(self, pos):
+        """The block with the coordinates pos [n_atoms, 3] (``Chem.MolToPDBBlock`` of the posed ligand)."""
+        a = np.asarray(pos, np.float32).reshape(self.n_atoms, 3)
+        rows = [l[:30] + "%8.3f%8.3f%8.3f" % tuple(float(v) for v in a[i]) + l[54:] for i, l in enumerate(self.atom_lines)]
+        return self.head + "".join(r + "\n" for r in rows) + self.tail

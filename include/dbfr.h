@@ -37,7 +37,9 @@ extern "C" {
                                 6: + dbfr_profile_useful_flops, dbfr_model_set_tie_log, dbfr_test_reduce_ln2; dbfr_model_set_edge_log accepts batches with fewer graphs than its capacity; an unknown DBFR_GEMM value fails dbfr_model_create;
                                    later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize,
                                    dbfr_pose_rmsd_in, dbfr_modes_opts, dbfr_pose_rmsd_matrix, dbfr_select_modes,
-                                   dbfr_pose_check_in, dbfr_pose_check_opts, dbfr_pose_check_out, dbfr_pose_check */
+                                   dbfr_pose_check_in, dbfr_pose_check_opts, dbfr_pose_check_out, dbfr_pose_check,
+                                   dbfr_xtc_in, dbfr_xtc_opts, dbfr_xtc_workspace_bytes, dbfr_xtc_encode, dbfr_pdb_atom_map,
+                                   dbfr_pdb_ligand, dbfr_complex_pdb_format, dbfr_complex_pdb_write_files */
 
 typedef enum {
   DBFR_OK = 0,
@@ -341,6 +343,36 @@ int64_t dbfr_pdb_format(const dbfr_pdb_topology* topo, int32_t n_rows, const int
 int dbfr_pdb_write_files(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, const float* pos14,
                          int32_t n_pose, const char* const* paths, int32_t n_threads);
 
+/* (ABI 6) The ATOM records of dbfr_pdb_format(topo, n_rows, rows, ...) as coordinate sources, in record order (the same walk
+ * as the text writer, so an XTC frame built from the map lists the atoms of the PDB in its order).  code[k] of record k:
+ * DBFR_XTC_POCKET(j, s) = atom14 slot s of pos14 row j (the row of rows[] the residue is in), or DBFR_XTC_STATIC(m) = the
+ * coordinate the writer prints for a residue no row covers, written to static_pos[m] ([n_static, 3], m counts up from 0).
+ * Returns the number of ATOM records (nothing is written when it exceeds cap); *n_static (may be NULL) the static ones. */
+int64_t dbfr_pdb_atom_map(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, int32_t* code, float* static_pos,
+                          int64_t cap, int64_t* n_static);
+
+/* (ABI 6) A ligand's PDB block (what Chem.MolToPDBBlock gives for a hydrogen-free mol without residue info: COMPND, HETATM
+ * ... 'UNL', CONECT, END) prepared once as text; per pose only columns 31-54 of the HETATM records change (three %8.3f).
+ * Byte parity with RDKit is NOT pinned (RDKit is absent offline); the XTC bytes do not depend on this text.            */
+typedef struct {
+  int32_t            n_atoms;
+  const char*        head;       /* lines before the atom records (COMPND), each newline-terminated, may be ""        */
+  const char* const* atom_line;  /* [n_atoms] HETATM records without newline, >= 54 chars; columns 31-54 are replaced   */
+  const char*        tail;       /* CONECT records and END, each newline-terminated                                   */
+} dbfr_pdb_ligand;
+
+/* PLComplex(protein, ligand).to_pdb() (druglib/utils/obj/complex.py:165-191): the protein's REMARK lines, the ligand's lines
+ * up to its first CONECT, the protein's other lines, the ligand's remaining lines and a final newline, joined by newlines.
+ * Protein text as dbfr_pdb_format(topo, n_rows, rows, pos14, -1, 1); lig_pos [n_atoms, 3].  Returns the byte count (nothing
+ * written when it exceeds cap).                                                                                         */
+int64_t dbfr_complex_pdb_format(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, const float* pos14,
+                                const dbfr_pdb_ligand* lig, const float* lig_pos, char* out, int64_t cap);
+/* paths[i] receives the complex of pos14[i] ([n_file, n_rows, 14, 3]) and lig_pos[i] ([n_file, n_atoms, 3]) on n_threads host
+ * threads (<= 0: OMP_NUM_THREADS when set, else 16; never more than n_file).                                             */
+int dbfr_complex_pdb_write_files(const dbfr_pdb_topology* topo, int32_t n_rows, const int32_t* rows, const float* pos14,
+                                 const dbfr_pdb_ligand* lig, const float* lig_pos, int32_t n_file, const char* const* paths,
+                                 int32_t n_threads);
+
 /* SD file of a ligand pose (host code, all pointers host): what the reference writes per pose as `lig_final.sdf`
  * (DiffBindFR/evaluation/export.py:97-103,236-244: Ligand3D.pos_update(pose) -> Chem.SDWriter).  The V2000 mol block of
  * the (hydrogen-free) ligand is prepared once as text; per pose only the coordinate columns change.
@@ -589,6 +621,60 @@ typedef struct {                 /* device arrays [n_frame]; any may be NULL    
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_pose_check(const dbfr_pose_check_in* in, const dbfr_pose_check_opts* opts, const dbfr_pose_check_out* out,
                     void* hip_stream);
+
+/* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file
+ * files; a file is the frames listed for it, in frame order, with one atom map.  Atom k of a frame is atom_map[map_ptr[m] + k]
+ * (m = file_map[frame_file[f]]) of source frame s = frame_src[f]:
+ *   0 <= code < 0x40000000        ligand atom code of lig[s]                                   (+ center)
+ *   code = DBFR_XTC_POCKET(r, a)  atom14 slot a of pocket row r of pos14[s]                    (+ center)
+ *   code = DBFR_XTC_STATIC(m)     static_pos[m], absolute
+ * (the centre added in float32).  Every coordinate x (A) goes through the chain a PDB file and an XTC writer apply:
+ *   q3 = rint((double)x * 1000) ("%8.3f"), xp = (float)((double)q3 / 1000) (a reader's float32), xn = xp * 0.1f (nm),
+ *   p = xn * precision, int = (int)(float)(p +- 0.5) (+ for xn >= 0),
+ * and frames are written in the XTC layout of libxdrfile's xdrfile_compress_coord_float (GROMACS xdr3dfcoord): header
+ * (1995, natoms, step, time, box[9], natoms), then <= 9 atoms: 3 natoms floats xn, else precision, minint[3], maxint[3],
+ * smallidx, nbytes and the bit stream.  Big-endian throughout.  step = first_step + frame_step[f], time = step_time * dt.
+ * Refused with DBFR_ERR_ARG after the launch (the call synchronises the stream): |p +- 0.5| > INT_MAX - 2, a range
+ * maxint - minint >= INT_MAX - 2, a frame whose consecutive atoms are so far apart that the adaptive table index would leave
+ * the table (smallidx + 8 >= 73), an index outside its array, frame_file not 0, 1, ... in frame order (every file at least one
+ * frame), more atoms than max_atoms.  Limits: n_frame <= 2^20, max_atoms <= 2^20.                                        */
+#define DBFR_XTC_POCKET(r, a) (0x40000000 + (r) * 14 + (a))
+#define DBFR_XTC_STATIC(m) (-1 - (m))
+typedef struct {
+  int32_t        n_frame;
+  int32_t        n_file;
+  int32_t        n_src;          /* source frames in lig / pos14                                                          */
+  int32_t        n_lig;          /* ligand atoms per source frame                                                         */
+  int32_t        n_res;          /* pocket rows per source frame                                                          */
+  int32_t        n_static;
+  int32_t        n_map;
+  int32_t        max_atoms;      /* host-known bound of every map's length (sizes the workspace and the output)            */
+  const float*   lig;            /* [n_src, n_lig, 3] pocket-centred (may be NULL when n_lig == 0)                          */
+  const float*   pos14;          /* [n_src, n_res, 14, 3] pocket-centred (may be NULL when n_res == 0)                      */
+  const float*   center;         /* [3]                                                                                    */
+  const float*   static_pos;     /* [n_static, 3] absolute (may be NULL when n_static == 0)                                 */
+  const int32_t* map_ptr;        /* [n_map + 1]                                                                            */
+  const int32_t* atom_map;       /* [map_ptr[n_map]] codes                                                                 */
+  const int32_t* file_map;       /* [n_file] atom map of every file                                                       */
+  const int32_t* frame_file;     /* [n_frame] 0, ..., 0, 1, ..., n_file - 1                                                 */
+  const int32_t* frame_src;      /* [n_frame] source frame                                                                 */
+  const int32_t* frame_step;     /* [n_frame] step of the frame inside its file (header step = first_step + this)          */
+} dbfr_xtc_in;                   /* every pointer a device pointer                                                         */
+
+typedef struct {
+  float   precision;             /* default 1000 (<= 0: 1000, like libxdrfile)                                             */
+  float   dt;                    /* ps per step, default 1.0: time = step * dt                                             */
+  int32_t first_step;            /* default 0                                                                              */
+  float   box[9];                /* nm, default zeros (the frame PDBs carry no CRYST1)                                      */
+} dbfr_xtc_opts;
+
+/* Workspace bytes of a dbfr_xtc_encode call of this shape and *out_cap, the output bytes to provide (the worst case).   */
+int dbfr_xtc_workspace_bytes(const dbfr_xtc_in* in, size_t* bytes, int64_t* out_cap);
+/* Encodes every file: out (device, out_cap bytes, 4-byte aligned) receives the file images back to back, offsets (device,
+ * [n_file + 1] int64) their byte offsets.  opts NULL = defaults.  Deterministic; a frame's bytes do not depend on the other
+ * frames of the launch.  Synchronises the stream (the refusal status).                                                   */
+int dbfr_xtc_encode(const dbfr_xtc_in* in, const dbfr_xtc_opts* opts, uint8_t* out, int64_t out_cap, int64_t* offsets,
+                    void* workspace, size_t workspace_bytes, void* hip_stream);
 
 /* Synchronises the stream and returns the device-side status word of the last
  * dbfr_score / dbfr_sample issued with this workspace (DBFR_OK, DBFR_ERR_CAPACITY,

@@ -12,5 +12,6 @@ from . import vina  # noqa: F401
 from . import modes  # noqa: F401
 from . import posecheck  # noqa: F401
 from . import trajectory  # noqa: F401
+from . import sites  # noqa: F401
 
 register_into_druglib()

@@ -147,6 +147,21 @@ class XtcOpts(C.Structure):
     _fields_ = [("precision", f32), ("dt", f32), ("first_step", i32), ("box", f32 * 9)]
 
 
+class SitesOpts(C.Structure):
+    _fields_ = [(n, f32) for n in ("spacing", "probe", "ray_length", "lining_cutoff")] + \
+               [(n, i32) for n in ("min_buried", "min_points", "max_sites")]
+
+
+class SitesIn(C.Structure):
+    _fields_ = [("n_prot", i32), ("n_res", i32), ("max_points", C.c_int64)] + \
+               [(n, vp) for n in ("res_ptr", "aatype", "atom37_pos", "atom37_mask", "radius")]
+
+
+class SitesOut(C.Structure):
+    _fields_ = [(n, vp) for n in ("n_sites", "label", "n_points", "score", "idx_sum", "centre", "lining", "grid", "occupancy",
+                                  "burial", "labels")]
+
+
 # every symbol include/dbfr.h declares (tests check that the library exports all of them)
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
@@ -156,7 +171,8 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
-           "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode"]
+           "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
+           "dbfr_sites_workspace_bytes", "dbfr_find_sites"]
 
 _lib = None
 
@@ -244,6 +260,8 @@ def load():
                                                  C.POINTER(C.c_char_p), i32]
     lib.dbfr_xtc_workspace_bytes.argtypes = [C.POINTER(XtcIn), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
     lib.dbfr_xtc_encode.argtypes = [C.POINTER(XtcIn), C.POINTER(XtcOpts), vp, C.c_int64, vp, vp, C.c_size_t, vp]
+    lib.dbfr_sites_workspace_bytes.argtypes = [C.POINTER(SitesIn), C.POINTER(C.c_size_t)]
+    lib.dbfr_find_sites.argtypes = [C.POINTER(SitesIn), C.POINTER(SitesOpts), C.POINTER(SitesOut), vp, C.c_size_t, vp]
     if lib.dbfr_abi_version() != 6:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

@@ -39,7 +39,8 @@ extern "C" {
                                    dbfr_pose_rmsd_in, dbfr_modes_opts, dbfr_pose_rmsd_matrix, dbfr_select_modes,
                                    dbfr_pose_check_in, dbfr_pose_check_opts, dbfr_pose_check_out, dbfr_pose_check,
                                    dbfr_xtc_in, dbfr_xtc_opts, dbfr_xtc_workspace_bytes, dbfr_xtc_encode, dbfr_pdb_atom_map,
-                                   dbfr_pdb_ligand, dbfr_complex_pdb_format, dbfr_complex_pdb_write_files */
+                                   dbfr_pdb_ligand, dbfr_complex_pdb_format, dbfr_complex_pdb_write_files,
+                                   dbfr_sites_opts, dbfr_sites_in, dbfr_sites_out, dbfr_sites_workspace_bytes, dbfr_find_sites */
 
 typedef enum {
   DBFR_OK = 0,
@@ -675,6 +676,63 @@ int dbfr_xtc_workspace_bytes(const dbfr_xtc_in* in, size_t* bytes, int64_t* out_
  * frames of the launch.  Synchronises the stream (the refusal status).                                                   */
 int dbfr_xtc_encode(const dbfr_xtc_in* in, const dbfr_xtc_opts* opts, uint8_t* out, int64_t out_cap, int64_t* offsets,
                     void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- Binding-site detection (csrc/sites.hip; docs/sites.md), LIGSITE-style, for a ragged batch of proteins.
+ * Atoms: the atom37 slots with mask > 0 of residues res_ptr[p] .. res_ptr[p+1]; radius = radius[aatype * 37 + slot] (+ probe).
+ * Grid: the absolute lattice h Z^3; per protein and axis I = floor(min / h) .. floor(max / h) over its atoms (floor in float64 of
+ * the fp32 values), point position h * I in fp32; linear index i + n_x (j + n_y k) (i, j, k = I - lo).  A protein's grid over
+ * 1024 points per axis or 2^24 points in all: DBFR_ERR_ARG.
+ *   occupied(q)  some atom with |q - x_a|^2 < (r_a + probe)^2 (fp32, every operation rounded);
+ *   burial b(q)  over the 3 axes and the 4 body diagonals, the lines that reach an occupied point within T_e = floor(ray_length /
+ *                (h |e|)) steps (float64 on the host) in BOTH senses; points off the grid are solvent; 0 at occupied points;
+ *   pocket       solvent points with b >= min_buried;
+ *   site         a 6-connected component of pocket points, labelled by its smallest linear index.
+ * Per site: n_points, score = sum b, idx_sum = sum (i, j, k) (int64), centre = h (lo + idx_sum / n_points) in float64.  Sites with
+ * n_points >= min_points are ranked by score (highest first), then label (lowest first); max_sites are kept.  A kept site's
+ * lining residues have an atom with |q - x_a| <= lining_cutoff (fp32) for some point q of the site.
+ * Integer atomics only (min-label union-find, int32 / int64 sums): a protein's outputs are the same bits alone or in any batch. */
+typedef struct {
+  float   spacing;               /* h (A), [0.25, 4], default 1.0                                                           */
+  float   probe;                 /* A, [0, 4], default 1.2                                                                  */
+  float   ray_length;            /* A, [spacing, 255 spacing], default 8.0                                                  */
+  float   lining_cutoff;         /* A, [0, 10], default 4.0                                                                 */
+  int32_t min_buried;            /* [1, 7], default 6                                                                       */
+  int32_t min_points;            /* [1, 2^24], default 30                                                                   */
+  int32_t max_sites;             /* [1, 64], default 5                                                                      */
+} dbfr_sites_opts;
+
+typedef struct {
+  int32_t        n_prot;
+  int32_t        n_res;          /* res_ptr[n_prot]                                                                         */
+  int64_t        max_points;     /* the workspace's grid-point capacity (the call's total over its proteins), <= 2^30         */
+  const int32_t* res_ptr;        /* device [n_prot + 1], 0 .. n_res, not decreasing                                          */
+  const int32_t* aatype;         /* device [n_res], 0..20 (others read as 20)                                               */
+  const float*   atom37_pos;     /* device [n_res, 37, 3]                                                                   */
+  const float*   atom37_mask;    /* device [n_res, 37]                                                                      */
+  const float*   radius;         /* device [21, 37] radius of every atom37 slot of every residue type, (0, 4]                 */
+} dbfr_sites_in;
+
+typedef struct {                 /* S = opts.max_sites; device arrays unless marked host                                    */
+  int32_t* n_sites;              /* [n_prot] sites kept                                                                     */
+  int32_t* label;                /* [n_prot, S] linear index of the site's smallest point; -1 for an unused slot               */
+  int32_t* n_points;             /* [n_prot, S]                                                                             */
+  int32_t* score;                /* [n_prot, S] sum of b                                                                    */
+  int64_t* idx_sum;              /* [n_prot, S, 3] (may be NULL)                                                            */
+  double*  centre;               /* [n_prot, S, 3] A                                                                        */
+  uint8_t* lining;               /* [n_res, S] 1 = residue lines site s of its protein (may be NULL)                          */
+  int32_t* grid;                 /* HOST [n_prot, 6]: lo (I of index 0) and n per axis (may be NULL); grid offsets of the
+                                    optional grids below: protein p starts at the sum of n_x n_y n_z of proteins < p          */
+  uint8_t* occupancy;            /* [total points] 1 = occupied (may be NULL; for tests)                                     */
+  uint8_t* burial;               /* [total points] b (may be NULL)                                                          */
+  int32_t* labels;               /* [total points] site label of pocket points (every component, kept or not), else -1       */
+} dbfr_sites_out;
+
+/* Workspace bytes of a call of in->n_prot proteins and at most in->max_points grid points.                                   */
+int dbfr_sites_workspace_bytes(const dbfr_sites_in* in, size_t* bytes);
+/* Finds the sites of every protein.  opts NULL = defaults.  Synchronises the stream (res_ptr and the grid sizes are read back);
+ * a call whose grids exceed in->max_points fails with DBFR_ERR_CAPACITY before any grid work.                                */
+int dbfr_find_sites(const dbfr_sites_in* in, const dbfr_sites_opts* opts, const dbfr_sites_out* out, void* workspace,
+                    size_t workspace_bytes, void* hip_stream);
 
 /* Synchronises the stream and returns the device-side status word of the last
  * dbfr_score / dbfr_sample issued with this workspace (DBFR_OK, DBFR_ERR_CAPACITY,

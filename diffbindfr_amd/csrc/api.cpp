@@ -1517,6 +1517,23 @@ extern "C" int dbfr_score(dbfr_model* m, const dbfr_batch* b, const dbfr_cond* c
   return take_launch_error();
 }
 
+// The update half of one denoise step (scFlex.py:154-230): scores + this step's noise slices -> new ligand coordinates, chi angles and
+// side chains.  dbfr_sample_range and the test hook dbfr_test_sde_step both go through here.
+static void pose_update(const dbfr_model* m, const dbfr_batch* b, const dbfr_step& sp, const dbfr_scores& sc, const float* z_tr,
+                        const float* z_rot, const float* z_tor, const float* z_sc, float* traj_lig, float* atom14_out,
+                        float* traj_atom14, int* err, hipStream_t st) {
+  SdeLigArgs la;
+  la.b = *b; la.tr_score = sc.tr; la.rot_score = sc.rot; la.tor_score = sc.tor;
+  la.z_tr = z_tr; la.z_rot = z_rot; la.z_tor = z_tor;
+  la.dt = sp.dt; la.tr_g2 = sp.tr_g2; la.tr_gsdt = sp.tr_gsdt; la.rot_g2 = sp.rot_g2; la.rot_gsdt = sp.rot_gsdt;
+  la.tor_g2 = sp.tor_g2; la.tor_gsdt = sp.tor_gsdt;
+  la.traj = traj_lig;
+  la.err = err;
+  launch_sde_ligand(la, st);
+  if (!m->cfg.no_sc_torsion)
+    launch_sidechain(*b, sc.sc_tor, z_sc, sp.dt, sp.sc_g2, sp.sc_gsdt, m->a14_group, atom14_out, traj_atom14, err, st);
+}
+
 extern "C" int dbfr_sample_range(dbfr_model* m, const dbfr_batch* b, const dbfr_step* steps, int32_t n_steps,
                                  int32_t step_begin, const dbfr_noise* noise, float* atom14_out, float* traj_lig,
                                  float* traj_atom14, void* workspace, size_t workspace_bytes, const dbfr_limits* lim,
@@ -1540,20 +1557,9 @@ extern "C" int dbfr_sample_range(dbfr_model* m, const dbfr_batch* b, const dbfr_
     dbfr_scores sc = {w.s_tr, w.s_rot, w.s_tor, w.s_sc};
     rc = run_score(m, b, &c, &sc, w, st, s);
     if (rc) return rc;
-    SdeLigArgs la;
-    la.b = *b; la.tr_score = w.s_tr; la.rot_score = w.s_rot; la.tor_score = w.s_tor;
-    la.z_tr = noise->z_tr + (size_t)s * G * 3; la.z_rot = noise->z_rot + (size_t)s * G * 3;
-    la.z_tor = noise->z_tor + (size_t)s * b->NTOR;
-    la.dt = sp.dt; la.tr_g2 = sp.tr_g2; la.tr_gsdt = sp.tr_gsdt; la.rot_g2 = sp.rot_g2; la.rot_gsdt = sp.rot_gsdt;
-    la.tor_g2 = sp.tor_g2; la.tor_gsdt = sp.tor_gsdt;
-    la.traj = traj_lig ? traj_lig + (size_t)s * b->NL * 3 : nullptr;
-    la.err = w.err;
-    launch_sde_ligand(la, st);
-    if (!m->cfg.no_sc_torsion) {
-      const bool last = s == n_steps - 1;
-      launch_sidechain(*b, w.s_sc, noise->z_sc + (size_t)s * b->NSC, sp.dt, sp.sc_g2, sp.sc_gsdt, m->a14_group,
-                       last ? atom14_out : nullptr, traj_atom14 ? traj_atom14 + (size_t)s * b->NR * 42 : nullptr, w.err, st);
-    }
+    pose_update(m, b, sp, sc, noise->z_tr + (size_t)s * G * 3, noise->z_rot + (size_t)s * G * 3, noise->z_tor + (size_t)s * b->NTOR,
+                noise->z_sc + (size_t)s * b->NSC, traj_lig ? traj_lig + (size_t)s * b->NL * 3 : nullptr,
+                s == n_steps - 1 ? atom14_out : nullptr, traj_atom14 ? traj_atom14 + (size_t)s * b->NR * 42 : nullptr, w.err, st);
   }
   HIPCHECK(hipGetLastError());
   return take_launch_error();
@@ -1764,6 +1770,22 @@ static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t fami
 
 // Test hook: the chunk table of DBFR_GEMM_REDUCE_FIRST for one flat, target-sorted edge list, cut every `span` edges as if those were graphs
 // (graph.hip k_flat_chunk_*; the same chunk_len as the per-graph kernels of the sampler).  Device pointers; scratch = n_span + 1 ints.
+// (ABI 7) Test hook: the update half of ONE denoise step on caller-supplied scores and noise slices (no score network, no workspace).
+extern "C" int dbfr_test_sde_step(const dbfr_model* m, const dbfr_batch* b, const dbfr_step* step, const dbfr_scores* scores,
+                                  const dbfr_noise* z, float* atom14_out, int32_t* err_word_out, void* hip_stream) {
+  int rc = check_batch(m, b);
+  if (rc) return rc;
+  if (!step || !scores || !z || !err_word_out) return fail(DBFR_ERR_ARG, "dbfr_test_sde_step: null argument");
+  if (!scores->tr || !scores->rot || !z->z_tr || !z->z_rot || (b->NTOR > 0 && (!scores->tor || !z->z_tor)) ||
+      (!m->cfg.no_sc_torsion && b->NSC > 0 && (!scores->sc_tor || !z->z_sc)))
+    return fail(DBFR_ERR_ARG, "dbfr_test_sde_step: null score or noise array");
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIPCHECK(hipMemsetAsync(err_word_out, 0, sizeof(int32_t), st));
+  pose_update(m, b, *step, *scores, z->z_tr, z->z_rot, z->z_tor, z->z_sc, nullptr, atom14_out, nullptr, err_word_out, st);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
 extern "C" int dbfr_test_chunk_table(const int32_t* tgt, const int32_t* n_edges_dev, int32_t max_edges, int32_t span, int32_t* scratch, int32_t cap,
                                      int32_t* chunk_es, int32_t* chunk_gl, void* hip_stream) {
   if (!tgt || !n_edges_dev || !scratch || !chunk_es || !chunk_gl || span <= 0 || max_edges < 0 || cap <= 0) return fail(DBFR_ERR_ARG, "dbfr_test_chunk_table: bad argument");

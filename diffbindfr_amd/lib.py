@@ -166,7 +166,7 @@ class SitesOut(C.Structure):
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
            "dbfr_init_poses", "dbfr_extract_templates", "dbfr_status_sync", "dbfr_abi_version", "dbfr_build_id", "dbfr_last_error", "dbfr_wigner3j", "dbfr_conv_paths", "dbfr_test_pack_f16_tiles", "dbfr_test_pack_f16_rows", "dbfr_test_chunk_table", "dbfr_test_pack_f16_depth", "dbfr_probe_mfma_f16",
-           "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2",
+           "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2", "dbfr_test_sde_step",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
@@ -231,6 +231,7 @@ def load():
     lib.dbfr_test_conv2.argtypes = lib.dbfr_test_conv.argtypes
     lib.dbfr_test_reduce_ln.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp]
     lib.dbfr_test_reduce_ln2.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp]
+    lib.dbfr_test_sde_step.argtypes = [vp, C.POINTER(Batch), C.POINTER(Step), C.POINTER(Scores), C.POINTER(Noise), vp, vp, vp]
     lib.dbfr_select_pocket.argtypes = [i32, i32, vp, i32, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]
     lib.dbfr_pose_metrics.argtypes = [C.POINTER(PoseMetricsIn), C.POINTER(PoseMetricsOut), vp]
     lib.dbfr_pdb_format.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, i32, i32, vp, C.c_int64]
@@ -262,7 +263,7 @@ def load():
     lib.dbfr_xtc_encode.argtypes = [C.POINTER(XtcIn), C.POINTER(XtcOpts), vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.dbfr_sites_workspace_bytes.argtypes = [C.POINTER(SitesIn), C.POINTER(C.c_size_t)]
     lib.dbfr_find_sites.argtypes = [C.POINTER(SitesIn), C.POINTER(SitesOpts), C.POINTER(SitesOut), vp, C.c_size_t, vp]
-    if lib.dbfr_abi_version() != 6:
+    if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib
     return lib

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DBFR_ABI_VERSION 6   /* 2: + dbfr_sample_range, dbfr_capacity_report, dbfr_sdf_*, dbfr_mdn_*, dbfr_build_id, dbfr_test_conv2;
+#define DBFR_ABI_VERSION 7   /* 2: + dbfr_sample_range, dbfr_capacity_report, dbfr_sdf_*, dbfr_mdn_*, dbfr_build_id, dbfr_test_conv2;
                                 3: + dbfr_model_set_edge_log, dbfr_model_fallback_convs, dbfr_test_pack_f16_depth, dbfr_probe_mfma_f16 (additions only);
                                 4: + DBFR_GEMM_REDUCE_FIRST (the new default), dbfr_profile_executed_flops; dbfr_model_set_edge_log takes the graph capacity; DBFR_GEMM_SPLIT_BF16_L1 (k_conv2s) retired; dbfr_test_conv2's message rows in that mode hold segment sums;
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
@@ -40,7 +40,8 @@ extern "C" {
                                    dbfr_pose_check_in, dbfr_pose_check_opts, dbfr_pose_check_out, dbfr_pose_check,
                                    dbfr_xtc_in, dbfr_xtc_opts, dbfr_xtc_workspace_bytes, dbfr_xtc_encode, dbfr_pdb_atom_map,
                                    dbfr_pdb_ligand, dbfr_complex_pdb_format, dbfr_complex_pdb_write_files,
-                                   dbfr_sites_opts, dbfr_sites_in, dbfr_sites_out, dbfr_sites_workspace_bytes, dbfr_find_sites */
+                                   dbfr_sites_opts, dbfr_sites_in, dbfr_sites_out, dbfr_sites_workspace_bytes, dbfr_find_sites;
+                                7: + dbfr_test_sde_step (additions only) */
 
 typedef enum {
   DBFR_OK = 0,
@@ -870,6 +871,15 @@ int dbfr_test_reduce_ln(dbfr_model* m, int32_t layer, int32_t family, const floa
 int dbfr_test_reduce_ln2(dbfr_model* m, int32_t layer, int32_t family, const float* msg, const int32_t* row_start,
                          const int32_t* row_cnt, int32_t n_nodes, const float* old, int32_t d_old, float* out,
                          int32_t mode, const uint8_t* seg_first, void* hip_stream);
+
+/* (ABI 7) Test hook: the UPDATE half of one denoise step alone -- what dbfr_sample_range runs after the score network (k_sde_ligand: rigid move,
+ * ordered torsion rotations, Kabsch re-alignment; unless no_sc_torsion k_sc_update + k_atom14: chi update, side-chain rebuild, compaction into
+ * rec_pos) -- through the very function dbfr_sample_range calls, on caller-supplied scores (tr [G,3], rot [G,3], tor [NTOR], sc_tor [NSC]; device)
+ * and ONE step's noise slices (z_tr [G,3], z_rot [G,3], z_tor [NTOR], z_sc [NSC]; device).  Only the g2 / gsdt / dt scalars of `step` are read.
+ * Advances b->lig_pos, b->torsion_angle and b->rec_pos in place; atom14_out [NR,14,3] device or NULL.  *err_word_out (device int32, cleared
+ * first) receives the status bits the kernels raised (2 = the Kabsch determinant check); nothing is synchronised.                             */
+int dbfr_test_sde_step(const dbfr_model* m, const dbfr_batch* b, const dbfr_step* step, const dbfr_scores* scores,
+                       const dbfr_noise* z, float* atom14_out, int32_t* err_word_out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -50,7 +50,7 @@ def kabsch(A, B):
     U, S, Vt = torch.linalg.svd(H)
     R = Vt.T @ U.T
     if torch.linalg.det(R) < 0:
-        R = (Vt.T @ torch.diag(torch.tensor([1.0, 1.0, -1.0]))) @ U.T
+        R = (Vt.T @ torch.diag(torch.tensor([1.0, 1.0, -1.0], dtype=A.dtype))) @ U.T
     t = -R @ ca + cb
     return R, t
 

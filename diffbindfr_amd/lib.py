@@ -133,6 +133,24 @@ class PoseCheckOut(C.Structure):
                                           "flat_dev", "n_stereo_flip", "passed")]
 
 
+class InteractionsIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_type", "lig_nbr", "lgrp_ptr", "lgrp",
+                                          "pocket_ptr", "pocket_pos_off", "pocket_pos", "pocket_meta", "static_ptr", "static_pos",
+                                          "static_meta", "rgrp_ptr", "rgrp", "res_ptr", "bits_off")] + \
+               [(n, C.c_int32) for n in ("max_lig", "max_lgrp", "max_res")]
+
+
+class InteractionsOpts(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("hydrophobic_dist", "hbond_dist", "hbond_angle", "ionic_dist", "cation_pi_dist",
+                                         "cation_pi_offset", "pi_dist", "pi_offset", "face_angle", "edge_angle", "xbond_dist",
+                                         "xbond_donor_angle", "xbond_acceptor_min", "xbond_acceptor_max")]
+
+
+class InteractionsOut(C.Structure):
+    _fields_ = [("bits", C.c_void_p), ("counts", C.c_void_p)]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -172,7 +190,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
-           "dbfr_sites_workspace_bytes", "dbfr_find_sites"]
+           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions"]
 
 _lib = None
 
@@ -263,6 +281,7 @@ def load():
     lib.dbfr_xtc_encode.argtypes = [C.POINTER(XtcIn), C.POINTER(XtcOpts), vp, C.c_int64, vp, vp, C.c_size_t, vp]
     lib.dbfr_sites_workspace_bytes.argtypes = [C.POINTER(SitesIn), C.POINTER(C.c_size_t)]
     lib.dbfr_find_sites.argtypes = [C.POINTER(SitesIn), C.POINTER(SitesOpts), C.POINTER(SitesOut), vp, C.c_size_t, vp]
+    lib.dbfr_interactions.argtypes = [C.POINTER(InteractionsIn), C.POINTER(InteractionsOpts), C.POINTER(InteractionsOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

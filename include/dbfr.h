@@ -41,7 +41,9 @@ extern "C" {
                                    dbfr_xtc_in, dbfr_xtc_opts, dbfr_xtc_workspace_bytes, dbfr_xtc_encode, dbfr_pdb_atom_map,
                                    dbfr_pdb_ligand, dbfr_complex_pdb_format, dbfr_complex_pdb_write_files,
                                    dbfr_sites_opts, dbfr_sites_in, dbfr_sites_out, dbfr_sites_workspace_bytes, dbfr_find_sites;
-                                7: + dbfr_test_sde_step (additions only) */
+                                7: + dbfr_test_sde_step (additions only);
+                                   later additions under the same number: dbfr_interactions_in, dbfr_interactions_opts, dbfr_interactions_out,
+                                   dbfr_interactions */
 
 typedef enum {
   DBFR_OK = 0,
@@ -623,6 +625,87 @@ typedef struct {                 /* device arrays [n_frame]; any may be NULL    
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_pose_check(const dbfr_pose_check_in* in, const dbfr_pose_check_opts* opts, const dbfr_pose_check_out* out,
                     void* hip_stream);
+
+/* ---- Protein-ligand interaction fingerprints of poses (csrc/interactions.hip; docs/interactions.md).  A batch of G groups (one
+ * group = the frames of one ligand in one complex), group g holding F_g frames of N_g ligand heavy atoms, M_g pocket atoms per
+ * frame and S_g static receptor atoms shared by its frames (receptor atom b of a frame: pocket atom b for b < M_g, static atom
+ * b - M_g otherwise), LG_g ligand groups, RG_g receptor groups and n_res_g residues.  Atom types are the XS codes of the Vina calls
+ * (0..16; hydrophobic C_H F_H Cl_H Br_H I_H, donors N_D N_DA O_D O_DA, acceptors N_A N_DA O_A O_DA).  A group (ligand or receptor)
+ * is a ring (kind 0, its atoms in cyclic order), a cation centre (1) or an anion centre (2) of up to 6 atoms; its centre is the
+ * centroid of its atoms IN THE FRAME, a ring's normal the normalised Newell sum  sum_k (p_k - c) x (p_k+1 - c)  (a ring whose
+ * sum vanishes is dropped).  Per (frame, residue) one 16-bit word, bits named from the ligand's side (a ligand, b receptor atom,
+ * d their distance; "angle(x-a..b)" is the angle at a between x and b, compared as a cosine; x over a's listed neighbours, y
+ * over b's):
+ *   0 Hydrophobic  both hydrophobic, d <= hydrophobic_dist
+ *   1 HBDonor      a donor, b acceptor, d <= hbond_dist, every angle(x-a..b) >= hbond_angle, every angle(y-b..a) >= hbond_angle
+ *   2 HBAcceptor   a acceptor, b donor, the same geometry
+ *   3 Cationic     ligand cation centre - receptor anion centre <= ionic_dist
+ *   4 Anionic      ligand anion centre - receptor cation centre <= ionic_dist
+ *   5 CationPi     ligand cation centre, receptor ring: centre distance <= cation_pi_dist, offset <= cation_pi_offset (offset =
+ *                  the distance of the cation's projection onto the ring plane from the ring centre)
+ *   6 PiCation     ligand ring, receptor cation centre: the same
+ *   7 FaceToFace   ring - ring: centres <= pi_dist, angle between the normals folded to [0, 90] <= face_angle, the smaller of
+ *                  the two offsets (each centre projected onto the other ring's plane) <= pi_offset
+ *   8 EdgeToFace   the same with the angle >= edge_angle
+ *   9 XBDonor      a of type Cl_H / Br_H / I_H with a carbon among its listed neighbours (c = the first such), b acceptor,
+ *                  d <= xbond_dist, angle(c-a..b) >= xbond_donor_angle, every angle(a..b-y) in [xbond_acceptor_min, xbond_acceptor_max]
+ * counts [n_frame, 10]: the residues of the frame with bit k set.  Only integer ORs and counts leave the kernel, so a frame's
+ * outputs are bitwise the same alone or in any batch.  A frame with a non-finite or out-of-range (|x| > 1e4) ligand or receptor
+ * coordinate gets an all-zero row and counts of -1.  Limits: N_g <= 256, LG_g <= 32, n_res_g <= 16384 (max_* above them:
+ * DBFR_ERR_ARG).  Receptor atoms and receptor groups are not limited.                                                       */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; counts are indexed by frame                           */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_type / lig_nbr (N_g >= 1)                         */
+  const int64_t* lig_pos_off;    /* [G] first row of group g in lig_pos: frame k of g at rows lig_pos_off[g] + k N_g           */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const int8_t*  lig_type;       /* [lig_ptr[G]] XS codes                                                                   */
+  const int32_t* lig_nbr;        /* [lig_ptr[G], 3] local indices of up to 3 bonded heavy neighbours, -1 padded              */
+  const int32_t* lgrp_ptr;       /* [G+1] ligand groups of every group                                                      */
+  const int32_t* lgrp;           /* [lgrp_ptr[G], 8]: kind, 6 local atom indices (-1 padded, at least 1), 0                  */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_meta (M_g atoms per frame, may be 0)    */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                         */
+  const float*   pocket_pos;
+  const int32_t* pocket_meta;    /* [pocket_ptr[G], 4]: type + 256 * residue (0 .. n_res_g - 1), 3 neighbours as receptor atom
+                                    indices b of the group (-1 padded)                                                      */
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / static_meta, or NULL = none             */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of lig_pos                                              */
+  const int32_t* static_meta;    /* like pocket_meta                                                                        */
+  const int32_t* rgrp_ptr;       /* [G+1] receptor groups of every group                                                    */
+  const int32_t* rgrp;           /* [rgrp_ptr[G], 8]: kind + 256 * residue, 6 receptor atom indices b (-1 padded), 0         */
+  const int32_t* res_ptr;        /* [G+1]: n_res_g = res_ptr[g+1] - res_ptr[g]                                               */
+  const int64_t* bits_off;       /* [G] frame k of g writes bits[bits_off[g] + k n_res_g ...]                                */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 32, 16384)                                   */
+  int32_t        max_lgrp;
+  int32_t        max_res;
+} dbfr_interactions_in;
+
+typedef struct {                 /* lengths in A, angles in degrees; defaults in brackets                                    */
+  float hydrophobic_dist;        /* [4.0]                                                                                   */
+  float hbond_dist;              /* [3.5]                                                                                   */
+  float hbond_angle;             /* [90]                                                                                    */
+  float ionic_dist;              /* [5.5]                                                                                   */
+  float cation_pi_dist;          /* [6.0]                                                                                   */
+  float cation_pi_offset;        /* [2.0]                                                                                   */
+  float pi_dist;                 /* [5.5]                                                                                   */
+  float pi_offset;               /* [2.0]                                                                                   */
+  float face_angle;              /* [30]                                                                                    */
+  float edge_angle;              /* [60]                                                                                    */
+  float xbond_dist;              /* [4.0]                                                                                   */
+  float xbond_donor_angle;       /* [135]                                                                                   */
+  float xbond_acceptor_min;      /* [90]                                                                                    */
+  float xbond_acceptor_max;      /* [150]                                                                                   */
+} dbfr_interactions_opts;
+
+typedef struct {                 /* device arrays                                                                           */
+  int16_t* bits;                 /* [sum_g F_g n_res_g]                                                                     */
+  int32_t* counts;               /* [n_frame, 10]                                                                           */
+} dbfr_interactions_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_interactions(const dbfr_interactions_in* in, const dbfr_interactions_opts* opts, const dbfr_interactions_out* out,
+                      void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file
  * files; a file is the frames listed for it, in frame order, with one atom map.  Atom k of a frame is atom_map[map_ptr[m] + k]

@@ -151,6 +151,22 @@ class InteractionsOut(C.Structure):
     _fields_ = [("bits", C.c_void_p), ("counts", C.c_void_p)]
 
 
+class PocketCheckIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "pocket_ptr", "pocket_pos_off", "pocket_pos", "pocket_rad", "pocket_col",
+                                          "pocket_rank", "static_ptr", "static_pos", "static_rad", "static_col", "mov_ptr", "mov_atom",
+                                          "excl_ptr", "excl", "closure_ptr", "closure_ab", "closure_len", "res_ptr", "res_off")] + \
+               [(n, C.c_int32) for n in ("max_pocket", "max_excl", "max_res", "cand_cap")] + [("host", C.c_void_p)]
+
+
+class PocketCheckOpts(C.Structure):
+    _fields_ = [("clash_ratio", C.c_float), ("bond_tol", C.c_float), ("max_clashes", C.c_int32)]
+
+
+class PocketCheckOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("n_clash", "min_ratio", "worst_pair", "res_clash", "n_broken", "max_bond_dev", "passed")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -190,7 +206,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
-           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions"]
+           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check"]
 
 _lib = None
 
@@ -282,6 +298,7 @@ def load():
     lib.dbfr_sites_workspace_bytes.argtypes = [C.POINTER(SitesIn), C.POINTER(C.c_size_t)]
     lib.dbfr_find_sites.argtypes = [C.POINTER(SitesIn), C.POINTER(SitesOpts), C.POINTER(SitesOut), vp, C.c_size_t, vp]
     lib.dbfr_interactions.argtypes = [C.POINTER(InteractionsIn), C.POINTER(InteractionsOpts), C.POINTER(InteractionsOut), vp]
+    lib.dbfr_pocket_check.argtypes = [C.POINTER(PocketCheckIn), C.POINTER(PocketCheckOpts), C.POINTER(PocketCheckOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

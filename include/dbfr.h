@@ -43,7 +43,8 @@ extern "C" {
                                    dbfr_sites_opts, dbfr_sites_in, dbfr_sites_out, dbfr_sites_workspace_bytes, dbfr_find_sites;
                                 7: + dbfr_test_sde_step (additions only);
                                    later additions under the same number: dbfr_interactions_in, dbfr_interactions_opts, dbfr_interactions_out,
-                                   dbfr_interactions */
+                                   dbfr_interactions, dbfr_pocket_check_in, dbfr_pocket_check_opts, dbfr_pocket_check_out,
+                                   dbfr_pocket_check */
 
 typedef enum {
   DBFR_OK = 0,
@@ -705,6 +706,78 @@ typedef struct {                 /* device arrays                               
 
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_interactions(const dbfr_interactions_in* in, const dbfr_interactions_opts* opts, const dbfr_interactions_out* out,
+                      void* hip_stream);
+
+/* ---- Validity checks of each pose's own sampled pocket (csrc/pocketcheck.hip; docs/pocketcheck.md).  A batch of G groups (one
+ * group = the frames of one complex), group g holding F_g frames of M_g pocket atoms each and S_g static receptor atoms shared by
+ * its frames (receptor atom b of a frame: pocket atom b for b < M_g, static atom b - M_g otherwise), r = van der Waals radii
+ * (given per atom), one residue column per atom, and a list of MOVABLE pocket atoms (side-chain atoms beyond CB), each with a
+ * sorted exclusion list: the receptor atoms within 3 bonds of it.
+ *   Check 1 (pocket_steric_clash).  Pair domain: unordered pairs {a, b}, a movable, b any other receptor atom not on a's
+ *     exclusion list (a pair of two movable atoms is one pair).  ratio = d_ab / (r_a + r_b); a pair clashes if ratio <
+ *     clash_ratio.  n_clash [n_frame, 3]: clashing pairs whose partner is movable (sc_sc), a non-movable pocket atom (sc_bb),
+ *     a static atom (sc_static).  min_ratio = the minimum over the domain (+inf: empty domain), worst_pair [n_frame, 2] = the
+ *     pair (a < b, receptor atom indices) of the minimum, ties to the lexicographically smallest pair, (-1, -1) for an empty
+ *     domain.  res_clash (uint8 per frame and residue column) = the clashing pairs the residue takes part in (a pair inside one
+ *     residue counts once), saturating at 255.  Passes if the three counts sum to <= max_clashes.
+ *   Check 2 (pocket_bonds_intact).  Closure bonds (a, b, input length): broken if |d_ab - length| > bond_tol.  n_broken, and
+ *     max_bond_dev = the largest |d_ab - length| (0: no closure bonds).  Passes if n_broken == 0.
+ *   passed: bit 0 = check 1, bit 1 = check 2, bit 2 = both (pk_valid).
+ * Every reduction is a minimum, a maximum or an integer count, so a frame's outputs are bitwise the same alone or in any batch.
+ * A frame with a non-finite or out-of-range (|x| > 1e4) coordinate (or a radius outside (0, 4]) gets counts of -1, NaN floats,
+ * worst_pair (-1, -1), passed 0 and an all-zero res_clash row.  Limits: M_g <= 8192, n_res_g <= 16384, exclusion lists of at
+ * most 32 atoms (max_* above them: DBFR_ERR_ARG).  Static atoms are not limited.                                            */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; per-frame outputs are indexed by frame                */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_rad / _col / _rank (M_g atoms per frame) */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                         */
+  const float*   pocket_pos;     /* [rows, 3]                                                                               */
+  const float*   pocket_rad;     /* [pocket_ptr[G]] radii in (0, 4]                                                         */
+  const int32_t* pocket_col;     /* [pocket_ptr[G]] residue column, 0 .. n_res_g - 1                                        */
+  const int32_t* pocket_rank;    /* [pocket_ptr[G]] position of the atom in its group's movable list, -1 = not movable      */
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / _rad / _col, or NULL = none             */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of pocket_pos                                           */
+  const float*   static_rad;
+  const int32_t* static_col;
+  const int32_t* mov_ptr;        /* [G+1] movable atoms of every group                                                      */
+  const int32_t* mov_atom;       /* [mov_ptr[G]] pocket atom index (0 .. M_g - 1) of every movable atom, ascending per group */
+  const int32_t* excl_ptr;       /* [mov_ptr[G] + 1] CSR over the movable atoms of all groups into excl                      */
+  const int32_t* excl;           /* receptor atom indices b of the group, ascending within a list, at most 32 per list       */
+  const int32_t* closure_ptr;    /* [G+1] closure bonds of every group                                                      */
+  const int32_t* closure_ab;     /* [closure_ptr[G], 2] receptor atom indices                                               */
+  const float*   closure_len;    /* [closure_ptr[G]] length in the input structure (A)                                      */
+  const int32_t* res_ptr;        /* [G+1]: n_res_g = res_ptr[g+1] - res_ptr[g]                                               */
+  const int64_t* res_off;        /* [G] frame k of g writes res_clash[res_off[g] + k n_res_g ...]                            */
+  int32_t        max_pocket;     /* host-known maxima over the groups (<= 8192, 32, 16384)                                  */
+  int32_t        max_excl;
+  int32_t        max_res;
+  int32_t        cand_cap;       /* partner candidates gathered in LDS per round, 0 = 1024 (same bits whatever the value; tests;
+                                    256 .. 1024)                                                                            */
+  const void*    host;           /* NULL, or a dbfr_pocket_check_in whose pointers are HOST copies of the same arrays (the two
+                                    position arrays are not read): every list length, atom index, residue column and radius is
+                                    then validated before the launch (DBFR_ERR_ARG)                                          */
+} dbfr_pocket_check_in;
+
+typedef struct {
+  float   clash_ratio;           /* (0, 10], default 0.75                                                                   */
+  float   bond_tol;              /* A, >= 0, default 0.3                                                                    */
+  int32_t max_clashes;           /* >= 0, default 0                                                                         */
+} dbfr_pocket_check_opts;
+
+typedef struct {                 /* device arrays; any may be NULL                                                          */
+  int32_t* n_clash;              /* [n_frame, 3] sc_sc, sc_bb, sc_static                                                    */
+  float*   min_ratio;            /* [n_frame]                                                                               */
+  int32_t* worst_pair;           /* [n_frame, 2]                                                                            */
+  uint8_t* res_clash;            /* [sum_g F_g n_res_g]                                                                     */
+  int32_t* n_broken;             /* [n_frame]                                                                               */
+  float*   max_bond_dev;         /* [n_frame]                                                                               */
+  int32_t* passed;               /* [n_frame]                                                                               */
+} dbfr_pocket_check_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_pocket_check(const dbfr_pocket_check_in* in, const dbfr_pocket_check_opts* opts, const dbfr_pocket_check_out* out,
                       void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file

@@ -15,5 +15,6 @@ from . import trajectory  # noqa: F401
 from . import sites  # noqa: F401
 from . import interactions  # noqa: F401
 from . import pocketcheck  # noqa: F401
+from . import sasa  # noqa: F401
 
 register_into_druglib()

@@ -167,6 +167,23 @@ class PocketCheckOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("n_clash", "min_ratio", "worst_pair", "res_clash", "n_broken", "max_bond_dev", "passed")]
 
 
+class SasaIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "lig_w", "lig_polar", "pocket_ptr",
+                                          "pocket_pos_off", "pocket_pos", "pocket_rad", "pocket_w", "pocket_col", "pocket_polar",
+                                          "static_ptr", "static_pos", "static_rad", "static_w", "static_col", "static_polar", "res_ptr",
+                                          "res_off", "points")] + \
+               [(n, C.c_int32) for n in ("n_points", "max_lig", "max_pocket", "max_res", "cand_cap")] + [("host", C.c_void_p)]
+
+
+class SasaOpts(C.Structure):
+    _fields_ = [("probe", C.c_float)]
+
+
+class SasaOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("lig_free", "lig_bound", "res_buried", "totals")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -206,7 +223,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
-           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check"]
+           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa"]
 
 _lib = None
 
@@ -299,6 +316,7 @@ def load():
     lib.dbfr_find_sites.argtypes = [C.POINTER(SitesIn), C.POINTER(SitesOpts), C.POINTER(SitesOut), vp, C.c_size_t, vp]
     lib.dbfr_interactions.argtypes = [C.POINTER(InteractionsIn), C.POINTER(InteractionsOpts), C.POINTER(InteractionsOut), vp]
     lib.dbfr_pocket_check.argtypes = [C.POINTER(PocketCheckIn), C.POINTER(PocketCheckOpts), C.POINTER(PocketCheckOut), vp]
+    lib.dbfr_sasa.argtypes = [C.POINTER(SasaIn), C.POINTER(SasaOpts), C.POINTER(SasaOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

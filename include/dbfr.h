@@ -44,7 +44,7 @@ extern "C" {
                                 7: + dbfr_test_sde_step (additions only);
                                    later additions under the same number: dbfr_interactions_in, dbfr_interactions_opts, dbfr_interactions_out,
                                    dbfr_interactions, dbfr_pocket_check_in, dbfr_pocket_check_opts, dbfr_pocket_check_out,
-                                   dbfr_pocket_check */
+                                   dbfr_pocket_check, dbfr_sasa_in, dbfr_sasa_opts, dbfr_sasa_out, dbfr_sasa */
 
 typedef enum {
   DBFR_OK = 0,
@@ -779,6 +779,75 @@ typedef struct {                 /* device arrays; any may be NULL              
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_pocket_check(const dbfr_pocket_check_in* in, const dbfr_pocket_check_opts* opts, const dbfr_pocket_check_out* out,
                       void* hip_stream);
+
+/* ---- Solvent-accessible and buried surface area of poses (csrc/sasa.hip; docs/sasa.md): Shrake-Rupley with integer results.  A
+ * batch of G groups (one group = the frames of one ligand in one complex), group g holding F_g frames of N_g ligand heavy atoms
+ * (L), M_g pocket atoms per frame and S_g static receptor atoms shared by its frames (R; receptor atom b of a frame: pocket atom
+ * b for b < M_g, static atom b - M_g otherwise) and n_res_g residue columns.  Atom i has a radius r_i in (0, 4], the expanded
+ * radius R_i = r_i + probe, an integer area weight w_i > 0 (n_points w_i <= 2^21), a polar flag and, in R, a residue column.
+ * points = n_points unit vectors u_k.  Point k of atom i is buried by atom c != i when |(x_i - x_c) + R_i u_k| < R_c; the
+ * difference x_i - x_c is formed first and no absolute point position is ever formed (float32, every operation rounded).
+ *   lig_free   points of a ligand atom buried by no other ligand atom                  (the free ligand in the pose's conformation)
+ *   lig_bound  points of a ligand atom buried by no other atom of L u R
+ *   buried_b   points of receptor atom b buried by at least one ligand atom and by no other receptor atom; summed with weights
+ *              this is SASA(receptor alone) - SASA(receptor in the complex)
+ *   res_buried [frame, residue column] = sum over the residue's atoms of buried_b w_b
+ *   totals     [frame, 6] = sum lig_free w, sum lig_bound w, the same two over the polar ligand atoms, sum buried_b w_b over R,
+ *              the same over the polar receptor atoms.  An area is a sum in units of 2^-12 A^2 when w = round(4 pi R^2 / n 4096).
+ * Every reduction is an integer sum, so a frame's outputs are bitwise the same alone, in any batch and for any cand_cap.  A frame
+ * with a non-finite or out-of-range (|x| > 1e4) coordinate (or a radius outside (0, 4]) gets -1 in every count and total and an
+ * all-zero res_buried row.  Limits: N_g <= 256, M_g <= 8192, n_res_g <= 16384 (max_* above them: DBFR_ERR_ARG); n_points a
+ * multiple of 64 in [64, 512]; probe in [0, 2].  Static atoms are not limited.                                              */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; totals are indexed by frame                           */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_rad / _w / _polar (N_g atoms per frame, may be 0)  */
+  const int64_t* lig_pos_off;    /* [G] frame k of g at rows lig_pos_off[g] + k N_g of lig_pos, lig_free and lig_bound        */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const float*   lig_rad;        /* [lig_ptr[G]] radii in (0, 4]                                                            */
+  const int32_t* lig_w;          /* [lig_ptr[G]] area weight of one point, > 0                                              */
+  const uint8_t* lig_polar;      /* [lig_ptr[G]] 1 = polar (N, O)                                                           */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_rad / _w / _col / _polar (may be 0 atoms) */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                         */
+  const float*   pocket_pos;     /* [rows, 3]                                                                               */
+  const float*   pocket_rad;
+  const int32_t* pocket_w;
+  const int32_t* pocket_col;     /* residue column, 0 .. n_res_g - 1                                                        */
+  const uint8_t* pocket_polar;
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / _rad / _w / _col / _polar, or NULL = none */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of lig_pos                                              */
+  const float*   static_rad;
+  const int32_t* static_w;
+  const int32_t* static_col;
+  const uint8_t* static_polar;
+  const int32_t* res_ptr;        /* [G+1]: n_res_g = res_ptr[g+1] - res_ptr[g]                                               */
+  const int64_t* res_off;        /* [G] frame k of g writes res_buried[res_off[g] + k n_res_g ...]                           */
+  const float*   points;         /* [n_points, 3] unit vectors                                                              */
+  int32_t        n_points;       /* 64, 128, ..., 512                                                                       */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 8192, 16384)                                 */
+  int32_t        max_pocket;
+  int32_t        max_res;
+  int32_t        cand_cap;       /* receptor atoms kept in LDS per frame, 0 = 1536 (same bits whatever the value; tests;
+                                    256 .. 2048); the atoms beyond it are read from memory                                  */
+  const void*    host;           /* NULL, or a dbfr_sasa_in whose pointers are HOST copies of the same arrays (the two frame
+                                    position arrays are not read): every count, residue column, radius, weight and point is
+                                    then validated before the launch (DBFR_ERR_ARG)                                          */
+} dbfr_sasa_in;
+
+typedef struct {
+  float probe;                   /* A, [0, 2], default 1.4                                                                  */
+} dbfr_sasa_opts;
+
+typedef struct {                 /* device arrays; any may be NULL                                                          */
+  int32_t* lig_free;             /* [rows of lig_pos]                                                                       */
+  int32_t* lig_bound;            /* [rows of lig_pos]                                                                       */
+  int32_t* res_buried;           /* [sum_g F_g n_res_g]                                                                     */
+  int64_t* totals;               /* [n_frame, 6]                                                                            */
+} dbfr_sasa_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_sasa(const dbfr_sasa_in* in, const dbfr_sasa_opts* opts, const dbfr_sasa_out* out, void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file
  * files; a file is the frames listed for it, in frame order, with one atom map.  Atom k of a frame is atom_map[map_ptr[m] + k]

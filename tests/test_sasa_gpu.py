@@ -1,0 +1,292 @@
+"""dbfr_sasa on the device against the float64 restatement in tests/sasa_ref.py (lo <= got <= hi for every per-atom count, every
+residue sum and every total): random ragged batches, the smallest candidate list, batch independence, hand-built motifs, the
+identities between the outputs, unusable coordinates and refusals, and the annotation at the end of the export pipeline."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from diffbindfr_amd import export as pex, sasa
+from diffbindfr_amd.interactions import residue_tags
+from diffbindfr_amd.ligand import SdfTemplate
+
+import pocketcheck_ref  # noqa: E402  (a module next to the test files: pytest puts their directory on sys.path)
+import sasa_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+GOLDEN = pocketcheck_ref.GOLDEN
+
+
+def _dev(gr):
+    d = dict(gr, lig=torch.as_tensor(gr["lig"], device=DEV))
+    if gr.get("pocket") is not None:
+        d["pocket"] = torch.as_tensor(gr["pocket"], device=DEV)
+    return d
+
+
+def _run(groups, **opts):
+    """The device outputs on the host: the lists per group of [F, N] / [F, n_res] arrays, the totals and the weights."""
+    out = sasa.burial([_dev(g) for g in groups], **opts)
+    r = {k: [x.cpu().numpy() for x in out[k]] for k in ("lig_free", "lig_bound", "res_buried")}
+    r["totals"] = out["totals"].cpu().numpy()
+    r["weights"] = out["weights"]
+    return r
+
+
+def _same_bits(a, b):
+    return a["totals"].tobytes() == b["totals"].tobytes() and all(
+        x.tobytes() == y.tobytes() for k in ("lig_free", "lig_bound", "res_buried") for x, y in zip(a[k], b[k]))
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(seed, n_points):
+    """The batch of a seed and the restatement of its every frame, computed once and left unchanged."""
+    groups = ref.random_batch(seed)
+    pts = sasa.sphere_points(n_points)
+    want = []
+    for gr in groups:
+        w = ref.group_weights(gr, sasa.area_weights, 1.4, n_points)
+        want.append([ref.frame_ref(gr, f, pts, w) for f in range(gr["lig"].shape[0])])
+    return groups, want
+
+
+def _inside(got, g, f, i, want, where):
+    """Frame i of the launch (frame f of group g) inside the restatement's interval, everywhere."""
+    print(where, got["totals"][i].tolist(), want["totals"][0].tolist(), want["totals"][1].tolist(), "open", want["open"])
+    for k in ("lig_free", "lig_bound", "res_buried"):
+        v = got[k][g][f].astype(np.int64)
+        assert v.shape == want[k][0].shape and (want[k][0] <= v).all() and (v <= want[k][1]).all(), (where, k, np.flatnonzero(
+            (v < want[k][0]) | (v > want[k][1])))
+    t = got["totals"][i]
+    assert (want["totals"][0] <= t).all() and (t <= want["totals"][1]).all(), (where, t, want["totals"])
+
+
+def _compare(groups, got, want):
+    i = 0
+    for g, gr in enumerate(groups):
+        for f in range(gr["lig"].shape[0]):
+            _inside(got, g, f, i, want[g][f], (g, f))
+            i += 1
+    assert i == len(got["totals"])
+
+
+@pytest.mark.parametrize("n_points", [64, 256])
+@pytest.mark.parametrize("seed", ref.BATCH_SEEDS)
+def test_kernel_matches_the_float64_restatement(seed, n_points):
+    groups, want = _batch(seed, n_points)
+    # what the batch must hold
+    assert "pocket" not in groups[0] and "static" not in groups[0] and "static" not in groups[1] and "pocket" in groups[1]
+    assert groups[2]["lig"].shape[1] == 1 and groups[3]["lig"].shape[:2] == (1, 256) and groups[4]["static"].shape[0] >= 3000
+    assert groups[5]["lig"].shape[0] == 5
+    far = np.concatenate([groups[6]["pocket"][0], groups[6]["static"]])
+    assert np.sqrt(((far[:, None] - groups[6]["lig"][0][None]) ** 2).sum(-1)).min() > 12.0
+    got = _run(groups, n_points=n_points)
+    _compare(groups, got, want)
+    first = np.concatenate([[0], np.cumsum([g["lig"].shape[0] for g in groups])])
+    for g in (0, 6):                                                  # no receptor, and a receptor out of reach
+        assert np.array_equal(got["lig_bound"][g], got["lig_free"][g]) and (got["lig_free"][g] > 0).any()
+        assert (got["totals"][first[g]:first[g + 1], 4:] == 0).all() and not got["res_buried"][g].any()
+    total = got["totals"].sum(0)
+    assert total[4] > 0 and total[1] < total[0], total
+    assert (got["totals"][first[4]:first[5], 4] > 0).all()             # the group beyond the candidate list buries receptor surface
+
+
+@pytest.mark.parametrize("seed", ref.BATCH_SEEDS)
+def test_the_smallest_candidate_list_gives_the_same_bits(seed):
+    groups, _ = _batch(seed, 256)
+    assert _same_bits(_run(groups, cand_cap=256), _run(groups))
+    assert _same_bits(_run(groups, cand_cap=2048), _run(groups))
+
+
+def test_frames_are_bitwise_independent_of_the_batch():
+    groups, _ = _batch(ref.BATCH_SEEDS[0], 256)
+    full = _run(groups)
+    back = _run(groups[::-1])
+    first = np.concatenate([[0], np.cumsum([g["lig"].shape[0] for g in groups])])
+    bfirst = np.concatenate([[0], np.cumsum([g["lig"].shape[0] for g in groups[::-1]])])
+    for g, gr in enumerate(groups):
+        s = len(groups) - 1 - g
+        one = _run([gr])
+        for k in ("lig_free", "lig_bound", "res_buried"):
+            assert full[k][g].tobytes() == back[k][s].tobytes() == one[k][0].tobytes(), (g, k)
+        assert full["totals"][first[g]:first[g + 1]].tobytes() == back["totals"][bfirst[s]:bfirst[s + 1]].tobytes() == one["totals"].tobytes(), g
+
+
+# ------------------------------------------------------------------------------------------------ hand-built motifs
+def _motif(lig, lig_rad, rec=(), rec_rad=(), rec_col=(), lig_polar=None, rec_polar=None):
+    """One frame: ligand atoms and pocket atoms at the given positions with the given radii and residue columns."""
+    lig = np.asarray(lig, np.float32).reshape(1, -1, 3)
+    gr = dict(lig=lig, lig_rad=np.asarray(lig_rad, np.float32),
+              lig_polar=np.zeros(lig.shape[1], np.uint8) if lig_polar is None else np.asarray(lig_polar, np.uint8))
+    rec = np.asarray(rec, np.float32).reshape(1, -1, 3)
+    if rec.shape[1]:
+        gr.update(pocket=rec, pocket_rad=np.asarray(rec_rad, np.float32), pocket_col=np.asarray(rec_col, np.int32),
+                  pocket_polar=np.zeros(rec.shape[1], np.uint8) if rec_polar is None else np.asarray(rec_polar, np.uint8),
+                  n_res=int(max(rec_col)) + 1)
+    return gr
+
+
+def test_motifs():
+    n, R = 256, 1.7 + 1.4
+    cases = [
+        _motif([[0, 0, 0]], [1.7]),                                                             # 0 an isolated atom
+        _motif([[0, 0, 0]], [1.7], [[2 * R + 0.01, 0, 0]], [1.7], [0]),                         # 1 a pair just beyond R_a + R_b
+        _motif([[0, 0, 0]], [1.7], [[2 * R - 0.7, 0, 0]], [1.7], [0]),                          # 2 a pair inside
+        _motif([[0, 0, 0]], [1.47], [[0.5, 0, 0]], [4.0], [0]),                                 # 3 swallowed by a receptor sphere
+        _motif([[0, 0, 0]], [1.7], [[5, 0, 0], [2.5, 3.0, 0]], [1.7, 1.7], [0, 1]),             # 4 the facing atom, its face covered
+        _motif([[0, 0, 0]], [1.7], [[5, 0, 0]], [1.7], [0]),                                    # 5 the facing atom alone
+        _motif([[0, 0, 0], [20, 0, 0]], [1.55, 1.7], [[4.5, 0, 0], [24.5, 0, 0]], [1.52, 1.7], [0, 1], [1, 0], [1, 0]),   # 6 polar / apolar
+    ]
+    got = _run(cases)
+    pts = sasa.sphere_points(n)
+    for i, gr in enumerate(cases):
+        _inside(got, i, 0, i, ref.frame_ref(gr, 0, pts, ref.group_weights(gr, sasa.area_weights, 1.4, n)), i)
+    t, w = got["totals"], got["weights"]
+    assert got["lig_free"][0].tolist() == [[n]] and got["lig_bound"][0].tolist() == [[n]] and t[0].tolist() == [n * w[0]["lig"][0]] * 2 + [0] * 4
+    assert got["lig_bound"][1].tolist() == [[n]] and t[1, 4] == 0 and not got["res_buried"][1].any()
+    assert 0 < got["lig_bound"][2][0, 0] < n and t[2, 4] > 0 and got["res_buried"][2][0, 0] == t[2, 4]
+    # (equal spheres: the ligand atom loses what the receptor atom loses, the cap n (1 - d / 2R) / 2 within 8 points)
+    cap = n * (1.0 - (2 * R - 0.7) / (2 * R)) / 2.0
+    assert abs(n - got["lig_bound"][2][0, 0] - cap) <= 8 and abs(t[2, 4] / w[2]["pocket"][0] - cap) <= 8
+    assert got["lig_free"][3].tolist() == [[n]] and got["lig_bound"][3].tolist() == [[0]]
+    assert 0 < got["res_buried"][4][0, 0] < got["res_buried"][5][0, 0]
+    # polar and apolar parts apart: the N atom with its O neighbour, the C atom with its C neighbour
+    wl, wp = w[6]["lig"].astype(np.int64), w[6]["pocket"].astype(np.int64)
+    fr, bd, rb = got["lig_free"][6][0] * wl, got["lig_bound"][6][0] * wl, got["res_buried"][6][0]
+    assert t[6].tolist() == [fr.sum(), bd.sum(), fr[0], bd[0], rb.sum(), rb[0]] and (rb > 0).all() and (bd < fr).all()
+    assert rb[0] % wp[0] == 0 and rb[1] % wp[1] == 0
+    # the probe is an option: without it the pair of case 2 does not touch
+    dry = _run([cases[2]], probe=0.0)
+    assert dry["lig_bound"][0].tolist() == [[n]] and dry["totals"][0, 4] == 0
+
+
+@pytest.mark.parametrize("seed", ref.BATCH_SEEDS)
+def test_identities_on_the_random_batch(seed):
+    groups, _ = _batch(seed, 256)
+    got = _run(groups)
+    i = 0
+    for g, gr in enumerate(groups):
+        wl = got["weights"][g]["lig"].astype(np.int64)
+        lpol = gr["lig_polar"] != 0
+        for f in range(gr["lig"].shape[0]):
+            t = got["totals"][i]
+            fr, bd = got["lig_free"][g][f].astype(np.int64), got["lig_bound"][g][f].astype(np.int64)
+            assert (bd <= fr).all() and (fr <= 256).all() and (bd >= 0).all(), (g, f)
+            assert t[0] == (fr * wl).sum() and t[1] == (bd * wl).sum() and t[2] == (fr * wl)[lpol].sum() and t[3] == (bd * wl)[lpol].sum()
+            assert got["res_buried"][g][f].astype(np.int64).sum() == t[4] and (got["res_buried"][g][f] >= 0).all(), (g, f)
+            assert 0 <= t[2] <= t[0] and 0 <= t[3] <= t[1] and 0 <= t[5] <= t[4], (g, f, t)
+            i += 1
+
+
+def test_unusable_coordinates_and_refusals():
+    groups, _ = _batch(ref.BATCH_SEEDS[0], 256)
+    gr = groups[5]
+    with pytest.raises(sasa.DbfrError, match="no CPU path"):
+        sasa.burial([dict(gr, lig=torch.as_tensor(gr["lig"]), pocket=torch.as_tensor(gr["pocket"]))])
+    with pytest.raises(sasa.DbfrError, match="no CPU path"):
+        sasa.burial([dict(_dev(gr), pocket=torch.as_tensor(gr["pocket"]))])
+    with pytest.raises(sasa.DbfrError, match="multiple of 64"):
+        sasa.burial([_dev(gr)], n_points=96)
+    with pytest.raises(sasa.DbfrError, match="radius"):
+        sasa.burial([_dev(dict(gr, lig_rad=np.full(12, 4.5, np.float32)))])
+    with pytest.raises(sasa.DbfrError, match="column"):
+        sasa.burial([_dev(dict(gr, n_res=3))])
+    with pytest.raises(sasa.DbfrError, match="256"):
+        sasa.burial([_dev(dict(gr, lig=np.zeros((1, 257, 3), np.float32), lig_rad=np.full(257, 1.7), lig_polar=np.zeros(257)))])
+    # a NaN ligand coordinate, a far-away pocket coordinate: -1 and a zero row; the other frames are whole
+    lig, pocket = gr["lig"].copy(), gr["pocket"].copy()
+    lig[0, 3, 1] = np.nan
+    pocket[1, 7, 0] = 2.0e4
+    pocket[2, 5, 2] = np.inf
+    got = _run([dict(gr, lig=lig, pocket=pocket)])
+    clean = _run([gr])
+    assert (got["totals"][:3] == -1).all() and (got["lig_free"][0][:3] == -1).all() and (got["lig_bound"][0][:3] == -1).all()
+    assert not got["res_buried"][0][:3].any() and clean["res_buried"][0][:3].any()
+    for k in ("lig_free", "lig_bound", "res_buried"):
+        assert got[k][0][3:].tobytes() == clean[k][0][3:].tobytes(), k
+    assert got["totals"][3:].tobytes() == clean["totals"][3:].tobytes()
+    # NULL outputs are accepted
+    import ctypes as C
+    from diffbindfr_amd import lib as L
+    lib = L.load()
+    t = {k: torch.as_tensor(v, device=DEV) for k, v in _flat_inputs(gr).items()}
+    order = [f for f, _ in L.SasaIn._fields_][2:25]
+    tot = torch.zeros(5, 6, dtype=torch.int64, device=DEV)
+    c_in = L.SasaIn(1, 5, *[t[k].data_ptr() for k in order], 256, 12, int(gr["pocket"].shape[1]), int(gr["n_res"]), 0, None)
+    for c_out in (L.SasaOut(None, None, None, tot.data_ptr()), L.SasaOut(None, None, None, None)):
+        assert lib.dbfr_sasa(C.byref(c_in), None, C.byref(c_out), None) == 0, lib.dbfr_last_error()
+        torch.cuda.synchronize()
+    assert np.array_equal(tot.cpu().numpy(), clean["totals"])
+
+
+def _flat_inputs(gr):
+    """The arrays of dbfr_sasa_in for one group, as the Python layer lays them out."""
+    F, N, M = gr["lig"].shape[0], gr["lig"].shape[1], gr["pocket"].shape[1]
+    S = gr["static"].shape[0]
+    w = lambda r: sasa.area_weights(np.asarray(r, np.float32), 1.4, 256)
+    return dict(frame_ptr=np.array([0, F], np.int32), lig_ptr=np.array([0, N], np.int32), lig_pos_off=np.zeros(1, np.int64),
+                lig_pos=gr["lig"].reshape(-1), lig_rad=gr["lig_rad"], lig_w=w(gr["lig_rad"]), lig_polar=gr["lig_polar"],
+                pocket_ptr=np.array([0, M], np.int32), pocket_pos_off=np.zeros(1, np.int64), pocket_pos=gr["pocket"].reshape(-1),
+                pocket_rad=gr["pocket_rad"], pocket_w=w(gr["pocket_rad"]), pocket_col=gr["pocket_col"], pocket_polar=gr["pocket_polar"],
+                static_ptr=np.array([0, S], np.int32), static_pos=gr["static"].reshape(-1), static_rad=gr["static_rad"],
+                static_w=w(gr["static_rad"]), static_col=gr["static_col"], static_polar=gr["static_polar"],
+                res_ptr=np.array([0, gr["n_res"]], np.int32), res_off=np.zeros(1, np.int64), points=sasa.sphere_points(256).reshape(-1))
+
+
+# ------------------------------------------------------------------------------------------------ the end of the pipeline
+def _3dbs_entry(P):
+    """An export.ComplexOutput of the 3DBS fixture (built like the one of tests/test_pocketcheck_gpu.py) whose final frames are
+    the crystal ligand pose against the input pocket, P times."""
+    z = pocketcheck_ref.load_3dbs()
+    mb = str(np.load(os.path.join(GOLDEN, "vina_3dbs.npz"))["molblock"])
+    xc = (z["lig_pos"] - z["center"]).astype(np.float32)
+    topo = pex.ProteinTopology(z["aatype"], z["atom37_pos"], z["atom37_mask"], z["residue_index"], z["chain_index"], z["b_factors"],
+                               str(z["remark"]), np.nonzero(z["pocket_mask"])[0])
+    prot = torch.as_tensor(np.repeat(z["target_atom14"][None], P, 0), dtype=torch.float32)[:, None].contiguous().to(DEV)
+    e = pex.ComplexOutput(name="set:3dbs", ligand_traj=torch.as_tensor(np.repeat(xc[None], P, 0))[:, None].to(DEV),
+                          protein_traj=prot, pocket_center_pos=z["center"], ligand_pos=z["lig_pos"],
+                          ligand_labels=z["lig_elements"], ligand_edge_index=z["lig_edge_index"], topology=topo,
+                          atom14_position=z["target_atom14"], atom14_mask=z["target_atom14_mask"],
+                          aatype=z["aatype"][z["pocket_mask"]], row={"protein": "3dbs_protein.pdb", "ligand": "x.sdf"},
+                          sdf_template=SdfTemplate.from_molblock(mb))
+    return e, z
+
+
+def test_annotate_at_the_end_of_the_pipeline():
+    import pandas as pd
+    e, z = _3dbs_entry(2)
+    frame = pd.DataFrame({"pose": [0, 1], "name": ["3dbs"] * 2})
+    df = sasa.annotate([e], frame)
+    assert list(df.columns) == ["pose", "name"] + sasa.COLUMNS and len(df) == 2
+    assert ((df["sasa_buried_frac"] > 0) & (df["sasa_buried_frac"] <= 1)).all()
+    assert df.iloc[0].tolist()[2:] == df.iloc[1].tolist()[2:]                       # the same pose twice
+    tags = set(residue_tags(e.topology))
+    parts = [p.rsplit(":", 1) for p in df["sasa_interface"][0].split(";")]
+    assert len(parts) == df["sasa_n_interface"][0] > 3 and all(t in tags and float(a) >= 1.0 for t, a in parts)
+    assert np.isclose(df["sasa_bsa"][0], df["sasa_buried_lig"][0] + df["sasa_buried_rec"][0])
+    assert np.isclose(df["sasa_buried_lig"][0], df["sasa_lig_free"][0] - df["sasa_lig_bound"][0]) and df["sasa_buried_rec"][0] > 0
+    assert 0 <= df["sasa_buried_lig_polar"][0] <= df["sasa_buried_lig"][0] and 0 <= df["sasa_buried_rec_polar"][0] <= df["sasa_buried_rec"][0]
+    print(df.iloc[0].to_dict())
+    # the crystal pose against the same ligand 30 A away, in the direction (of 64) that leaves the protein furthest behind
+    allx = z["atom37_pos"][z["atom37_mask"] > 0.5].astype(np.float64)
+    moved = [z["lig_pos"] + 30.0 * u for u in sasa.sphere_points(64).astype(np.float64)]
+    gap = [np.sqrt(((allx[:, None] - x[None]) ** 2).sum(-1)).min() for x in moved]
+    away = moved[int(np.argmax(gap))]
+    assert max(gap) > 7.0                                                            # beyond any R_a + R_b
+    ref_df = sasa.annotate([e], frame, poses=[np.stack([z["lig_pos"], away])], reference="input")
+    assert list(ref_df.columns) == ["pose", "name"] + sasa.COLUMNS + sasa.REFERENCE_COLUMNS
+    assert ref_df["sasa_buried_frac"][0] > ref_df["sasa_buried_frac"][1] == 0.0
+    assert ref_df["sasa_bsa"][1] == 0.0 and ref_df["sasa_n_interface"][1] == 0 and ref_df["sasa_interface"][1] == ""
+    assert ref_df["sasa_buried_frac_ref"].tolist() == [ref_df["sasa_buried_frac"][0]] * 2
+    assert ref_df["sasa_interface_recovery"].tolist() == [1.0, 0.0]
+    assert ref_df["sasa_interface"][0] == df["sasa_interface"][0]
+    assert abs(ref_df["sasa_lig_free"][1] / ref_df["sasa_lig_free"][0] - 1.0) < 0.01 and ref_df["sasa_lig_bound"][1] == ref_df["sasa_lig_free"][1]
+    rep = sasa.report(ref_df)
+    assert rep["metric"].tolist() == ["n", "median_buried_frac", "share_buried"] and rep["value"][0] == 2.0
+    big = sasa.annotate([e], frame, interface_area=10.0)
+    assert 0 < big["sasa_n_interface"][0] < df["sasa_n_interface"][0]
+    with pytest.raises(sasa.DbfrError, match="frame rows"):
+        sasa.annotate([e], frame.iloc[:1])

@@ -16,5 +16,6 @@ from . import sites  # noqa: F401
 from . import interactions  # noqa: F401
 from . import pocketcheck  # noqa: F401
 from . import sasa  # noqa: F401
+from . import apoholo  # noqa: F401
 
 register_into_druglib()

@@ -184,6 +184,28 @@ class SasaOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("lig_free", "lig_bound", "res_buried", "totals")]
 
 
+class HoloSiteIn(C.Structure):
+    _fields_ = [("n_pair", C.c_int32)] + [(n, C.c_void_p) for n in ("atom_ptr", "atom_pos", "atom_res", "lig_ptr", "lig_pos", "res_ptr")] + \
+               [("n_res", C.c_int32), ("max_atoms", C.c_int32), ("cutoff", C.c_float)]
+
+
+class HoloMetricsIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "site_ptr", "site_aatype", "site_row", "site_matched", "holo14", "holo_mask", "apo14",
+                                          "frame_mask", "holo_chi", "site_off", "res_ptr", "pocket_off", "pocket", "hlig_ptr", "hlig",
+                                          "pair_off", "lig_ptr", "lig_off", "lig", "perm_ptr", "perm_off", "perms")] + \
+               [(n, C.c_int32) for n in ("max_site", "max_res", "max_lig")] + [("host", C.c_void_p)]
+
+
+class HoloMetricsOpts(C.Structure):
+    _fields_ = [("radius", C.c_float)]
+
+
+class HoloMetricsOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("pair_dist", "plddt_den", "lddt_den", "sc_rmsd", "sc_sq_sum", "sc_n", "chi", "altchi", "dchi",
+                                          "plddt_num", "lddt_num")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -223,7 +245,8 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
-           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa"]
+           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
+           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics"]
 
 _lib = None
 
@@ -317,6 +340,9 @@ def load():
     lib.dbfr_interactions.argtypes = [C.POINTER(InteractionsIn), C.POINTER(InteractionsOpts), C.POINTER(InteractionsOut), vp]
     lib.dbfr_pocket_check.argtypes = [C.POINTER(PocketCheckIn), C.POINTER(PocketCheckOpts), C.POINTER(PocketCheckOut), vp]
     lib.dbfr_sasa.argtypes = [C.POINTER(SasaIn), C.POINTER(SasaOpts), C.POINTER(SasaOut), vp]
+    lib.dbfr_seq_align.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32]
+    lib.dbfr_holo_site.argtypes = [C.POINTER(HoloSiteIn), vp, vp]
+    lib.dbfr_holo_metrics.argtypes = [C.POINTER(HoloMetricsIn), C.POINTER(HoloMetricsOpts), C.POINTER(HoloMetricsOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

@@ -44,7 +44,9 @@ extern "C" {
                                 7: + dbfr_test_sde_step (additions only);
                                    later additions under the same number: dbfr_interactions_in, dbfr_interactions_opts, dbfr_interactions_out,
                                    dbfr_interactions, dbfr_pocket_check_in, dbfr_pocket_check_opts, dbfr_pocket_check_out,
-                                   dbfr_pocket_check, dbfr_sasa_in, dbfr_sasa_opts, dbfr_sasa_out, dbfr_sasa */
+                                   dbfr_pocket_check, dbfr_sasa_in, dbfr_sasa_opts, dbfr_sasa_out, dbfr_sasa, dbfr_seq_align,
+                                   dbfr_holo_site_in, dbfr_holo_site, dbfr_holo_metrics_in, dbfr_holo_metrics_opts, dbfr_holo_metrics_out,
+                                   dbfr_holo_metrics */
 
 typedef enum {
   DBFR_OK = 0,
@@ -848,6 +850,118 @@ typedef struct {                 /* device arrays; any may be NULL              
 
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_sasa(const dbfr_sasa_in* in, const dbfr_sasa_opts* opts, const dbfr_sasa_out* out, void* hip_stream);
+
+/* ---- Holo-pocket recovery of apo / AF2 docking (csrc/apoholo.hip; docs/apoholo.md): what the reference's pair_spatial_metrics
+ * (DiffBindFR/utils/apo_holo.py) measures between a holo crystal structure and the docked apo structure, for every pose.
+ *
+ * Global sequence alignment, host only (no GPU call), library threads over a ragged batch of n_pair sequence pairs.  Scoring is
+ * match 1, mismatch 0, gaps 0: the score is the length of the longest common subsequence.  Residue codes outside 0..19 match
+ * nothing.  With S[i][j] the score of a[0..i) against b[0..j) the traceback runs from (na, nb): take the pair (i-1, j-1) when
+ * a[i-1] == b[j-1] and S[i][j] == S[i-1][j-1] + 1, else step i-1 when S[i-1][j] == S[i][j], else step j-1.
+ * a_to_b[a_ptr[p] + i] = index in sequence b of pair p of the identical residue a[i] is paired with, or -1.  na nb above
+ * DBFR_ALIGN_MAX_CELLS (2^26) is refused with DBFR_ERR_ARG.  n_threads <= 0: one per core, at most 16.                     */
+#define DBFR_ALIGN_MAX_CELLS (1 << 26)
+int dbfr_seq_align(int32_t n_pair, const int32_t* a_ptr, const int32_t* a, const int32_t* b_ptr, const int32_t* b,
+                   int32_t* a_to_b, int32_t* score, int32_t n_threads);
+
+/* Binding-site selection on the device, one launch for a ragged batch of n_pair structures: residue r of pair p is flagged when
+ * any of its atoms lies within cutoff (sqrt(d2) <= cutoff, float32) of any ligand atom.  Atoms are whatever the caller lists
+ * (heavy atoms and, for selection only, hydrogens), each with the residue it belongs to.  All pointers are device pointers.  */
+typedef struct {
+  int32_t        n_pair;
+  const int32_t* atom_ptr;       /* [n_pair+1] atoms of every pair in atom_pos / atom_res                                    */
+  const float*   atom_pos;       /* [atom_ptr[n_pair], 3]                                                                   */
+  const int32_t* atom_res;       /* [atom_ptr[n_pair]] residue of the atom, 0 .. n_res_p - 1 (others are skipped)             */
+  const int32_t* lig_ptr;        /* [n_pair+1] ligand atoms of every pair in lig_pos                                         */
+  const float*   lig_pos;        /* [lig_ptr[n_pair], 3]                                                                    */
+  const int32_t* res_ptr;        /* [n_pair+1] residues of every pair in `site`                                              */
+  int32_t        n_res;          /* res_ptr[n_pair] (host-known): the bytes of `site`                                        */
+  int32_t        max_atoms;      /* host-known maximum of the atoms of one pair                                             */
+  float          cutoff;         /* A, (0, 100]                                                                             */
+} dbfr_holo_site_in;
+/* site: [res_ptr[n_pair]] bytes, zeroed by the call on the stream, 1 = site residue.                                        */
+int dbfr_holo_site(const dbfr_holo_site_in* in, uint8_t* site, void* hip_stream);
+
+/* The per-frame metrics.  A batch of G groups (one group = one complex with its holo/apo pair record), group g holding F_g frames
+ * (poses), S_g site residues, R_g sampled pocket rows per frame, H_g holo ligand atoms, N_g atoms of the pose's own ligand
+ * (0 = none) and n_perm_g automorphisms of it.  Site residue s has a type, a `matched` flag, its holo atom14 coordinates and mask in
+ * the frame of the poses, and the frame's residue: pocket row site_row[s] of the frame when site_row[s] >= 0, else the static
+ * atoms apo14[s]; frame_mask[s] is the atom14 mask of that residue.  Unmatched rows get NaN / 0 everywhere.
+ *   pair_dist [group, s, 14, H]  |holo atom - holo ligand atom| (float32) of every SCORED pair, -1 elsewhere.  Scored: s matched,
+ *              the atom present in holo_mask and frame_mask, distance < radius.  Formed once per group; every frame reads it.
+ *   plddt_den [group, s]  scored pairs of s                                      (int32)
+ *   lddt_den  [group]     sum of plddt_den                                       (int32)
+ *   sc_rmsd   [frame, s]  sqrt(mean |holo - frame|^2) over atom14 slots 4..13 (the heavy atoms but N, CA, C, O), NaN when the two
+ *              present-atom sets differ or are empty; sc_sq_sum / sc_n [frame]: the sum of squares and atom count pooled over s
+ *   chi       [frame, s, 4], altchi [frame, s, 2]  chi1..chi4 of the frame's residue (IUPAC sign, radians, the library's chi atom
+ *              table) and the alternative naming: altchi1 of VAL (CG2), altchi2 of ASP (OD2), LEU, PHE, TYR (CD2); NaN elsewhere
+ *   dchi      [frame, s, 4]  |chi - holo_chi| wrapped into [0, pi]; where the alternative exists and is defined, the minimum of
+ *              that and |altchi - holo_chi| wrapped
+ *   plddt_num [frame, s]  sum over the scored pairs of how many of |d_holo - d_frame| < 0.5, 1, 2, 4 hold, d_frame measured from
+ *              the frame's atom to the HOLO ligand atom                           (int32)
+ *   lddt_num  [frame]     the same summed over s with d_frame measured to atom perms[p][h] of the pose's own ligand, maximum
+ *              over p; -1 when N_g != H_g                                          (int32)
+ * Float sums run in a fixed order and counts are integers: a frame's outputs are bitwise the same alone, in any batch and in any
+ * frame order.  A frame with a non-finite or |x| > 1e4 coordinate gets -1 in every count and NaN in every float.
+ * Limits (DBFR_ERR_ARG beyond them): H_g, N_g <= 256; 14 R_g <= 8192 pocket atoms; S_g <= 512; automorphisms are not limited. */
+#define DBFR_HOLO_MAX_LIG 256
+#define DBFR_HOLO_MAX_POCKET 8192
+#define DBFR_HOLO_MAX_SITE 512
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; per-frame outputs are indexed by frame                 */
+  const int32_t* site_ptr;       /* [G+1] first site residue of every group in the per-residue arrays below                  */
+  const int32_t* site_aatype;    /* [site_ptr[G]] 0..19 (others: no chi angles)                                             */
+  const int32_t* site_row;       /* [site_ptr[G]] pocket row of the residue, or -1: apo14 for every frame                    */
+  const uint8_t* site_matched;   /* [site_ptr[G]]                                                                           */
+  const float*   holo14;         /* [site_ptr[G], 14, 3]                                                                    */
+  const uint8_t* holo_mask;      /* [site_ptr[G], 14]                                                                       */
+  const float*   apo14;          /* [site_ptr[G], 14, 3] read where site_row < 0                                            */
+  const uint8_t* frame_mask;     /* [site_ptr[G], 14]                                                                       */
+  const float*   holo_chi;       /* [site_ptr[G], 4] chi1..chi4 of the holo residue, NaN where undefined                     */
+  const int64_t* site_off;       /* [G] frame k of g writes its per-residue outputs at rows site_off[g] + k S_g              */
+  const int32_t* res_ptr;        /* [G+1]: R_g = res_ptr[g+1] - res_ptr[g]                                                   */
+  const int64_t* pocket_off;     /* [G] frame k of g at rows pocket_off[g] + k R_g of pocket                                 */
+  const float*   pocket;         /* [rows, 14, 3]                                                                           */
+  const int32_t* hlig_ptr;       /* [G+1] holo ligand atoms of every group in hlig                                           */
+  const float*   hlig;           /* [hlig_ptr[G], 3]                                                                        */
+  const int64_t* pair_off;       /* [G] first float of group g in pair_dist (S_g 14 H_g floats)                              */
+  const int32_t* lig_ptr;        /* [G+1]: N_g = lig_ptr[g+1] - lig_ptr[g]                                                   */
+  const int64_t* lig_off;        /* [G] frame k of g at rows lig_off[g] + k N_g of lig                                       */
+  const float*   lig;            /* [rows, 3] the poses' own ligand atoms                                                   */
+  const int32_t* perm_ptr;       /* [G+1] first automorphism of every group (n_perm_g >= 1 where N_g == H_g > 0)              */
+  const int64_t* perm_off;       /* [G] first int of group g in perms                                                       */
+  const int32_t* perms;          /* group by group [n_perm_g, N_g]: holo ligand atom h is compared with pose atom perms[p][h] */
+  int32_t        max_site;       /* host-known maxima over the groups (<= 512, 585, 256)                                    */
+  int32_t        max_res;
+  int32_t        max_lig;        /* over N_g and H_g                                                                        */
+  const void*    host;           /* required: a dbfr_holo_metrics_in whose pointers are HOST copies of the index arrays (the
+                                    coordinate, mask, type and chi arrays are not read): every count, pocket row, offset and
+                                    automorphism entry is validated before the launches (DBFR_ERR_ARG)                       */
+} dbfr_holo_metrics_in;
+
+typedef struct {
+  float radius;                  /* A, (0, 100], default 6.0: holo pairs below it are scored                               */
+} dbfr_holo_metrics_opts;
+
+typedef struct {                 /* device arrays; all but pair_dist may be NULL                                             */
+  float*   pair_dist;            /* [sum_g S_g 14 H_g] written by the first launch, read by the second                       */
+  int32_t* plddt_den;            /* [site_ptr[G]]                                                                           */
+  int32_t* lddt_den;             /* [G]                                                                                     */
+  float*   sc_rmsd;              /* [sum_g F_g S_g]                                                                         */
+  float*   sc_sq_sum;            /* [n_frame]                                                                               */
+  int32_t* sc_n;                 /* [n_frame]                                                                               */
+  float*   chi;                  /* [sum_g F_g S_g, 4]                                                                      */
+  float*   altchi;               /* [sum_g F_g S_g, 2]                                                                      */
+  float*   dchi;                 /* [sum_g F_g S_g, 4]                                                                      */
+  int32_t* plddt_num;            /* [sum_g F_g S_g]                                                                         */
+  int32_t* lddt_num;             /* [n_frame]                                                                               */
+} dbfr_holo_metrics_out;
+
+/* Two launches for the whole batch: the pairs of every group, then every frame.  opts NULL = defaults.                      */
+int dbfr_holo_metrics(const dbfr_holo_metrics_in* in, const dbfr_holo_metrics_opts* opts, const dbfr_holo_metrics_out* out,
+                      void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file
  * files; a file is the frames listed for it, in frame order, with one atom map.  Atom k of a frame is atom_map[map_ptr[m] + k]

@@ -21,13 +21,18 @@
 //     16 x 16 blocks of Z as fp32 into the other LDS buffer, column = segment -- with the cutting of this tile's Z in its shadow, then step B of this
 //     tile: the eight waves take one k-step of 32 each of the 256 (c, k) values of every column, W2' fragments straight from L2 into registers a
 //     whole tile ahead (every wave another k-step: no LDS ring), columns = the up to 32 segments of the workgroup's eight chunks; partial sums over
-//     the k-steps are added across the waves once per output irrep.
+//     the k-steps are added across the waves once per output irrep;
+//   * the tenth slot of a c tile, the SWITCH (k tile 9 = the bias row, wave 0's alone; then the next c tile's Y and its first step A), runs UNDER the
+//     W2' fetch of the next tile, which is requested first.  That needs the switch -- and since then the whole tile loop -- free of scratch: a reload
+//     counts in vmcnt and would wait for the fragments just requested.  So the lo pieces of H of the k tiles 0 and 1 live in the wave's LDS area (w_hl),
+//     lane-derived addresses are computed where they are used (cz_lane_here), and the irrep's first fetch sits inside the loop form that consumes it.
+//     For the k tile 9 the waves 1..7 ask for wave 0's share instead of their own all-zero shares of the packed table (fetchW's `share`).
 // Scaling (exact powers of two): inputs per edge, W1 per matrix or per row (conv2h), h per chunk, y per chunk (bound from max |x| max |sh|), Z by the
 // constant 2^-20 (|Z| <= 32 x 2^15 x 2^15), W2' per output ROW (undone on the accumulator rows at the end: no row-depth limit).
 // Message interface: the sum of a segment lands in the message row of the segment's FIRST edge; the scalar columns of its other rows are not
 // written -- k_reduce_ln[_layer] add a node's flagged rows for these columns (EdgeSet::seg_first, written with the chunk table) and all rows
 // for the vector columns, and divide by the number of edges as before.
-// Design, cost model and what bounds the kernel: docs/kernels/conv_reduce_first.md; what was tried: profiles/TUNING_r5.md.
+// Design, cost model and what bounds the kernel: docs/kernels/conv_reduce_first.md; what was tried: profiles/TUNING_r5.md, TUNING_r6.md, TUNING_r7.md (the switch).
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -58,7 +63,8 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 #define CZ_KPB 1                    // k tiles per barrier
 #define CZ_BUF (CZ_KPB * CZ_TILE)
 #define CZ_ZBYTES (2 * CZ_BUF)      // two buffers: step A of the next tile writes while step B of this one reads
-#define CZ_WAVE_FLOATS (32 * 12 + 32 + 32 + 32 + 32 + 32 + CZ_MAXSEG * 16 + 24 * 64)   // harmonics [32][12] | sa | ua | gather row offsets | segment ids | first slot of segment j | masks [CZ_MAXSEG segments][4 lane groups][4 dwords] | gathered x of the next c tile [8 slots x 3 components][64 lanes]
+#define CZ_NHL 2                    // k tiles whose lo piece of H lives in the wave's LDS area instead of registers: those the c-tile switch reads
+#define CZ_WAVE_FLOATS (32 * 12 + 32 + 32 + 32 + 32 + 32 + CZ_MAXSEG * 16 + 24 * 64 + CZ_NHL * 256)   // harmonics [32][12] | sa | ua | gather row offsets | segment ids | first slot of segment j | masks [CZ_MAXSEG segments][4 lane groups][4 dwords] | gathered x of the next c tile [8 slots x 3 components][64 lanes] | lo pieces of H of the k tiles 0..CZ_NHL-1 [64 lanes][4 dwords]
 #ifndef CZ_PRIO
 #define CZ_PRIO 1
 #endif
@@ -87,6 +93,14 @@ __device__ __forceinline__ float cz_wave_max(float v) {
   return v;
 }
 
+// The lane id, computed HERE: the empty volatile statement keeps hipcc from hoisting it, and every address that follows from it, out of the tile
+// loops -- where such a value is spilled and its reload, counted in vmcnt, waits for every W2' fragment in flight.
+__device__ __forceinline__ int cz_lane_here() {
+  int l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+  asm volatile("" : "+v"(l));
+  return l;
+}
+
 template <int I, int N, typename F>
 __device__ __forceinline__ void cz_static_for(F&& f) {
   if constexpr (I < N) { f(std::integral_constant<int, I>{}); cz_static_for<I + 1, N>(f); }
@@ -108,6 +122,10 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
   int* w_first = w_seg + 32;                                // [32] first slot of segment j
   unsigned* w_mask = reinterpret_cast<unsigned*>(w_first + 32);   // [CZ_MAXSEG][4][4] segment j's mask on the A-operand registers of lane group g
   float* w_xs = reinterpret_cast<float*>(w_mask + CZ_MAXSEG * 16);   // [24][64] the next c tile's gathered x values: row = slot t (+ 8 m: component m of a vector input), one dword per lane
+  // Lo pieces of H of the k tiles 0 and 1, 16 bytes per lane: what the first step A of a c tile (k tile 0) and the step A inside tile 0 (k tile 1) read.
+  // The register allocator spills the lo pieces of the first k tiles to scratch; a scratch reload counts in vmcnt, so it waits for every W2' fragment
+  // in flight, and the switch had to park the stream.  An LDS read counts in lgkmcnt: the fetch of the next tile can go out first.
+  u32x4* w_hl = reinterpret_cast<u32x4*>(w_xs + 24 * 64);   // [CZ_NHL][64]
   int* b_nseg = reinterpret_cast<int*>(lds + CZ_ZBYTES / 4 + NW * CZ_WAVE_FLOATS);   // [NW]
   int* b_col_edge = b_nseg + NW;                            // [48] message row of the column's segment, -1: column unused
   float* b_col_inv = reinterpret_cast<float*>(b_col_edge + 16 * CZ_NCB);   // [32] takes the chunk's factors off
@@ -202,7 +220,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
 
     stamp(2);
     // ---- hidden layer, transposed: D[edge, unit] = sum_f a[edge, f] W1[unit, f]; A = the edge's inputs (cut per edge), B = W1h tiles
-    u32x4 Hh[CZ_NKT][2];                                     // H pieces [k tile][hi, lo]: lane (unit n, group g), eight edges {4g..4g+3, 16+4g..16+4g+3}
+    u32x4 Hh[CZ_NKT][2];                                     // H pieces [k tile][hi, lo]: lane (unit n, group g), eight edges {4g..4g+3, 16+4g..16+4g+3}; the lo pieces of the k tiles < CZ_NHL are in w_hl instead
     int eh = 0;                                              // the factor on h is 2^(15 - ehc + k1) = phi, also what the constant 1 of the bias becomes
     {
       const __amdgpu_buffer_rsrc_t rW1 = __builtin_amdgcn_make_buffer_rsrc((void*)W.W1h, 0, KT * CH_TILE_BYTES, 0x00020000);
@@ -329,7 +347,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
         cz_split2(Hf[m][1][0] * sH, Hf[m][1][1] * sH, h2, l2);
         cz_split2(Hf[m][1][2] * sH, Hf[m][1][3] * sH, h3, l3);
         Hh[m][0] = (u32x4){h0, h1, h2, h3};
-        Hh[m][1] = (u32x4){l0, l1, l2, l3};
+        if (m < CZ_NHL) w_hl[m * 64 + lane] = (u32x4){l0, l1, l2, l3};   // (read back by this wave only)
+        else Hh[m][1] = (u32x4){l0, l1, l2, l3};
       }
     }
     const int ephi = 15 - eh + W.k1;                         // log2 of the factor on h
@@ -396,12 +415,15 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       int gq = W.ct0[io] * CZ_NKT;                           // running (c tile, k tile) index into W2z; CZ_NKT is even: the Z buffer of tile gq is kt & 1
       const int gq_last = (W.ct0[io] + W.nct[io]) * CZ_NKT - 1;
       u32x4 Wf[2][3][2];                                     // W2' fragments of my k-step: [tile parity][w tile][hi, lo], fetched one whole tile ahead
-      auto fetchW = [&](auto par_c, int q) {
+      auto fetchW = [&](auto par_c, int q, int share) {
         constexpr int par = decltype(par_c)::value;
         if ((ABL & 1) && q != W.ct0[io] * CZ_NKT) return;
         // (no branch around these loads, not even for the k tile 9 whose fragments only wave 0 uses: behind a conditional fetch hipcc's wait-count
-        // pass assumes the loads were NOT issued and makes step B wait for vmcnt(0), i.e. for the fragments requested a moment ago)
-        const char* p = wbase + ((size_t)q * 8 + wave) * CZ_TILE_BYTES;
+        // pass assumes the loads were NOT issued and makes step B wait for vmcnt(0), i.e. for the fragments requested a moment ago.  What the other
+        // seven waves are spared is the ADDRESS: `share` is the k-step whose 6 KB the wave asks for -- its own for the k tiles 0..8, wave 0's for the k
+        // tile 9, whose other seven shares are the zero padding of the packed table: the lines are on their way into this CU's L1 for wave 0 anyway,
+        // and 42 of the 48 KB of that tile never leave L2)
+        const char* p = wbase + ((size_t)q * 8 + share) * CZ_TILE_BYTES;
 #pragma unroll
         for (int wt = 0; wt < 3; ++wt)
 #pragma unroll
@@ -444,6 +466,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       // every load issued before the `younger` most recent ones has landed -- the stage's gathers among them
       auto wait_stage = [&](auto younger_c) {
         constexpr int y = decltype(younger_c)::value;
+        static_assert(y == 0 || y == 6, "wait_stage: a fetch is six loads");
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (y == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -451,7 +474,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       };
       auto finish_Y = [&](int ct) {
         if (nseg_u == 0 || (ABL & 16)) return;
-        const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), n = lane & 15, g = lane >> 4;
+        const int lane = cz_lane_here(), n = lane & 15, g = lane >> 4;
         const unsigned cd_n = b_cdesc[(W.ct0[io] + ct) * 16 + n];
         const bool vec = (__builtin_amdgcn_readfirstlane(cd_n) >> 12) & 1u;
         const int so = (cd_n >> 16) & 15;
@@ -484,13 +507,21 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
 #define YM(j, p) __builtin_bit_cast(f16x8, Ym[j][p])
 #define MF(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 #define SL __builtin_amdgcn_sched_barrier(0)
+      // lo piece of H of k tile kt: from the wave's LDS area for the first CZ_NHL k tiles (lane id from v_mbcnt, as in finish_Y: nothing kept across the tiles)
+      auto load_hl = [&](auto kt_c) -> u32x4 {
+        constexpr int kt = decltype(kt_c)::value;
+        if constexpr (kt < CZ_NHL) {
+          return w_hl[kt * 64 + cz_lane_here()];
+        } else
+          return Hh[kt][1];
+      };
       // step A of one (c, k) tile, on its own (the first tile of an irrep, the first tile of a c tile): Z[c, k] of my four segment slots -- independent
       // three-product chains side by side -- as fp32 to LDS (column = segment)
       auto stepA = [&](auto kt_c, auto buf_c) {
         constexpr int kt = decltype(kt_c)::value, boff = decltype(buf_c)::value * CZ_BUF;
         if (ABL & 4) return;
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        const f16x8 hh = __builtin_bit_cast(f16x8, Hh[kt][0]), hl = __builtin_bit_cast(f16x8, Hh[kt][1]);
+        const f16x8 hh = __builtin_bit_cast(f16x8, Hh[kt][0]), hl = __builtin_bit_cast(f16x8, load_hl(kt_c));
         f32x4 z[CZ_MAXSEG];
 #pragma unroll
         for (int j = 0; j < CZ_MAXSEG; ++j) z[j] = MF(YM(j, 0), hl, zero);
@@ -518,12 +549,12 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
         constexpr int kt = decltype(kt_c)::value, NCBV = decltype(ncb_c)::value;
         constexpr int boffA = ((kt + 1) & 1) * CZ_BUF;
         // (the next tile's fragments are requested behind step A's first CZ_FETCH_AT matrix instructions, not at the top of the tile: same-box A/B, TUNING_r5.md)
-        if constexpr (CZ_FETCH_AT == 0) fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last));
+        if constexpr (CZ_FETCH_AT == 0) fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last), kt + 1 == KT ? 0 : wave);
         const char* zr = zb + (kt & 1) * CZ_BUF + wave * CZ_VSTRIDE + g * 512 + n * 16;
         f32x4 zf0[2], zf1[2];
         zf0[0] = *reinterpret_cast<const f32x4*>(zr); zf0[1] = *reinterpret_cast<const f32x4*>(zr + 256);
         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        const f16x8 hh = __builtin_bit_cast(f16x8, Hh[kt + 1][0]), hl = __builtin_bit_cast(f16x8, Hh[kt + 1][1]);
+        const f16x8 hh = __builtin_bit_cast(f16x8, Hh[kt + 1][0]), hl = __builtin_bit_cast(f16x8, load_hl(std::integral_constant<int, kt + 1>{}));
         u32x4 p0h, p0l, p1h, p1l;
         f32x4 z0, z1, z2, z3;
         if constexpr ((ABL & 4) != 0) {
@@ -536,20 +567,20 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
         z1 = MF(YM(1, 0), hl, zero); SL;
         z2 = MF(YM(2, 0), hl, zero); SL;
         z3 = MF(YM(3, 0), hl, zero); SL;
-        if constexpr (CZ_FETCH_AT == 4) { fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last)); SL; }
+        if constexpr (CZ_FETCH_AT == 4) { fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last), kt + 1 == KT ? 0 : wave); SL; }
         z0 = MF(YM(0, 1), hh, z0); cut(zf0, p0h, p0l, K0{}); SL;
         z1 = MF(YM(1, 1), hh, z1); SL;
         z2 = MF(YM(2, 1), hh, z2); cut(zf0, p0h, p0l, K1{}); SL;
         z3 = MF(YM(3, 1), hh, z3); SL;
-        if constexpr (CZ_FETCH_AT == 8) { fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last)); SL; }
+        if constexpr (CZ_FETCH_AT == 8) { fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last), kt + 1 == KT ? 0 : wave); SL; }
         CZ_SETPRIO(2);
         z0 = MF(YM(0, 0), hh, z0); cut(zf0, p0h, p0l, K2{}); SL;
         z1 = MF(YM(1, 0), hh, z1); SL;
         z2 = MF(YM(2, 0), hh, z2); cut(zf0, p0h, p0l, K3{}); SL;
         z3 = MF(YM(3, 0), hh, z3); SL;
-        if constexpr (CZ_FETCH_AT == 12) { fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last)); SL; }
+        if constexpr (CZ_FETCH_AT == 12) { fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last), kt + 1 == KT ? 0 : wave); SL; }
         }
-        if constexpr ((ABL & 4) != 0 && CZ_FETCH_AT != 0) fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last));
+        if constexpr ((ABL & 4) != 0 && CZ_FETCH_AT != 0) fetchW(std::integral_constant<int, (kt + 1) & 1>{}, min(gq + 1, gq_last), kt + 1 == KT ? 0 : wave);
 #define WFR(wt, pc) __builtin_bit_cast(f16x8, Wf[kt & 1][wt][pc])
         if constexpr ((ABL & 8) != 0) {
           if constexpr (!(ABL & 4)) { *reinterpret_cast<f32x4*>(za[0] + boffA) = z0; *reinterpret_cast<f32x4*>(za[1] + boffA) = z1; *reinterpret_cast<f32x4*>(za[2] + boffA) = z2; *reinterpret_cast<f32x4*>(za[3] + boffA) = z3; }
@@ -585,12 +616,14 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       // the k tile 9 (the bias row: k-step 0 only, wave 0's) and, under it, the next c tile's Y and its first step A
       auto tile9 = [&](int ct) {
         constexpr int kt = KT;
-        // Order: wave 0's step B, the next c tile's Y and first step A, and only then the W2' fetch of the next tile.  Both parts reload a few spilled
-        // loop invariants, and a reload waits for vmcnt(0): behind the fetch that is a whole L2 round trip (7 800 cycles for this tile when the
-        // fetch came first).
-        wait_stage(K0{});
+        // Order: the W2' fetch of the next tile FIRST (the fragment registers of parity 0 are free since tile 8's step B), then wave 0's step B, the next
+        // c tile's Y and its first step A under it.  Nothing in here may reload from scratch -- a reload waits for vmcnt(0), behind the fetch a whole
+        // L2 round trip (7 800 cycles for this tile when round 5 tried this order) -- which is why the lo pieces of H that the switch reads live in LDS
+        // (w_hl).  The stage's gathers and this tile's fragments are older than the fetch's six loads: the counted wait.
+        fetchW(K0{}, min(gq + 1, gq_last), wave);
+        wait_stage(std::integral_constant<int, 6>{});
         if (wave == 0 && !(ABL & 8)) {
-          const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), n = lane & 15, g = lane >> 4;
+          const int lane = cz_lane_here(), n = lane & 15, g = lane >> 4;
           const char* zr = zb + (kt & 1) * CZ_BUF + g * 512 + n * 16;
 #pragma unroll
           for (int cb = 0; cb < CZ_NCB; ++cb)
@@ -609,20 +642,20 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
             }
         }
         if (ct + 1 < W.nct[io]) { finish_Y(ct + 1); stepA(K0{}, K0{}); }
-        __builtin_amdgcn_sched_barrier(0);
-        fetchW(K0{}, min(gq + 1, gq_last));
       };
 #undef WFR
       // While step B reads tile i from buffer i & 1, step A of tile i + 1 is written into the other buffer; one barrier per tile.
       prefetch_x(0);
       wait_stage(K0{});
-      fetchW(K0{}, gq);
-      finish_Y(0);
-      stepA(K0{}, K0{});
-      __syncthreads();
       // (the column-block count is decided once per unit, OUTSIDE the tile loops: as a branch inside a tile hipcc hoists the instructions the two
       // forms share -- the Z reads and the first half of the cutting, with their s_waitcnt -- in front of step A's matrix instructions)
+      // (the first fetch and the first step A of the irrep belong to the form that runs: requested in front of the branch, the fragments stay live -- in
+      // scratch -- through the other form's loop, and their reload lands in the c-tile switch)
       auto run_tiles = [&](auto ncb_c) {
+        fetchW(K0{}, gq, wave);
+        finish_Y(0);
+        stepA(K0{}, K0{});
+        __syncthreads();
         for (int ct = 0; ct < W.nct[io]; ++ct) {
           cz_static_for<0, CZ_NKT>([&](auto kt_c) {
             constexpr int kt = decltype(kt_c)::value;

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import lib as L
+from . import frames as fb, lib as L
 from .lib import DbfrError, HoloMetricsIn, HoloMetricsOpts, HoloMetricsOut, HoloSiteIn
 from .tables import residue_tables
 
@@ -187,10 +187,6 @@ class PairRecord:
         return float(np.sqrt((d * d).mean())) if d.size else float("nan")
 
 
-def _ptr(counts, dtype=np.int32):
-    return np.concatenate([[0], np.cumsum(counts)]).astype(dtype)
-
-
 def select_sites(structures, cutoff=6.0, device="cuda:0"):
     """``dbfr_holo_site`` over a list of (atom positions [A, 3], residue of every atom [A], n_res, ligand atoms [L, 3]): a list of
     bool [n_res] arrays, True where any listed atom of the residue lies within ``cutoff`` (<=) of any ligand atom."""
@@ -212,16 +208,16 @@ def select_sites(structures, cutoff=6.0, device="cuda:0"):
     if any(a.shape[0] != r.shape[0] for a, r in zip(A, res)):
         raise DbfrError("one residue index per listed atom")
     t = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x, dt), device=dev)
-    d = dict(atom_ptr=t(_ptr([a.shape[0] for a in A]), np.int32), atom_pos=t(np.concatenate(A + [np.zeros((1, 3), np.float32)]), np.float32),
-             atom_res=t(np.concatenate(res + [np.zeros(1, np.int32)]), np.int32), lig_ptr=t(_ptr([x.shape[0] for x in lig]), np.int32),
-             lig_pos=t(np.concatenate(lig + [np.zeros((1, 3), np.float32)]), np.float32), res_ptr=t(_ptr(n_res), np.int32))
+    d = dict(atom_ptr=t(fb.ptr([a.shape[0] for a in A]), np.int32), atom_pos=t(np.concatenate(A + [np.zeros((1, 3), np.float32)]), np.float32),
+             atom_res=t(np.concatenate(res + [np.zeros(1, np.int32)]), np.int32), lig_ptr=t(fb.ptr([x.shape[0] for x in lig]), np.int32),
+             lig_pos=t(np.concatenate(lig + [np.zeros((1, 3), np.float32)]), np.float32), res_ptr=t(fb.ptr(n_res), np.int32))
     site = torch.zeros(sum(n_res) + 1, dtype=torch.uint8, device=dev)
     cin = HoloSiteIn(len(structures), *[d[k].data_ptr() for k in ("atom_ptr", "atom_pos", "atom_res", "lig_ptr", "lig_pos", "res_ptr")],
                      sum(n_res), max(a.shape[0] for a in A), float(cutoff))
     with torch.cuda.device(dev):
         L.check(lib.dbfr_holo_site(C.byref(cin), C.c_void_p(site.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     flags = site.cpu().numpy() != 0
-    off = _ptr(n_res, np.int64)
+    off = fb.ptr(n_res, np.int64)
     return [flags[off[i]:off[i + 1]] for i in range(len(structures))]
 
 
@@ -324,10 +320,7 @@ def pair(holo, apo, holo_lig, cutoff=6.0, residues=None, extra=None, superpose=N
 
 # ------------------------------------------------------------------------------------------------ device call
 def _opts(**opts):
-    bad = set(opts) - set(DEFAULTS)
-    if bad:
-        raise DbfrError(f"unknown holo-metrics options {sorted(bad)} (known: {sorted(DEFAULTS)})")
-    o = {**DEFAULTS, **opts}
+    o = fb.check_opts(opts, DEFAULTS, "holo-metrics")
     if not 0.0 < float(o["radius"]) <= 100.0:
         raise DbfrError("radius must lie in (0, 100] A and must not be NaN")
     return HoloMetricsOpts(float(o["radius"]))
@@ -339,17 +332,13 @@ def evaluate_launcher(pairs, groups, **opts):
     o = _opts(**opts)
     if not groups or len(pairs) != len(groups):
         raise DbfrError(f"{len(pairs)} pair records for {len(groups)} groups (one each, at least one)")
-    p0 = groups[0].get("pocket")
-    dev = p0.device if torch.is_tensor(p0) else torch.device("cpu")
-    if dev.type != "cuda":
-        raise DbfrError("the holo metrics are computed on the GPU only (no CPU path): the frames are on " + str(dev))
+    dev = fb.device_of(groups[0].get("pocket"), "the holo metrics are computed on the GPU only (no CPU path): the frames are on ")
     G = len(groups)
     F, S, R, H, N, P = (np.zeros(G, np.int64) for _ in range(6))
     pocket, lig, perms = [], [], []
     for g, (pr, gr) in enumerate(zip(pairs, groups)):
-        p, x = gr.get("pocket"), gr.get("lig")
-        if not torch.is_tensor(p) or p.device != dev or (x is not None and (not torch.is_tensor(x) or x.device != dev)):
-            raise DbfrError(f"group {g}: pocket frames and poses must be device tensors on {dev} (no CPU path)")
+        p = gr.get("pocket")
+        fb.on_device(g, dev, "pocket frames and poses must be device tensors", p, gr.get("lig"))
         if p.dim() != 4 or tuple(p.shape[2:]) != (14, 3):
             raise DbfrError(f"group {g}: pocket frames must be [F, R, 14, 3]")
         F[g], R[g], S[g], H[g] = p.shape[0], p.shape[1], pr.n_site, pr.holo_lig.shape[0]
@@ -357,11 +346,7 @@ def evaluate_launcher(pairs, groups, **opts):
             raise DbfrError(f"group {g}: {14 * R[g]} pocket atoms, at most {MAX_POCKET}")
         if S[g] > MAX_SITE:
             raise DbfrError(f"group {g}: {S[g]} site residues, at most {MAX_SITE}")
-        if x is None:
-            x = torch.zeros(int(F[g]), 0, 3, device=dev)
-        if x.dim() != 3 or x.shape[0] != F[g] or x.shape[2] != 3:
-            raise DbfrError(f"group {g}: ligand poses must be [F, N, 3] with the frames of the pocket")
-        N[g] = x.shape[1]
+        x, _, N[g] = fb.pose_rows(gr.get("lig"), g, dev, "ligand poses must be [F, N, 3] with the frames of the pocket", F[g])
         if N[g] > MAX_LIG or H[g] > MAX_LIG:
             raise DbfrError(f"group {g}: {max(N[g], H[g])} ligand atoms, at most {MAX_LIG}")
         if (pr.site_row >= R[g]).any():
@@ -374,21 +359,22 @@ def evaluate_launcher(pairs, groups, **opts):
             raise DbfrError(f"group {g}: an automorphism entry is no ligand atom")
         P[g] = pm.shape[0]
         pocket.append(p.detach().reshape(-1).to(torch.float32))
-        lig.append(x.detach().reshape(-1).to(torch.float32))
+        lig.append(x)
         perms.append(pm.reshape(-1))
-    cat = lambda xs, dt, w: np.concatenate([np.asarray(x, dt).reshape(-1) for x in xs] + [np.zeros(w, dt)])
-    host = dict(frame_ptr=_ptr(F), site_ptr=_ptr(S), site_aatype=cat([p.aatype for p in pairs], np.int32, 1),
+    lig_pos, lig_off = fb.pose_block(lig, F, N, dev, pad=3)
+    cat = fb.cat
+    host = dict(frame_ptr=fb.ptr(F), site_ptr=fb.ptr(S), site_aatype=cat([p.aatype for p in pairs], np.int32, 1),
                 site_row=cat([p.site_row for p in pairs], np.int32, 1), site_matched=cat([p.matched for p in pairs], np.uint8, 1),
                 holo14=cat([p.holo14 for p in pairs], np.float32, 42), holo_mask=cat([p.holo_mask for p in pairs], np.uint8, 14),
                 apo14=cat([p.apo14 for p in pairs], np.float32, 42), frame_mask=cat([p.apo_mask for p in pairs], np.uint8, 14),
-                holo_chi=cat([p.holo_chi[:, :4] for p in pairs], np.float32, 4), site_off=_ptr(F * S, np.int64)[:-1].copy(),
-                res_ptr=_ptr(R), pocket_off=_ptr(F * R, np.int64)[:-1].copy(), hlig_ptr=_ptr(H),
-                hlig=cat([p.holo_lig for p in pairs], np.float32, 3), pair_off=_ptr(S * 14 * H, np.int64)[:-1].copy(), lig_ptr=_ptr(N),
-                lig_off=_ptr(F * N, np.int64)[:-1].copy(), perm_ptr=_ptr(P), perm_off=_ptr(P * N, np.int64)[:-1].copy(),
+                holo_chi=cat([p.holo_chi[:, :4] for p in pairs], np.float32, 4), site_off=fb.ptr(F * S, np.int64)[:-1].copy(),
+                res_ptr=fb.ptr(R), pocket_off=fb.ptr(F * R, np.int64)[:-1].copy(), hlig_ptr=fb.ptr(H),
+                hlig=cat([p.holo_lig for p in pairs], np.float32, 3), pair_off=fb.ptr(S * 14 * H, np.int64)[:-1].copy(), lig_ptr=fb.ptr(N),
+                lig_off=lig_off, perm_ptr=fb.ptr(P), perm_off=fb.ptr(P * N, np.int64)[:-1].copy(),
                 perms=cat(perms, np.int32, 1))
     t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
     t["pocket"] = torch.cat(pocket + [torch.zeros(42, device=dev)])
-    t["lig"] = torch.cat(lig + [torch.zeros(3, device=dev)])
+    t["lig"] = lig_pos
     n_frame, n_row, n_site, n_pair = int(F.sum()), int((F * S).sum()), int(S.sum()), int((S * 14 * H).sum())
     z = lambda n, dt: torch.zeros(n + 1, dtype=dt, device=dev)
     out = dict(pair_dist=z(n_pair, torch.float32), plddt_den=z(n_site, torch.int32), lddt_den=z(G, torch.int32), sc_rmsd=z(n_row, torch.float32),
@@ -398,15 +384,10 @@ def evaluate_launcher(pairs, groups, **opts):
     order = [f for f, _ in HoloMetricsIn._fields_][2:25]
     mx = lambda a: int(max(a)) if len(a) else 0
     tail = (mx(S), mx(R), max(mx(N), mx(H)))
-    hin = HoloMetricsIn(G, n_frame, *[host[k].ctypes.data if k in host else None for k in order], *tail, None)
-    cin = HoloMetricsIn(G, n_frame, *[t[k].data_ptr() for k in order], *tail, C.addressof(hin))
     cout = HoloMetricsOut(*[out[k].data_ptr() for k, _ in HoloMetricsOut._fields_])
-
-    def launch(_staged=(t, host, hin)):   # (the staged tensors and the host copies live as long as the closure)
-        with torch.cuda.device(dev):
-            L.check(lib.dbfr_holo_metrics(C.byref(cin), C.byref(o), C.byref(cout), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-
-    roff, soff, poff, fptr = _ptr(F * S, np.int64), _ptr(S, np.int64), _ptr(S * 14 * H, np.int64), _ptr(F, np.int64)
+    # (once=False: dbfr_holo_metrics takes its site count from the host copies at every launch)
+    launch = fb.launcher(lib.dbfr_holo_metrics, HoloMetricsIn, (G, n_frame), order, tail, t, dev, o, cout, host, once=False)
+    roff, soff, poff, fptr = fb.ptr(F * S, np.int64), fb.ptr(S, np.int64), fb.ptr(S * 14 * H, np.int64), fb.ptr(F, np.int64)
     per = lambda k, w: [out[k][w * roff[g]:w * roff[g + 1]].view(*((int(F[g]), int(S[g])) + ((w,) if w > 1 else ()))) for g in range(G)]
     res = dict(sc_rmsd=per("sc_rmsd", 1), chi=per("chi", 4), altchi=per("altchi", 2), dchi=per("dchi", 4), plddt_num=per("plddt_num", 1),
                plddt_den=[out["plddt_den"][soff[g]:soff[g + 1]] for g in range(G)], lddt_den=out["lddt_den"][:G],

@@ -12,6 +12,7 @@
 
 #include "../../include/dbfr.h"
 #include "common.h"
+#include "frames.h"
 
 #define RT_TABLE __device__ const
 namespace ah_tables {
@@ -19,8 +20,8 @@ namespace ah_tables {
 }
 #undef RT_TABLE
 
-#define AH_THREADS 256
-#define AH_WAVES (AH_THREADS / 64)
+#define AH_THREADS FR_THREADS
+#define AH_WAVES FR_WAVES
 #define AH_PERM_TILE 256           // automorphisms whose numerators sit in LDS at a time
 #define AH_MAX_RES (DBFR_HOLO_MAX_POCKET / 14)
 #define AH_VAL 19
@@ -32,24 +33,9 @@ struct AhArgs {
   float radius;
 };
 
-__device__ __forceinline__ int ah_group(const int32_t* ptr, int n, int x) {      // the last group whose first entry is <= x
-  int g = 0, hi = n;
-  while (hi - g > 1) {
-    const int mid = (g + hi) >> 1;
-    if (ptr[mid] <= x) g = mid;
-    else hi = mid;
-  }
-  return g;
-}
-
 __device__ __forceinline__ float ah_dist(float ax, float ay, float az, float bx, float by, float bz) {
   const float dx = ax - bx, dy = ay - by, dz = az - bz;
   return sqrtf(dx * dx + dy * dy + dz * dz);
-}
-
-__device__ __forceinline__ int ah_wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // ------------------------------------------------------------------------------------------------ the pairs of a group
@@ -57,7 +43,7 @@ __device__ __forceinline__ int ah_wave_sum(int v) {
 __global__ __launch_bounds__(64) void k_holo_pairs(AhArgs a) {
   const dbfr_holo_metrics_in& in = a.in;
   const int sf = blockIdx.x, lane = threadIdx.x;
-  const int g = ah_group(in.site_ptr, in.n_group, sf);
+  const int g = frame_group(in.site_ptr, in.n_group, sf);
   const int s = sf - in.site_ptr[g], S = in.site_ptr[g + 1] - in.site_ptr[g];
   const int h0 = in.hlig_ptr[g], H = in.hlig_ptr[g + 1] - h0;
   int cnt = 0;
@@ -75,7 +61,7 @@ __global__ __launch_bounds__(64) void k_holo_pairs(AhArgs a) {
       cnt += scored;
     }
   }
-  cnt = ah_wave_sum(cnt);
+  cnt = wave_sum(cnt);
   if (lane == 0) {
     if (a.out.plddt_den) a.out.plddt_den[sf] = cnt;
     if (a.out.lddt_den && cnt) atomicAdd(&a.out.lddt_den[g], cnt);        // an integer sum: the order does not matter
@@ -112,7 +98,7 @@ __global__ __launch_bounds__(AH_THREADS) void k_holo_frames(AhArgs a) {
   const dbfr_holo_metrics_in& in = a.in;
   const dbfr_holo_metrics_out& out = a.out;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int g = ah_group(in.frame_ptr, in.n_group, f);
+  const int g = frame_group(in.frame_ptr, in.n_group, f);
   const int k = f - in.frame_ptr[g];
   const int s0 = in.site_ptr[g], S = in.site_ptr[g + 1] - s0;
   const int R = in.res_ptr[g + 1] - in.res_ptr[g];
@@ -131,20 +117,20 @@ __global__ __launch_bounds__(AH_THREADS) void k_holo_frames(AhArgs a) {
     const float* src = in.pocket + 42 * (in.pocket_off[g] + (long long)k * R);
     for (int i = tid; i < 42 * R; i += AH_THREADS) {
       const float v = src[i];
-      bad_x |= !(fabsf(v) <= 1e4f);
+      bad_x |= !coord_ok(v);
       pk[i] = v;
     }
     for (int i = tid; i < 3 * H; i += AH_THREADS) hl[i] = in.hlig[3 * (size_t)h0 + i];
     const float* lsrc = in.lig + 3 * (in.lig_off[g] + (long long)k * N);
     for (int i = tid; i < 3 * N; i += AH_THREADS) {
       const float v = lsrc[i];
-      bad_x |= !(fabsf(v) <= 1e4f);
+      bad_x |= !coord_ok(v);
       pl[i] = v;
     }
     for (int i = tid; i < 42 * S; i += AH_THREADS) {                  // the static atoms that stand in for a pocket row
       const int s = i / 42;
       if (in.site_matched[s0 + s] && in.site_row[s0 + s] < 0 && in.frame_mask[14 * (size_t)(s0 + s) + (i - 42 * s) / 3])
-        bad_x |= !(fabsf(in.apo14[42 * (size_t)s0 + i]) <= 1e4f);
+        bad_x |= !coord_ok(in.apo14[42 * (size_t)s0 + i]);
     }
     for (int s = tid; s < S; s += AH_THREADS) {
       sq[s] = 0.f;
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(AH_THREADS) void k_holo_frames(AhArgs a) {
               cnt += (df < 0.5f) + (df < 1.f) + (df < 2.f) + (df < 4.f);
             }
           }
-        cnt = ah_wave_sum(cnt);
+        cnt = wave_sum(cnt);
         if (lane == 0 && out.plddt_num) out.plddt_num[orow + s] = cnt;
       }
       // the same against the pose's own ligand, one numerator per automorphism
@@ -265,7 +251,7 @@ __global__ __launch_bounds__(AH_THREADS) void k_holo_frames(AhArgs a) {
               cnt += (df < 0.5f) + (df < 1.f) + (df < 2.f) + (df < 4.f);
             }
           }
-          cnt = ah_wave_sum(cnt);
+          cnt = wave_sum(cnt);
           if (lane == 0 && cnt) atomicAdd(&permacc[p], cnt);            // an integer sum in LDS
         }
     }
@@ -324,11 +310,6 @@ __global__ __launch_bounds__(AH_THREADS) void k_holo_site(dbfr_holo_site_in in, 
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int ah_err(const char* fn, const std::string& s) {
-  dbfr_set_error(std::string(fn) + ": " + s);
-  return DBFR_ERR_ARG;
-}
-
 // the longest common subsequence of a and b with the traceback of include/dbfr.h; the table in uint16 (a score is <= 8192)
 static int ah_align_one(const int32_t* a, int na, const int32_t* b, int nb, int32_t* a_to_b) {
   for (int i = 0; i < na; ++i) a_to_b[i] = -1;
@@ -364,15 +345,15 @@ static int ah_align_one(const int32_t* a, int na, const int32_t* b, int nb, int3
 extern "C" int dbfr_seq_align(int32_t n_pair, const int32_t* a_ptr, const int32_t* a, const int32_t* b_ptr, const int32_t* b,
                               int32_t* a_to_b, int32_t* score, int32_t n_threads) {
   const char* fn = "dbfr_seq_align";
-  if (n_pair < 0) return ah_err(fn, "negative n_pair");
+  if (n_pair < 0) return arg_err(fn, "negative n_pair");
   if (n_pair == 0) return DBFR_OK;
-  if (!a_ptr || !b_ptr || !a_to_b) return ah_err(fn, "a_ptr / b_ptr / a_to_b missing");
+  if (!a_ptr || !b_ptr || !a_to_b) return arg_err(fn, "a_ptr / b_ptr / a_to_b missing");
   for (int p = 0; p < n_pair; ++p) {
     const long long na = (long long)a_ptr[p + 1] - a_ptr[p], nb = (long long)b_ptr[p + 1] - b_ptr[p];
-    if (na < 0 || nb < 0) return ah_err(fn, "pair " + std::to_string(p) + ": a negative length");
+    if (na < 0 || nb < 0) return arg_err(fn, "pair " + std::to_string(p) + ": a negative length");
     if (na * nb > DBFR_ALIGN_MAX_CELLS)
-      return ah_err(fn, "pair " + std::to_string(p) + ": " + std::to_string(na) + " x " + std::to_string(nb) + " cells, at most 2^26");
-    if ((na && !a) || (nb && !b)) return ah_err(fn, "a / b missing");
+      return arg_err(fn, "pair " + std::to_string(p) + ": " + std::to_string(na) + " x " + std::to_string(nb) + " cells, at most 2^26");
+    if ((na && !a) || (nb && !b)) return arg_err(fn, "a / b missing");
   }
   int nt = n_threads > 0 ? n_threads : (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
   nt = std::min(nt, (int)n_pair);
@@ -395,15 +376,15 @@ extern "C" int dbfr_seq_align(int32_t n_pair, const int32_t* a_ptr, const int32_
 
 extern "C" int dbfr_holo_site(const dbfr_holo_site_in* in, uint8_t* site, void* hip_stream) {
   const char* fn = "dbfr_holo_site";
-  if (!in || !site) return ah_err(fn, "null argument");
-  if (in->n_pair < 0 || in->max_atoms < 0) return ah_err(fn, "negative n_pair / max_atoms");
-  if (!(in->cutoff > 0.f && in->cutoff <= 100.f)) return ah_err(fn, "cutoff must lie in (0, 100] A and must not be NaN");
+  if (!in || !site) return arg_err(fn, "null argument");
+  if (in->n_pair < 0 || in->max_atoms < 0) return arg_err(fn, "negative n_pair / max_atoms");
+  if (!(in->cutoff > 0.f && in->cutoff <= 100.f)) return arg_err(fn, "cutoff must lie in (0, 100] A and must not be NaN");
   if (in->n_pair == 0) return DBFR_OK;
-  if (in->n_pair > 65535) return ah_err(fn, "more than 65535 pairs in one launch");
+  if (in->n_pair > 65535) return arg_err(fn, "more than 65535 pairs in one launch");
   if (!in->atom_ptr || !in->atom_pos || !in->atom_res || !in->lig_ptr || !in->lig_pos || !in->res_ptr)
-    return ah_err(fn, "atom_ptr / atom_pos / atom_res / lig_ptr / lig_pos / res_ptr missing");
+    return arg_err(fn, "atom_ptr / atom_pos / atom_res / lig_ptr / lig_pos / res_ptr missing");
   const int32_t n_res = in->n_res;
-  if (n_res < 0) return ah_err(fn, "negative n_res");
+  if (n_res < 0) return arg_err(fn, "negative n_res");
   if (n_res == 0 || in->max_atoms == 0) return DBFR_OK;
   HIPCHECK(hipMemsetAsync(site, 0, (size_t)n_res, (hipStream_t)hip_stream));
   const unsigned bx = (unsigned)((in->max_atoms + AH_THREADS - 1) / AH_THREADS);
@@ -412,43 +393,36 @@ extern "C" int dbfr_holo_site(const dbfr_holo_site_in* in, uint8_t* site, void* 
   return DBFR_OK;
 }
 
-static int ah_limit_err(const char* what, long long got, int lim) {
-  return ah_err("dbfr_holo_metrics", std::string(what) + " " + std::to_string(got) + " outside [0, " + std::to_string(lim) +
-                                         "]: groups beyond it are not supported");
-}
-
 // the host copies of the index arrays, when the caller has them
 static int ah_validate(const dbfr_holo_metrics_in& d, const dbfr_holo_metrics_in& h) {
   const char* fn = "dbfr_holo_metrics";
   if (!h.frame_ptr || !h.site_ptr || !h.site_row || !h.site_off || !h.res_ptr || !h.pocket_off || !h.hlig_ptr || !h.pair_off || !h.lig_ptr ||
       !h.lig_off || !h.perm_ptr || !h.perm_off || (h.perm_ptr[d.n_group] > 0 && !h.perms))
-    return ah_err(fn, "host: a host copy of an index array is missing");
+    return arg_err(fn, "host: a host copy of an index array is missing");
   const int G = d.n_group;
-  if (h.frame_ptr[0] != 0 || h.frame_ptr[G] != d.n_frame) return ah_err(fn, "frame_ptr does not run from 0 to n_frame");
+  if (const int rc = frame_ptr_err(fn, h.frame_ptr, G, d.n_frame)) return rc;
   long long site_rows = 0, pocket_rows = 0, pair_floats = 0, lig_rows = 0, perm_ints = 0;
   for (int g = 0; g < G; ++g) {
     const std::string where = "group " + std::to_string(g) + ": ";
     const long long F = (long long)h.frame_ptr[g + 1] - h.frame_ptr[g], S = (long long)h.site_ptr[g + 1] - h.site_ptr[g],
                     R = (long long)h.res_ptr[g + 1] - h.res_ptr[g], H = (long long)h.hlig_ptr[g + 1] - h.hlig_ptr[g],
                     N = (long long)h.lig_ptr[g + 1] - h.lig_ptr[g], P = (long long)h.perm_ptr[g + 1] - h.perm_ptr[g];
-    if (F < 0 || S < 0 || R < 0 || H < 0 || N < 0 || P < 0) return ah_err(fn, where + "a negative count");
-    if (S > d.max_site) return ah_err(fn, where + std::to_string(S) + " site residues, max_site says " + std::to_string(d.max_site));
-    if (R > d.max_res) return ah_err(fn, where + std::to_string(R) + " pocket rows, max_res says " + std::to_string(d.max_res));
-    if (H > d.max_lig || N > d.max_lig)
-      return ah_err(fn, where + std::to_string(std::max(H, N)) + " ligand atoms, max_lig says " + std::to_string(d.max_lig));
+    if (const int rc = group_counts_err(fn, where, {{F}, {S, "site residues", "max_site", d.max_site}, {R, "pocket rows", "max_res", d.max_res},
+                                                    {H}, {N}, {P}, {std::max(H, N), "ligand atoms", "max_lig", d.max_lig}}))
+      return rc;
     // the arrays are laid out group by group without overlap
     if (h.site_off[g] != site_rows || h.pocket_off[g] != pocket_rows || h.pair_off[g] != pair_floats || h.lig_off[g] != lig_rows ||
         h.perm_off[g] != perm_ints)
-      return ah_err(fn, where + "site_off / pocket_off / pair_off / lig_off / perm_off is not the running sum of the groups before it");
+      return arg_err(fn, where + "site_off / pocket_off / pair_off / lig_off / perm_off is not the running sum of the groups before it");
     site_rows += F * S; pocket_rows += F * R; pair_floats += S * 14 * H; lig_rows += F * N; perm_ints += P * N;
     for (int s = 0; s < S; ++s) {
       const int row = h.site_row[h.site_ptr[g] + s];
-      if (row < -1 || row >= R) return ah_err(fn, where + "site_row " + std::to_string(row) + " of site residue " + std::to_string(s) + " is no pocket row");
+      if (row < -1 || row >= R) return arg_err(fn, where + "site_row " + std::to_string(row) + " of site residue " + std::to_string(s) + " is no pocket row");
     }
-    if (N == H && H > 0 && P < 1) return ah_err(fn, where + "no automorphism (the identity is one)");
+    if (N == H && H > 0 && P < 1) return arg_err(fn, where + "no automorphism (the identity is one)");
     for (long long i = 0; i < P * N; ++i)
       if (h.perms[h.perm_off[g] + i] < 0 || h.perms[h.perm_off[g] + i] >= N)
-        return ah_err(fn, where + "an automorphism entry is no ligand atom");
+        return arg_err(fn, where + "an automorphism entry is no ligand atom");
   }
   return DBFR_OK;
 }
@@ -456,21 +430,21 @@ static int ah_validate(const dbfr_holo_metrics_in& d, const dbfr_holo_metrics_in
 extern "C" int dbfr_holo_metrics(const dbfr_holo_metrics_in* in, const dbfr_holo_metrics_opts* opts, const dbfr_holo_metrics_out* out,
                                  void* hip_stream) {
   const char* fn = "dbfr_holo_metrics";
-  if (!in || !out) return ah_err(fn, "null argument");
-  if (in->n_group < 0 || in->n_frame < 0) return ah_err(fn, "negative n_group / n_frame");
-  if (in->max_site < 0 || in->max_site > DBFR_HOLO_MAX_SITE) return ah_limit_err("max_site (site residues)", in->max_site, DBFR_HOLO_MAX_SITE);
-  if (in->max_res < 0 || in->max_res > AH_MAX_RES) return ah_limit_err("14 max_res (pocket atoms)", 14LL * in->max_res, DBFR_HOLO_MAX_POCKET);
-  if (in->max_lig < 0 || in->max_lig > DBFR_HOLO_MAX_LIG) return ah_limit_err("max_lig (ligand atoms)", in->max_lig, DBFR_HOLO_MAX_LIG);
+  if (!in || !out) return arg_err(fn, "null argument");
+  if (in->n_group < 0 || in->n_frame < 0) return arg_err(fn, "negative n_group / n_frame");
+  if (in->max_site < 0 || in->max_site > DBFR_HOLO_MAX_SITE) return limit_err(fn, "max_site (site residues)", in->max_site, 0, DBFR_HOLO_MAX_SITE);
+  if (in->max_res < 0 || in->max_res > AH_MAX_RES) return limit_err(fn, "14 max_res (pocket atoms)", 14LL * in->max_res, 0, DBFR_HOLO_MAX_POCKET);
+  if (in->max_lig < 0 || in->max_lig > DBFR_HOLO_MAX_LIG) return limit_err(fn, "max_lig (ligand atoms)", in->max_lig, 0, DBFR_HOLO_MAX_LIG);
   dbfr_holo_metrics_opts o = {6.0f};
   if (opts) o = *opts;
-  if (!(o.radius > 0.f && o.radius <= 100.f)) return ah_err(fn, "radius must lie in (0, 100] A and must not be NaN");
-  if (in->n_group == 0) return in->n_frame == 0 ? DBFR_OK : ah_err(fn, "frames without groups");
+  if (!(o.radius > 0.f && o.radius <= 100.f)) return arg_err(fn, "radius must lie in (0, 100] A and must not be NaN");
+  if (in->n_group == 0) return in->n_frame == 0 ? DBFR_OK : arg_err(fn, "frames without groups");
   if (!in->frame_ptr || !in->site_ptr || !in->site_aatype || !in->site_row || !in->site_matched || !in->holo14 || !in->holo_mask || !in->apo14 ||
       !in->frame_mask || !in->holo_chi || !in->site_off || !in->res_ptr || !in->pocket_off || !in->pocket || !in->hlig_ptr || !in->hlig ||
       !in->pair_off || !in->lig_ptr || !in->lig_off || !in->lig || !in->perm_ptr || !in->perm_off || !in->perms)
-    return ah_err(fn, "an input array is missing");
-  if (!out->pair_dist) return ah_err(fn, "out.pair_dist (the pair table of every group) is missing");
-  if (!in->host) return ah_err(fn, "in.host (the host copies of the index arrays) is missing: the counts are validated before every launch");
+    return arg_err(fn, "an input array is missing");
+  if (!out->pair_dist) return arg_err(fn, "out.pair_dist (the pair table of every group) is missing");
+  if (!in->host) return arg_err(fn, "in.host (the host copies of the index arrays) is missing: the counts are validated before every launch");
   const dbfr_holo_metrics_in& h = *static_cast<const dbfr_holo_metrics_in*>(in->host);
   const int rc = ah_validate(*in, h);
   if (rc != DBFR_OK) return rc;
@@ -483,14 +457,10 @@ extern "C" int dbfr_holo_metrics(const dbfr_holo_metrics_in* in, const dbfr_holo
   const int n_site = h.site_ptr[in->n_group];
   if (out->lddt_den) HIPCHECK(hipMemsetAsync(out->lddt_den, 0, sizeof(int32_t) * (size_t)in->n_group, st));
   if (n_site > 0) {
-    hipLaunchKernelGGL(k_holo_pairs, dim3((unsigned)n_site), dim3(64), 0, st, a);
-    HIPCHECK(hipGetLastError());
+    HIPCHECK(launch_frames(k_holo_pairs, n_site, 64, 0, st, a));
   }
   if (in->n_frame == 0) return DBFR_OK;
   const size_t lds = 4 * (42 * (size_t)in->max_res + 6 * (size_t)in->max_lig + 2 * (size_t)in->max_site) + 16;
-  if (lds > 32 * 1024)
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_holo_frames), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_holo_frames, dim3((unsigned)in->n_frame), dim3(AH_THREADS), lds, st, a);
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(launch_frames(k_holo_frames, in->n_frame, AH_THREADS, lds, st, a));
   return DBFR_OK;
 }

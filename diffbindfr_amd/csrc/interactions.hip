@@ -7,6 +7,7 @@
 
 #include "../../include/dbfr.h"
 #include "common.h"
+#include "frames.h"
 
 // One workgroup per frame.  The ligand (positions, XS types, neighbour lists) and the centres and normals of its groups in this
 // frame are staged in LDS next to one 16-bit word per residue (two to a 32-bit LDS word).  The receptor atoms (pocket atoms of
@@ -15,7 +16,7 @@
 // past one per thread: centre and normal from this frame's positions, tested against the ligand groups.  Hits are ORed into the
 // LDS words with integer atomics; the row is written coalesced and the per-kind counts are popcounts of ballots.  Only integer
 // ORs and sums leave a thread: the bits of a frame do not depend on the launch it is part of.
-#define IF_THREADS 256
+#define IF_THREADS FR_THREADS
 #define IF_MAX_LIG 256
 #define IF_MAX_LGRP 32
 #define IF_MAX_RES 16384
@@ -87,12 +88,7 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
   const dbfr_interactions_in& in = a.in;
   __shared__ IfThr o;                                       // the thresholds: read from LDS, not held in scalar registers
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
-  int g = 0, hi = in.n_group;                               // the last group whose first frame is <= f
-  while (hi - g > 1) {
-    const int mid = (g + hi) >> 1;
-    if (in.frame_ptr[mid] <= f) g = mid;
-    else hi = mid;
-  }
+  const int g = frame_group(in.frame_ptr, in.n_group, f);
   const int k = f - in.frame_ptr[g];
   const int l0 = in.lig_ptr[g], N = in.lig_ptr[g + 1] - l0;
   const int g0 = in.lgrp_ptr[g], LG = in.lgrp_ptr[g + 1] - g0;
@@ -111,7 +107,7 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
     const float* lp = in.lig_pos + 3 * (in.lig_pos_off[g] + (long long)k * N);
     for (int i = tid; i < N; i += IF_THREADS) {
       const float x = lp[3 * i], y = lp[3 * i + 1], z = lp[3 * i + 2];
-      bad_atom |= !(fabsf(x) <= 1e4f && fabsf(y) <= 1e4f && fabsf(z) <= 1e4f);
+      bad_atom |= !atom_ok(x, y, z);
       const int ty = min(max((int)in.lig_type[l0 + i], 0), 16);
       lx[i] = make_float4(x, y, z, __int_as_float(ty));
 #pragma unroll
@@ -123,7 +119,7 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
   }
   __syncthreads();
   const int MR = M + S;
-  const float* pp = in.pocket_pos + 3 * (in.pocket_pos_off[g] + (long long)k * M);
+  const Receptor rec = {in.pocket_pos + 3 * (in.pocket_pos_off[g] + (long long)k * M), in.static_pos + 3 * (size_t)s0, nullptr, nullptr, M};
   if (shape_ok && NR > 0) {
     // ligand groups of this frame
     if (tid < LG) {
@@ -146,10 +142,10 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
     }
     // receptor atoms against the ligand atoms: bits 0, 1, 2, 9
     for (int b = tid; b < MR; b += IF_THREADS) {
-      const float* y = b < M ? pp + 3 * (size_t)b : in.static_pos + 3 * (size_t)(s0 + (b - M));
+      const float* y = rec.pos(b);
       const float yx = y[0], yy = y[1], yz = y[2];
-      bad_atom |= !(fabsf(yx) <= 1e4f && fabsf(yy) <= 1e4f && fabsf(yz) <= 1e4f);
-      const int4 meta = *(const int4*)((b < M ? in.pocket_meta + 4 * (size_t)(m0 + b) : in.static_meta + 4 * (size_t)(s0 + (b - M))));
+      bad_atom |= !atom_ok(yx, yy, yz);
+      const int4 meta = *(const int4*)rec.sel(b, in.pocket_meta + 4 * (size_t)m0, in.static_meta + 4 * (size_t)s0, 4);
       const int tb = min(meta.x & 255, 16);
       const int res = min(max(meta.x >> 8, 0), NR - 1);
       const bool hyd_b = IF_HYD >> tb & 1u, don_b = IF_DON >> tb & 1u, acc_b = IF_ACC >> tb & 1u;
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
           for (int j = 0; j < 3; ++j) {
             nv[j] = nbi[j] >= 0;
             const int c = min(max(nbi[j], 0), MR - 1);
-            const float* z = c < M ? pp + 3 * (size_t)c : in.static_pos + 3 * (size_t)(s0 + (c - M));
+            const float* z = rec.pos(c);
             ny[j][0] = z[0]; ny[j][1] = z[1]; ny[j][2] = z[2];
           }
           loaded = true;
@@ -218,7 +214,7 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
 #pragma unroll
       for (int j = 0; j < IF_GROUP_W; ++j) {
         const int b = min(max(at[j], 0), max(MR - 1, 0));
-        const float* y = b < M ? pp + 3 * (size_t)b : in.static_pos + 3 * (size_t)(s0 + (b - M));
+        const float* y = rec.pos(b);
         const bool use = at[j] >= 0 && MR > 0;
         p[j][0] = use ? y[0] : 0.f; p[j][1] = use ? y[1] : 0.f; p[j][2] = use ? y[2] : 0.f;
         n += (use && n == j);
@@ -274,43 +270,33 @@ __global__ __launch_bounds__(IF_THREADS) void k_interactions(IfArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int if_limit_err(const char* what, int got, int lim) {
-  dbfr_set_error(std::string("dbfr_interactions: ") + what + " " + std::to_string(got) + " outside [0, " + std::to_string(lim) +
-                 "]: groups beyond it are not supported");
-  return DBFR_ERR_ARG;
-}
-
 static float cos_deg(float deg) { return (float)std::cos((double)deg * 3.14159265358979323846 / 180.0); }
 
 extern "C" int dbfr_interactions(const dbfr_interactions_in* in, const dbfr_interactions_opts* opts, const dbfr_interactions_out* out,
                                  void* hip_stream) {
-  if (!in || !out) { dbfr_set_error("dbfr_interactions: null argument"); return DBFR_ERR_ARG; }
-  if (in->n_group < 0 || in->n_frame < 0) { dbfr_set_error("dbfr_interactions: negative n_group / n_frame"); return DBFR_ERR_ARG; }
-  if (in->max_lig < 0 || in->max_lig > IF_MAX_LIG) return if_limit_err("max_lig (ligand atoms)", in->max_lig, IF_MAX_LIG);
-  if (in->max_lgrp < 0 || in->max_lgrp > IF_MAX_LGRP) return if_limit_err("max_lgrp (ligand rings and charge centres)", in->max_lgrp, IF_MAX_LGRP);
-  if (in->max_res < 0 || in->max_res > IF_MAX_RES) return if_limit_err("max_res (residues)", in->max_res, IF_MAX_RES);
+  const char* fn = "dbfr_interactions";
+  if (!in || !out) return arg_err(fn, "null argument");
+  if (in->n_group < 0 || in->n_frame < 0) return arg_err(fn, "negative n_group / n_frame");
+  if (in->max_lig < 0 || in->max_lig > IF_MAX_LIG) return limit_err(fn, "max_lig (ligand atoms)", in->max_lig, 0, IF_MAX_LIG);
+  if (in->max_lgrp < 0 || in->max_lgrp > IF_MAX_LGRP) return limit_err(fn, "max_lgrp (ligand rings and charge centres)", in->max_lgrp, 0, IF_MAX_LGRP);
+  if (in->max_res < 0 || in->max_res > IF_MAX_RES) return limit_err(fn, "max_res (residues)", in->max_res, 0, IF_MAX_RES);
   dbfr_interactions_opts o = {4.0f, 3.5f, 90.f, 5.5f, 6.0f, 2.0f, 5.5f, 2.0f, 30.f, 60.f, 4.0f, 135.f, 90.f, 150.f};
   if (opts) o = *opts;
   const float lengths[] = {o.hydrophobic_dist, o.hbond_dist, o.ionic_dist, o.cation_pi_dist, o.cation_pi_offset, o.pi_dist, o.pi_offset,
                            o.xbond_dist};
   const float angles[] = {o.hbond_angle, o.face_angle, o.edge_angle, o.xbond_donor_angle, o.xbond_acceptor_min, o.xbond_acceptor_max};
   for (float v : lengths)
-    if (!(v >= 0.f && v <= 100.f)) { dbfr_set_error("dbfr_interactions: a length threshold is NaN or outside [0, 100] A"); return DBFR_ERR_ARG; }
+    if (!(v >= 0.f && v <= 100.f)) return arg_err(fn, "a length threshold is NaN or outside [0, 100] A");
   for (float v : angles)
-    if (!(v >= 0.f && v <= 180.f)) { dbfr_set_error("dbfr_interactions: an angle threshold is NaN or outside [0, 180] degrees"); return DBFR_ERR_ARG; }
+    if (!(v >= 0.f && v <= 180.f)) return arg_err(fn, "an angle threshold is NaN or outside [0, 180] degrees");
   if (in->n_frame == 0) return DBFR_OK;
-  if (in->n_group == 0) { dbfr_set_error("dbfr_interactions: frames without groups"); return DBFR_ERR_ARG; }
+  if (in->n_group == 0) return arg_err(fn, "frames without groups");
   if (!in->frame_ptr || !in->lig_ptr || !in->lig_pos_off || !in->lig_pos || !in->lig_type || !in->lig_nbr || !in->lgrp_ptr || !in->lgrp ||
       !in->pocket_ptr || !in->pocket_pos_off || !in->pocket_pos || !in->pocket_meta || !in->rgrp_ptr || !in->rgrp || !in->res_ptr ||
-      !in->bits_off) {
-    dbfr_set_error("dbfr_interactions: frame_ptr / lig_ptr / lig_pos_off / lig_pos / lig_type / lig_nbr / lgrp_ptr / lgrp / pocket_ptr / "
-                   "pocket_pos_off / pocket_pos / pocket_meta / rgrp_ptr / rgrp / res_ptr / bits_off missing");
-    return DBFR_ERR_ARG;
-  }
-  if (in->static_ptr && (!in->static_pos || !in->static_meta)) {
-    dbfr_set_error("dbfr_interactions: static_ptr given without static_pos / static_meta");
-    return DBFR_ERR_ARG;
-  }
+      !in->bits_off)
+    return arg_err(fn, "frame_ptr / lig_ptr / lig_pos_off / lig_pos / lig_type / lig_nbr / lgrp_ptr / lgrp / pocket_ptr / pocket_pos_off / "
+                       "pocket_pos / pocket_meta / rgrp_ptr / rgrp / res_ptr / bits_off missing");
+  if (in->static_ptr && (!in->static_pos || !in->static_meta)) return arg_err(fn, "static_ptr given without static_pos / static_meta");
   IfArgs a;
   a.in = *in;
   a.out = *out;
@@ -321,7 +307,6 @@ extern "C" int dbfr_interactions(const dbfr_interactions_in* in, const dbfr_inte
   t.cos_xmin = cos_deg(o.xbond_acceptor_min); t.cos_xmax = cos_deg(o.xbond_acceptor_max);
   const float widest = std::fmax(o.hydrophobic_dist, std::fmax(o.hbond_dist, o.xbond_dist)) + IF_EARLY;
   t.early2 = widest * widest;
-  hipLaunchKernelGGL(k_interactions, dim3((unsigned)in->n_frame), dim3(IF_THREADS), 0, (hipStream_t)hip_stream, a);
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(launch_frames(k_interactions, in->n_frame, IF_THREADS, 0, hip_stream, a));
   return DBFR_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "../../include/dbfr.h"
 #include "common.h"
+#include "frames.h"
 
 // One workgroup per frame.  The frame's MOVABLE atoms (x, y, z, r) are staged in LDS in list order, with their bounding box.
 // The partners (pocket atoms of the frame, then the static atoms of the group) stream past in tiles of one atom per thread: a
@@ -20,8 +21,8 @@
 // the frame has a pair below cap; a frame without one (nothing near its side chains) takes a second pass over every partner
 // without any filter.  Every reduction is a minimum over (ratio, a, b) keys, a maximum or an integer count, and the per-residue
 // bytes saturate: the bits of a frame do not depend on the launch it is part of.
-#define PK_THREADS 256
-#define PK_WAVES (PK_THREADS / 64)
+#define PK_THREADS FR_THREADS
+#define PK_WAVES FR_WAVES
 #define PK_MAX_POCKET 8192
 #define PK_MAX_EXCL 32
 #define PK_MAX_RES 16384
@@ -43,11 +44,6 @@ struct PkKey {                     // the worst pair so far: smallest ratio, tie
 
 __device__ __forceinline__ bool key_less(float r, int a, int b, const PkKey& k) {
   return r < k.r || (r == k.r && (a < k.a || (a == k.a && b < k.b)));
-}
-
-__device__ __forceinline__ int pk_wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // saturating +1 on byte `col` of the packed residue counters (rare: only clashing pairs come here)
@@ -136,12 +132,7 @@ __global__ __launch_bounds__(PK_THREADS) void k_pocket_check(PkArgs a) {
   float4* mx = pk_dyn;
   unsigned* resw = reinterpret_cast<unsigned*>(pk_dyn + a.lds_mov);
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g = 0, hi = in.n_group;                               // the last group whose first frame is <= f
-  while (hi - g > 1) {
-    const int mid = (g + hi) >> 1;
-    if (in.frame_ptr[mid] <= f) g = mid;
-    else hi = mid;
-  }
+  const int g = frame_group(in.frame_ptr, in.n_group, f);
   const int k = f - in.frame_ptr[g];
   const int m0 = in.pocket_ptr[g], M = in.pocket_ptr[g + 1] - m0;
   const int s0 = in.static_ptr ? in.static_ptr[g] : 0, S = in.static_ptr ? in.static_ptr[g + 1] - s0 : 0;
@@ -153,35 +144,20 @@ __global__ __launch_bounds__(PK_THREADS) void k_pocket_check(PkArgs a) {
   const float clash = a.o.clash_ratio, cap = fmaxf(clash, 1.f);
   const int MR = shape_ok ? M + S : 0;
   const float* pp = in.pocket_pos + 3 * (in.pocket_pos_off[g] + (long long)k * M);
+  const Receptor rec = {pp, in.static_pos + 3 * (size_t)s0, in.pocket_rad + m0, in.static_rad + s0, M};
   int bad_atom = 0;
   if (res_ok)
     for (int t = tid; t < (NR + 3) / 4; t += PK_THREADS) resw[t] = 0u;
   // the movable atoms and their bounding box
-  float lox = INFINITY, loy = INFINITY, loz = INFINITY, hix = -INFINITY, hiy = -INFINITY, hiz = -INFINITY, rmax = 0.f;
+  FrameBox box;
   if (shape_ok)
     for (int i = tid; i < NMOV; i += PK_THREADS) {
       const int at = min(max(in.mov_atom[v0 + i], 0), M - 1);
       const float x = pp[3 * (size_t)at], y = pp[3 * (size_t)at + 1], z = pp[3 * (size_t)at + 2], r = in.pocket_rad[m0 + at];
       mx[i] = make_float4(x, y, z, r);
-      lox = fminf(lox, x); loy = fminf(loy, y); loz = fminf(loz, z);
-      hix = fmaxf(hix, x); hiy = fmaxf(hiy, y); hiz = fmaxf(hiz, z);
-      rmax = fmaxf(rmax, r);
+      box.add(x, y, z, r);
     }
-  for (int o = 32; o > 0; o >>= 1) {
-    lox = fminf(lox, __shfl_xor(lox, o)); loy = fminf(loy, __shfl_xor(loy, o)); loz = fminf(loz, __shfl_xor(loz, o));
-    hix = fmaxf(hix, __shfl_xor(hix, o)); hiy = fmaxf(hiy, __shfl_xor(hiy, o)); hiz = fmaxf(hiz, __shfl_xor(hiz, o));
-    rmax = fmaxf(rmax, __shfl_xor(rmax, o));
-  }
-  if (lane == 0) {
-    redf[wave][0] = lox; redf[wave][1] = loy; redf[wave][2] = loz; redf[wave][3] = hix; redf[wave][4] = hiy; redf[wave][5] = hiz;
-    redf[wave][6] = rmax;
-  }
-  __syncthreads();                                          // mx, resw and the per-wave boxes complete
-  for (int w = 0; w < PK_WAVES; ++w) {
-    lox = fminf(lox, redf[w][0]); loy = fminf(loy, redf[w][1]); loz = fminf(loz, redf[w][2]);
-    hix = fmaxf(hix, redf[w][3]); hiy = fmaxf(hiy, redf[w][4]); hiz = fmaxf(hiz, redf[w][5]);
-    rmax = fmaxf(rmax, redf[w][6]);
-  }
+  box.block_reduce(redf, lane, wave);                       // (its barrier: mx and resw complete too)
   PkFrame fr;
   fr.mx = mx; fr.resw = resw; fr.mov_atom = in.mov_atom + v0; fr.excl_ptr = in.excl_ptr + v0; fr.excl = in.excl;
   fr.pocket_col = in.pocket_col + m0; fr.M = M; fr.NMOV = shape_ok ? NMOV : 0; fr.NR = NR; fr.clash = clash; fr.cap = cap;
@@ -194,31 +170,24 @@ __global__ __launch_bounds__(PK_THREADS) void k_pocket_check(PkArgs a) {
     const int b = b0 + tid;
     bool c = false;
     if (b < MR) {
-      const float* y = b < M ? pp + 3 * (size_t)b : in.static_pos + 3 * (size_t)(s0 + (b - M));
+      const float* y = rec.pos(b);
       const float bx = y[0], by = y[1], bz = y[2];
-      const float rb = b < M ? in.pocket_rad[m0 + b] : in.static_rad[s0 + (b - M)];
-      bad_atom |= !(fabsf(bx) <= 1e4f && fabsf(by) <= 1e4f && fabsf(bz) <= 1e4f && rb > 0.f && rb <= 4.f);
-      const float grow = cap * (rb + rmax) * 1.00001f + 1e-3f;
-      c = b < M || (bx >= lox - grow && bx <= hix + grow && by >= loy - grow && by <= hiy + grow && bz >= loz - grow && bz <= hiz + grow);
+      const float rb = rec.rad(b);
+      bad_atom |= !atom_ok(bx, by, bz, rb);
+      const float grow = cap * (rb + box.rmax) * 1.00001f + 1e-3f;
+      c = b < M || box.touches(bx, by, bz, grow);
     }
-    const unsigned long long bal = __ballot(c);
-    const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = ncand, tot = 0;
-    for (int w = 0; w < PK_WAVES; ++w) {
-      off += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    if (c) cand[off + pre] = b;                             // off + pre < ncand + 256 <= cap: the list was worked off in time
+    int slot, tot;
+    block_compact(c, ncand, wcnt, lane, wave, slot, tot);
+    if (c) cand[slot] = b;                                  // slot < ncand + 256 <= cap: a full list is worked off in time (below)
     ncand += tot;
     __syncthreads();                                        // cand complete; wcnt is rewritten by the next tile
     if (ncand + PK_THREADS > a.cap || b0 + PK_THREADS >= MR) {
       for (int t = tid; t < ncand; t += PK_THREADS) {
         const int bb = cand[t];
-        const float* y = bb < M ? pp + 3 * (size_t)bb : in.static_pos + 3 * (size_t)(s0 + (bb - M));
-        const float rb = bb < M ? in.pocket_rad[m0 + bb] : in.static_rad[s0 + (bb - M)];
-        const int colb = bb < M ? in.pocket_col[m0 + bb] : in.static_col[s0 + (bb - M)];
+        const float* y = rec.pos(bb);
+        const float rb = rec.rad(bb);
+        const int colb = *rec.sel(bb, in.pocket_col + m0, in.static_col + s0);
         const int rankb = bb < M ? in.pocket_rank[m0 + bb] : -1;
         scan_partner<false>(fr, bb, y[0], y[1], y[2], rb, colb, rankb, bb < M ? (rankb >= 0 ? 0 : 1) : 2, key, thr, n);
       }
@@ -230,8 +199,8 @@ __global__ __launch_bounds__(PK_THREADS) void k_pocket_check(PkArgs a) {
   key = block_min_key(key, redf, redi, lane, wave);
   if (!bad && key.a < 0 && fr.NMOV > 0) {                     // no pair below cap: every partner, no filter (uniform branch)
     for (int b = tid; b < MR; b += PK_THREADS) {
-      const float* y = b < M ? pp + 3 * (size_t)b : in.static_pos + 3 * (size_t)(s0 + (b - M));
-      const float rb = b < M ? in.pocket_rad[m0 + b] : in.static_rad[s0 + (b - M)];
+      const float* y = rec.pos(b);
+      const float rb = rec.rad(b);
       const int rankb = b < M ? in.pocket_rank[m0 + b] : -1;
       scan_partner<true>(fr, b, y[0], y[1], y[2], rb, 0, rankb, 0, key, thr, n);
     }
@@ -243,16 +212,15 @@ __global__ __launch_bounds__(PK_THREADS) void k_pocket_check(PkArgs a) {
   if (MR > 0)
     for (int t = tid; t < NC; t += PK_THREADS) {
       const int ia = min(max(in.closure_ab[2 * (size_t)(c0 + t)], 0), MR - 1), ib = min(max(in.closure_ab[2 * (size_t)(c0 + t) + 1], 0), MR - 1);
-      const float* p = ia < M ? pp + 3 * (size_t)ia : in.static_pos + 3 * (size_t)(s0 + (ia - M));
-      const float* q = ib < M ? pp + 3 * (size_t)ib : in.static_pos + 3 * (size_t)(s0 + (ib - M));
+      const float *p = rec.pos(ia), *q = rec.pos(ib);
       const float dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
       const float dev = fabsf(sqrtf(dx * dx + dy * dy + dz * dz) - in.closure_len[c0 + t]);
       nbroken += dev > a.o.bond_tol;
       maxdev = fmaxf(maxdev, dev);
     }
-  for (int o = 32; o > 0; o >>= 1) maxdev = fmaxf(maxdev, __shfl_xor(maxdev, o));
-  nbroken = pk_wave_sum(nbroken);
-  n[0] = pk_wave_sum(n[0]); n[1] = pk_wave_sum(n[1]); n[2] = pk_wave_sum(n[2]);
+  maxdev = wave_max(maxdev);
+  nbroken = wave_sum(nbroken);
+  n[0] = wave_sum(n[0]); n[1] = wave_sum(n[1]); n[2] = wave_sum(n[2]);
   if (lane == 0) {
     redf[wave][0] = maxdev;
     redi[wave][0] = n[0]; redi[wave][1] = n[1]; redi[wave][2] = n[2]; redi[wave][3] = nbroken;
@@ -285,15 +253,7 @@ __global__ __launch_bounds__(PK_THREADS) void k_pocket_check(PkArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int pk_err(const std::string& s) {
-  dbfr_set_error("dbfr_pocket_check: " + s);
-  return DBFR_ERR_ARG;
-}
-
-static int pk_limit_err(const char* what, int got, int lo, int lim) {
-  return pk_err(std::string(what) + " " + std::to_string(got) + " outside [" + std::to_string(lo) + ", " + std::to_string(lim) +
-                "]: groups beyond it are not supported");
-}
+static int pk_err(const std::string& s) { return arg_err("dbfr_pocket_check", s); }
 
 // the host copies of the index arrays, when the caller has them: every list length, atom index, column and radius
 static int pk_validate(const dbfr_pocket_check_in& d, const dbfr_pocket_check_in& h) {
@@ -301,23 +261,21 @@ static int pk_validate(const dbfr_pocket_check_in& d, const dbfr_pocket_check_in
       !h.excl || !h.closure_ptr || !h.closure_ab || !h.closure_len || !h.res_ptr || (d.static_ptr && (!h.static_ptr || !h.static_rad || !h.static_col)))
     return pk_err("host: a host copy of an index array is missing");
   const int G = d.n_group;
-  if (h.frame_ptr[0] != 0 || h.frame_ptr[G] != d.n_frame) return pk_err("frame_ptr does not run from 0 to n_frame");
+  const char* fn = "dbfr_pocket_check";
+  if (const int rc = frame_ptr_err(fn, h.frame_ptr, G, d.n_frame)) return rc;
   for (int g = 0; g < G; ++g) {
     const std::string where = "group " + std::to_string(g) + ": ";
     const int m0 = h.pocket_ptr[g], M = h.pocket_ptr[g + 1] - m0, s0 = d.static_ptr ? h.static_ptr[g] : 0,
               S = d.static_ptr ? h.static_ptr[g + 1] - s0 : 0, v0 = h.mov_ptr[g], NMOV = h.mov_ptr[g + 1] - v0, c0 = h.closure_ptr[g],
               NC = h.closure_ptr[g + 1] - c0, NR = h.res_ptr[g + 1] - h.res_ptr[g];
-    if (h.frame_ptr[g + 1] < h.frame_ptr[g] || M < 0 || S < 0 || NMOV < 0 || NC < 0 || NR < 0) return pk_err(where + "a negative count");
-    if (M > d.max_pocket) return pk_err(where + std::to_string(M) + " pocket atoms, max_pocket says " + std::to_string(d.max_pocket));
-    if (NR > d.max_res) return pk_err(where + std::to_string(NR) + " residue columns, max_res says " + std::to_string(d.max_res));
+    if (const int rc = group_counts_err(fn, where, {{h.frame_ptr[g + 1] - h.frame_ptr[g]}, {M, "pocket atoms", "max_pocket", d.max_pocket}, {S},
+                                                    {NMOV}, {NC}, {NR, "residue columns", "max_res", d.max_res}}))
+      return rc;
     if (NMOV > M) return pk_err(where + "more movable atoms than pocket atoms");
     const int MR = M + S;
-    for (int b = 0; b < MR; ++b) {
-      const float r = b < M ? h.pocket_rad[m0 + b] : h.static_rad[s0 + b - M];
-      const int col = b < M ? h.pocket_col[m0 + b] : h.static_col[s0 + b - M];
-      if (!(r > 0.f && r <= 4.f)) return pk_err(where + "the radius of receptor atom " + std::to_string(b) + " lies outside (0, 4]");
-      if (col < 0 || col >= NR) return pk_err(where + "the residue column of receptor atom " + std::to_string(b) + " is out of range");
-    }
+    if (const int rc = receptor_atoms_err(fn, where, M, S, h.pocket_rad + m0, d.static_ptr ? h.static_rad + s0 : nullptr, h.pocket_col + m0,
+                                          d.static_ptr ? h.static_col + s0 : nullptr, NR, [](int) { return DBFR_OK; }))
+      return rc;
     int n_rank = 0;
     for (int b = 0; b < M; ++b) {
       const int rk = h.pocket_rank[m0 + b];
@@ -354,11 +312,11 @@ extern "C" int dbfr_pocket_check(const dbfr_pocket_check_in* in, const dbfr_pock
                                  void* hip_stream) {
   if (!in || !out) return pk_err("null argument");
   if (in->n_group < 0 || in->n_frame < 0) return pk_err("negative n_group / n_frame");
-  if (in->max_pocket < 0 || in->max_pocket > PK_MAX_POCKET) return pk_limit_err("max_pocket (pocket atoms)", in->max_pocket, 0, PK_MAX_POCKET);
-  if (in->max_excl < 0 || in->max_excl > PK_MAX_EXCL) return pk_limit_err("max_excl (exclusion list length)", in->max_excl, 0, PK_MAX_EXCL);
-  if (in->max_res < 0 || in->max_res > PK_MAX_RES) return pk_limit_err("max_res (residue columns)", in->max_res, 0, PK_MAX_RES);
+  if (in->max_pocket < 0 || in->max_pocket > PK_MAX_POCKET) return limit_err("dbfr_pocket_check", "max_pocket (pocket atoms)", in->max_pocket, 0, PK_MAX_POCKET);
+  if (in->max_excl < 0 || in->max_excl > PK_MAX_EXCL) return limit_err("dbfr_pocket_check", "max_excl (exclusion list length)", in->max_excl, 0, PK_MAX_EXCL);
+  if (in->max_res < 0 || in->max_res > PK_MAX_RES) return limit_err("dbfr_pocket_check", "max_res (residue columns)", in->max_res, 0, PK_MAX_RES);
   if (in->cand_cap != 0 && (in->cand_cap < PK_THREADS || in->cand_cap > PK_CAND))
-    return pk_limit_err("cand_cap (LDS partner candidates)", in->cand_cap, PK_THREADS, PK_CAND);
+    return limit_err("dbfr_pocket_check", "cand_cap (LDS partner candidates)", in->cand_cap, PK_THREADS, PK_CAND);
   dbfr_pocket_check_opts o = {0.75f, 0.3f, 0};
   if (opts) o = *opts;
   if (!(o.clash_ratio > 0.f && o.clash_ratio <= 10.f)) return pk_err("clash_ratio must lie in (0, 10] and must not be NaN");
@@ -385,9 +343,6 @@ extern "C" int dbfr_pocket_check(const dbfr_pocket_check_in* in, const dbfr_pock
   a.cap = in->cand_cap ? in->cand_cap : PK_CAND;
   a.lds_mov = in->max_pocket;
   const size_t lds = 16 * (size_t)in->max_pocket + 4 * (size_t)((in->max_res + 3) / 4) + 16;
-  if (lds > 32 * 1024)
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pocket_check), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_pocket_check, dim3((unsigned)in->n_frame), dim3(PK_THREADS), lds, (hipStream_t)hip_stream, a);
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(launch_frames(k_pocket_check, in->n_frame, PK_THREADS, lds, hip_stream, a));
   return DBFR_OK;
 }

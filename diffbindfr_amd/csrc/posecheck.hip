@@ -8,6 +8,7 @@
 
 #include "../../include/dbfr.h"
 #include "common.h"
+#include "frames.h"
 
 // One workgroup per frame.  The ligand (positions, radii) and, per atom, the bit mask of the lower-index ligand atoms whose
 // lattice spheres can share a point with its own are staged in LDS.  The receptor (pocket atoms of the frame, then the static
@@ -16,8 +17,8 @@
 // pass walks every ligand atom's bounding box; a point inside the atom's sphere counts for the lowest-index atom whose sphere
 // holds it (its neighbour mask says which atoms to ask) and is then tested against the compacted receptor atoms.  Every
 // reduction is a min / max or an integer sum: the bits of a frame do not depend on the launch it is part of.
-#define PC_THREADS 256
-#define PC_WAVES (PC_THREADS / 64)
+#define PC_THREADS FR_THREADS
+#define PC_WAVES FR_WAVES
 #define PC_MAX_LIG 256
 #define PC_MAX_PAIR 32640          // every pair of 256 atoms
 #define PC_MAX_FLAT 64
@@ -32,19 +33,6 @@ struct PcArgs {
   dbfr_pose_check_out out;
   int cap;
 };
-
-__device__ __forceinline__ float wave_min(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 __device__ __forceinline__ float dist2(float px, float py, float pz, float qx, float qy, float qz) {
   const float dx = px - qx, dy = py - qy, dz = pz - qz;
@@ -126,12 +114,7 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
   const dbfr_pose_check_in& in = a.in;
   const dbfr_pose_check_opts& o = a.o;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g = 0, hi = in.n_group;                               // the last group whose first frame is <= f
-  while (hi - g > 1) {
-    const int mid = (g + hi) >> 1;
-    if (in.frame_ptr[mid] <= f) g = mid;
-    else hi = mid;
-  }
+  const int g = frame_group(in.frame_ptr, in.n_group, f);
   const int k = f - in.frame_ptr[g];
   const int l0 = in.lig_ptr[g], N = in.lig_ptr[g + 1] - l0;
   const int m0 = in.pocket_ptr[g], M = in.pocket_ptr[g + 1] - m0;
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
     const float* lp = in.lig_pos + 3 * (in.lig_pos_off[g] + (long long)k * N);
     for (int i = tid; i < N; i += PC_THREADS) {
       const float x = lp[3 * i], y = lp[3 * i + 1], z = lp[3 * i + 2], r = in.lig_rad[l0 + i];
-      bad_atom |= !(fabsf(x) <= 1e4f && fabsf(y) <= 1e4f && fabsf(z) <= 1e4f && r > 0.f && r <= 4.f);
+      bad_atom |= !atom_ok(x, y, z, r);
       lx[i] = make_float4(x, y, z, r);
     }
   }
@@ -184,7 +167,8 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
     nbm[i][w] = m;
   }
   // receptor pass: distances, ratios, clashes, candidates (index order: pocket atoms, then static atoms)
-  const float* pp = in.pocket_pos + 3 * (in.pocket_pos_off[g] + (long long)k * M);
+  const Receptor rec = {in.pocket_pos + 3 * (in.pocket_pos_off[g] + (long long)k * M), in.static_pos + 3 * (size_t)s0, in.pocket_rad + m0,
+                        in.static_rad + s0, M};
   const int MR = M + S;
   float mind = INFINITY, minr = INFINITY;
   int ncl = 0, ncand = 0;
@@ -193,9 +177,9 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
     bool c = false;
     float yx = 0.f, yy = 0.f, yz = 0.f, rb = 0.f;
     if (b < MR) {
-      const float* y = b < M ? pp + 3 * b : in.static_pos + 3 * (s0 + (b - M));
+      const float* y = rec.pos(b);
       yx = y[0]; yy = y[1]; yz = y[2];
-      rb = b < M ? in.pocket_rad[m0 + b] : in.static_rad[s0 + b - M];
+      rb = rec.rad(b);
       const float Rb = vs * rb;
       for (int i = 0; i < N; ++i) {
         const float4 q = lx[i];
@@ -207,18 +191,11 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
         c = c || d < vs * q.w + Rb + PC_MARGIN;
       }
     }
-    const unsigned long long bal = __ballot(c);
-    const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = ncand, tot = 0;
-    for (int w = 0; w < PC_WAVES; ++w) {
-      off += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    if (c && off + pre < a.cap) {
+    int slot, tot;
+    block_compact(c, ncand, wcnt, lane, wave, slot, tot);
+    if (c && slot < a.cap) {                                // a full list drops the entry: `spill` below sends the lattice pass to memory
       const float Rb = vs * rb;
-      cand[off + pre] = make_float4(yx, yy, yz, Rb * Rb);
+      cand[slot] = make_float4(yx, yy, yz, Rb * Rb);
     }
     ncand += tot;
     __syncthreads();                                        // wcnt is rewritten by the next tile
@@ -293,8 +270,8 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
       }
       if (spill)
         for (int b = 0; b < MR && !hit; ++b) {
-          const float* y = b < M ? pp + 3 * b : in.static_pos + 3 * (s0 + (b - M));
-          const float Rb = vs * (b < M ? in.pocket_rad[m0 + b] : in.static_rad[s0 + b - M]);
+          const float* y = rec.pos(b);
+          const float Rb = vs * rec.rad(b);
           hit = dist2(px, py, pz, y[0], y[1], y[2]) < Rb * Rb;
         }
       nov += hit;
@@ -349,48 +326,35 @@ __global__ __launch_bounds__(PC_THREADS) void k_pose_check(PcArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int limit_err(const char* what, int got, int lim) {
-  dbfr_set_error(std::string("dbfr_pose_check: ") + what + " " + std::to_string(got) + " outside [0, " + std::to_string(lim) +
-                 "]: groups beyond it are not supported");
-  return DBFR_ERR_ARG;
-}
-
 extern "C" int dbfr_pose_check(const dbfr_pose_check_in* in, const dbfr_pose_check_opts* opts, const dbfr_pose_check_out* out,
                                void* hip_stream) {
-  if (!in || !out) { dbfr_set_error("dbfr_pose_check: null argument"); return DBFR_ERR_ARG; }
-  if (in->n_group < 0 || in->n_frame < 0) { dbfr_set_error("dbfr_pose_check: negative n_group / n_frame"); return DBFR_ERR_ARG; }
-  if (in->max_lig < 0 || in->max_lig > PC_MAX_LIG) return limit_err("max_lig (ligand atoms)", in->max_lig, PC_MAX_LIG);
-  if (in->max_pair < 0 || in->max_pair > PC_MAX_PAIR) return limit_err("max_pair (internal pairs)", in->max_pair, PC_MAX_PAIR);
-  if (in->max_flat < 0 || in->max_flat > PC_MAX_FLAT) return limit_err("max_flat (flatness bonds)", in->max_flat, PC_MAX_FLAT);
-  if (in->max_stereo < 0 || in->max_stereo > PC_MAX_STEREO) return limit_err("max_stereo (stereo bonds)", in->max_stereo, PC_MAX_STEREO);
-  if (in->cand_cap < 0 || in->cand_cap > PC_CAND) return limit_err("cand_cap (LDS receptor candidates)", in->cand_cap, PC_CAND);
+  const char* fn = "dbfr_pose_check";
+  if (!in || !out) return arg_err(fn, "null argument");
+  if (in->n_group < 0 || in->n_frame < 0) return arg_err(fn, "negative n_group / n_frame");
+  if (in->max_lig < 0 || in->max_lig > PC_MAX_LIG) return limit_err(fn, "max_lig (ligand atoms)", in->max_lig, 0, PC_MAX_LIG);
+  if (in->max_pair < 0 || in->max_pair > PC_MAX_PAIR) return limit_err(fn, "max_pair (internal pairs)", in->max_pair, 0, PC_MAX_PAIR);
+  if (in->max_flat < 0 || in->max_flat > PC_MAX_FLAT) return limit_err(fn, "max_flat (flatness bonds)", in->max_flat, 0, PC_MAX_FLAT);
+  if (in->max_stereo < 0 || in->max_stereo > PC_MAX_STEREO) return limit_err(fn, "max_stereo (stereo bonds)", in->max_stereo, 0, PC_MAX_STEREO);
+  if (in->cand_cap < 0 || in->cand_cap > PC_CAND) return limit_err(fn, "cand_cap (LDS receptor candidates)", in->cand_cap, 0, PC_CAND);
   dbfr_pose_check_opts o = {0.75f, 5.0f, 0.8f, 0.075f, 0.7f, 0.25f, 0.25f};
   if (opts) o = *opts;
-  if (!(o.grid >= 0.05f && o.grid <= 1.f)) { dbfr_set_error("dbfr_pose_check: grid must lie in [0.05, 1] A"); return DBFR_ERR_ARG; }
-  if (!(o.vol_scale > 0.f && o.vol_scale <= 2.f)) { dbfr_set_error("dbfr_pose_check: vol_scale must lie in (0, 2]"); return DBFR_ERR_ARG; }
+  if (!(o.grid >= 0.05f && o.grid <= 1.f)) return arg_err(fn, "grid must lie in [0.05, 1] A");
+  if (!(o.vol_scale > 0.f && o.vol_scale <= 2.f)) return arg_err(fn, "vol_scale must lie in (0, 2]");
   if (std::isnan(o.clash_ratio) || std::isnan(o.max_distance) || std::isnan(o.vol_overlap) || std::isnan(o.internal_ratio) ||
-      std::isnan(o.flat_tol)) {
-    dbfr_set_error("dbfr_pose_check: a threshold is NaN");
-    return DBFR_ERR_ARG;
-  }
+      std::isnan(o.flat_tol))
+    return arg_err(fn, "a threshold is NaN");
   if (in->n_frame == 0) return DBFR_OK;
-  if (in->n_group == 0) { dbfr_set_error("dbfr_pose_check: frames without groups"); return DBFR_ERR_ARG; }
+  if (in->n_group == 0) return arg_err(fn, "frames without groups");
   if (!in->frame_ptr || !in->lig_ptr || !in->lig_pos_off || !in->lig_pos || !in->lig_rad || !in->pocket_ptr ||
-      !in->pocket_pos_off || !in->pair_ptr || !in->flat_ptr || !in->stereo_ptr) {
-    dbfr_set_error("dbfr_pose_check: frame_ptr / lig_ptr / lig_pos_off / lig_pos / lig_rad / pocket_ptr / pocket_pos_off / "
-                   "pair_ptr / flat_ptr / stereo_ptr missing");
-    return DBFR_ERR_ARG;
-  }
-  if (in->static_ptr && (!in->static_pos || !in->static_rad)) {
-    dbfr_set_error("dbfr_pose_check: static_ptr given without static_pos / static_rad");
-    return DBFR_ERR_ARG;
-  }
+      !in->pocket_pos_off || !in->pair_ptr || !in->flat_ptr || !in->stereo_ptr)
+    return arg_err(fn, "frame_ptr / lig_ptr / lig_pos_off / lig_pos / lig_rad / pocket_ptr / pocket_pos_off / pair_ptr / flat_ptr / "
+                       "stereo_ptr missing");
+  if (in->static_ptr && (!in->static_pos || !in->static_rad)) return arg_err(fn, "static_ptr given without static_pos / static_rad");
   PcArgs a;
   a.in = *in;
   a.o = o;
   a.out = *out;
   a.cap = in->cand_cap ? in->cand_cap : PC_CAND;
-  hipLaunchKernelGGL(k_pose_check, dim3((unsigned)in->n_frame), dim3(PC_THREADS), 0, (hipStream_t)hip_stream, a);
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(launch_frames(k_pose_check, in->n_frame, PC_THREADS, 0, hip_stream, a));
   return DBFR_OK;
 }

@@ -8,6 +8,7 @@
 
 #include "../../include/dbfr.h"
 #include "common.h"
+#include "frames.h"
 
 // One workgroup per frame.  The ligand (x, y, z, R = r + probe) and the unit vectors sit in LDS.  Two passes over the receptor
 // (the frame's pocket atoms, then the group's static atoms): the first finds the largest R of an atom that can touch the ligand
@@ -21,8 +22,8 @@
 // loop when no lane is open any more.  A receptor atom's points go against the ligand first: most fail there.
 // The filters only drop atoms that bury no point, every point test is the same float32 expression wherever the neighbour came
 // from, and every reduction is an integer sum: the bits of a frame do not depend on the launch or on `cap`.
-#define SA_THREADS 256
-#define SA_WAVES (SA_THREADS / 64)
+#define SA_THREADS FR_THREADS
+#define SA_WAVES FR_WAVES
 #define SA_MAX_LIG 256
 #define SA_MAX_POCKET 8192
 #define SA_MAX_RES 16384
@@ -138,12 +139,7 @@ __global__ __launch_bounds__(SA_THREADS) void k_sasa(SaArgs a) {
   int* nidx = reinterpret_cast<int*>(sa_dyn + a.cap);
   int* res = nidx + a.cap;
   const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int g = 0, hi = in.n_group;                               // the last group whose first frame is <= f
-  while (hi - g > 1) {
-    const int mid = (g + hi) >> 1;
-    if (in.frame_ptr[mid] <= f) g = mid;
-    else hi = mid;
-  }
+  const int g = frame_group(in.frame_ptr, in.n_group, f);
   const int k = f - in.frame_ptr[g];
   const int n0 = in.lig_ptr[g], NL = in.lig_ptr[g + 1] - n0;
   const int m0 = in.pocket_ptr[g], M = in.pocket_ptr[g + 1] - m0;
@@ -165,43 +161,27 @@ __global__ __launch_bounds__(SA_THREADS) void k_sasa(SaArgs a) {
     for (int t = tid; t < NR; t += SA_THREADS) res[t] = 0;
   for (int t = tid; t < NP; t += SA_THREADS) pts[t] = make_float4(in.points[3 * t], in.points[3 * t + 1], in.points[3 * t + 2], 0.f);
   // the ligand and its bounding box
-  float lox = INFINITY, loy = INFINITY, loz = INFINITY, hix = -INFINITY, hiy = -INFINITY, hiz = -INFINITY, rlmax = 0.f;
+  FrameBox box;                                             // rmax: the largest R of the ligand
   if (shape_ok)
     for (int i = tid; i < NL; i += SA_THREADS) {
       const float x = lp[3 * (size_t)i], y = lp[3 * (size_t)i + 1], z = lp[3 * (size_t)i + 2], r = in.lig_rad[n0 + i];
-      bad_atom |= !(fabsf(x) <= 1e4f && fabsf(y) <= 1e4f && fabsf(z) <= 1e4f && r > 0.f && r <= 4.f);
+      bad_atom |= !atom_ok(x, y, z, r);
       const float R = r + a.probe;
       lig[i] = make_float4(x, y, z, R);
-      lox = fminf(lox, x); loy = fminf(loy, y); loz = fminf(loz, z);
-      hix = fmaxf(hix, x); hiy = fmaxf(hiy, y); hiz = fmaxf(hiz, z);
-      rlmax = fmaxf(rlmax, R);
+      box.add(x, y, z, R);
     }
-  for (int o = 32; o > 0; o >>= 1) {
-    lox = fminf(lox, __shfl_xor(lox, o)); loy = fminf(loy, __shfl_xor(loy, o)); loz = fminf(loz, __shfl_xor(loz, o));
-    hix = fmaxf(hix, __shfl_xor(hix, o)); hiy = fmaxf(hiy, __shfl_xor(hiy, o)); hiz = fmaxf(hiz, __shfl_xor(hiz, o));
-    rlmax = fmaxf(rlmax, __shfl_xor(rlmax, o));
-  }
-  if (lane == 0) {
-    redf[wave][0] = lox; redf[wave][1] = loy; redf[wave][2] = loz; redf[wave][3] = hix; redf[wave][4] = hiy; redf[wave][5] = hiz;
-    redf[wave][6] = rlmax;
-  }
-  __syncthreads();                                          // lig, pts, res and the per-wave boxes complete
-  for (int w = 0; w < SA_WAVES; ++w) {
-    lox = fminf(lox, redf[w][0]); loy = fminf(loy, redf[w][1]); loz = fminf(loz, redf[w][2]);
-    hix = fmaxf(hix, redf[w][3]); hiy = fmaxf(hiy, redf[w][4]); hiz = fmaxf(hiz, redf[w][5]);
-    rlmax = fmaxf(rlmax, redf[w][6]);
-  }
+  box.block_reduce(redf, lane, wave);                       // (its barrier: lig, pts and res complete too)
+  const float rlmax = box.rmax;
   // first pass: every coordinate and radius checked; the largest R of an atom that can touch the ligand
   float rcmax = 0.f;
   for (int b = tid; b < MR; b += SA_THREADS) {
     const float* y = b < M ? pp + 3 * (size_t)b : sp + 3 * (size_t)(b - M);
     const float bx = y[0], by = y[1], bz = y[2], rb = b < M ? prad[b] : srad[b - M];
-    bad_atom |= !(fabsf(bx) <= 1e4f && fabsf(by) <= 1e4f && fabsf(bz) <= 1e4f && rb > 0.f && rb <= 4.f);
+    bad_atom |= !atom_ok(bx, by, bz, rb);
     const float R = rb + a.probe, grow = (rlmax + R) * SA_WIDE + 0.05f;
-    if (bx >= lox - grow && bx <= hix + grow && by >= loy - grow && by <= hiy + grow && bz >= loz - grow && bz <= hiz + grow)
-      rcmax = fmaxf(rcmax, R);
+    if (box.touches(bx, by, bz, grow)) rcmax = fmaxf(rcmax, R);
   }
-  for (int o = 32; o > 0; o >>= 1) rcmax = fmaxf(rcmax, __shfl_xor(rcmax, o));
+  rcmax = wave_max(rcmax);
   if (lane == 0) redf[wave][7] = rcmax;
   const bool bad = __syncthreads_or(bad_atom) || !shape_ok; // uniform over the workgroup; redf[][7] complete
   for (int w = 0; w < SA_WAVES; ++w) rcmax = fmaxf(rcmax, redf[w][7]);
@@ -216,21 +196,14 @@ __global__ __launch_bounds__(SA_THREADS) void k_sasa(SaArgs a) {
         const float* y = b < M ? pp + 3 * (size_t)b : sp + 3 * (size_t)(b - M);
         e = make_float4(y[0], y[1], y[2], (b < M ? prad[b] : srad[b - M]) + a.probe);
         const float grow = (rlmax + 2.f * rcmax + e.w) * SA_WIDE + 0.1f;
-        c = e.x >= lox - grow && e.x <= hix + grow && e.y >= loy - grow && e.y <= hiy + grow && e.z >= loz - grow && e.z <= hiz + grow;
+        c = box.touches(e.x, e.y, e.z, grow);
       }
-      const unsigned long long bal = __ballot(c);
-      const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-      if (lane == 0) wcnt[wave] = __popcll(bal);
-      __syncthreads();
-      int off = nN, sum = 0;
-      for (int w = 0; w < SA_WAVES; ++w) {
-        off += w < wave ? wcnt[w] : 0;
-        sum += wcnt[w];
-      }
-      const bool fits = nN + sum <= a.cap;                  // uniform
+      int slot, sum;
+      block_compact(c, nN, wcnt, lane, wave, slot, sum);
+      const bool fits = nN + sum <= a.cap;                  // uniform; a tile that does not fit ends the list: memory from here on
       if (fits && c) {
-        nl[off + pre] = e;
-        nidx[off + pre] = b;
+        nl[slot] = e;
+        nidx[slot] = b;
       }
       __syncthreads();                                      // the entries complete; wcnt is rewritten by the next tile
       if (!fits) {
@@ -312,15 +285,7 @@ __global__ __launch_bounds__(SA_THREADS) void k_sasa(SaArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-static int sa_err(const std::string& s) {
-  dbfr_set_error("dbfr_sasa: " + s);
-  return DBFR_ERR_ARG;
-}
-
-static int sa_limit_err(const char* what, int got, int lo, int lim) {
-  return sa_err(std::string(what) + " " + std::to_string(got) + " outside [" + std::to_string(lo) + ", " + std::to_string(lim) +
-                "]: groups beyond it are not supported");
-}
+static int sa_err(const std::string& s) { return arg_err("dbfr_sasa", s); }
 
 // the host copies of the index arrays, when the caller has them: every count, column, radius, weight and unit vector
 static int sa_validate(const dbfr_sasa_in& d, const dbfr_sasa_in& h) {
@@ -329,7 +294,8 @@ static int sa_validate(const dbfr_sasa_in& d, const dbfr_sasa_in& h) {
       (d.static_ptr && (!h.static_ptr || !h.static_rad || !h.static_w || !h.static_col || !h.static_polar)))
     return sa_err("host: a host copy of an index array is missing");
   const int G = d.n_group;
-  if (h.frame_ptr[0] != 0 || h.frame_ptr[G] != d.n_frame) return sa_err("frame_ptr does not run from 0 to n_frame");
+  const char* fn = "dbfr_sasa";
+  if (const int rc = frame_ptr_err(fn, h.frame_ptr, G, d.n_frame)) return rc;
   for (int k = 0; k < d.n_points; ++k) {
     const double x = h.points[3 * k], y = h.points[3 * k + 1], z = h.points[3 * k + 2];
     if (!(std::fabs(std::sqrt(x * x + y * y + z * z) - 1.0) <= 1e-4)) return sa_err("point " + std::to_string(k) + " is no unit vector");
@@ -339,23 +305,22 @@ static int sa_validate(const dbfr_sasa_in& d, const dbfr_sasa_in& h) {
     const std::string where = "group " + std::to_string(g) + ": ";
     const int n0 = h.lig_ptr[g], NL = h.lig_ptr[g + 1] - n0, m0 = h.pocket_ptr[g], M = h.pocket_ptr[g + 1] - m0,
               s0 = d.static_ptr ? h.static_ptr[g] : 0, S = d.static_ptr ? h.static_ptr[g + 1] - s0 : 0, NR = h.res_ptr[g + 1] - h.res_ptr[g];
-    if (h.frame_ptr[g + 1] < h.frame_ptr[g] || NL < 0 || M < 0 || S < 0 || NR < 0) return sa_err(where + "a negative count");
-    if (NL > d.max_lig) return sa_err(where + std::to_string(NL) + " ligand atoms, max_lig says " + std::to_string(d.max_lig));
-    if (M > d.max_pocket) return sa_err(where + std::to_string(M) + " pocket atoms, max_pocket says " + std::to_string(d.max_pocket));
-    if (NR > d.max_res) return sa_err(where + std::to_string(NR) + " residue columns, max_res says " + std::to_string(d.max_res));
+    if (const int rc = group_counts_err(fn, where, {{h.frame_ptr[g + 1] - h.frame_ptr[g]}, {NL, "ligand atoms", "max_lig", d.max_lig},
+                                                    {M, "pocket atoms", "max_pocket", d.max_pocket}, {S},
+                                                    {NR, "residue columns", "max_res", d.max_res}}))
+      return rc;
     for (int i = 0; i < NL; ++i) {
       if (!(h.lig_rad[n0 + i] > 0.f && h.lig_rad[n0 + i] <= 4.f)) return sa_err(where + "the radius of ligand atom " + std::to_string(i) + " lies outside (0, 4]");
       if (!weight_ok(h.lig_w[n0 + i]))
         return sa_err(where + "the weight of ligand atom " + std::to_string(i) + " is not positive or n_points * weight exceeds 2^21");
     }
-    for (int b = 0; b < M + S; ++b) {
-      const float r = b < M ? h.pocket_rad[m0 + b] : h.static_rad[s0 + b - M];
-      const int w = b < M ? h.pocket_w[m0 + b] : h.static_w[s0 + b - M];
-      const int col = b < M ? h.pocket_col[m0 + b] : h.static_col[s0 + b - M];
-      if (!(r > 0.f && r <= 4.f)) return sa_err(where + "the radius of receptor atom " + std::to_string(b) + " lies outside (0, 4]");
-      if (!weight_ok(w)) return sa_err(where + "the weight of receptor atom " + std::to_string(b) + " is not positive or n_points * weight exceeds 2^21");
-      if (col < 0 || col >= NR) return sa_err(where + "the residue column of receptor atom " + std::to_string(b) + " is out of range");
-    }
+    auto weight_err = [&](int b) {
+      return weight_ok(b < M ? h.pocket_w[m0 + b] : h.static_w[s0 + b - M]) ? DBFR_OK
+          : sa_err(where + "the weight of receptor atom " + std::to_string(b) + " is not positive or n_points * weight exceeds 2^21");
+    };
+    if (const int rc = receptor_atoms_err(fn, where, M, S, h.pocket_rad + m0, d.static_ptr ? h.static_rad + s0 : nullptr, h.pocket_col + m0,
+                                          d.static_ptr ? h.static_col + s0 : nullptr, NR, weight_err))
+      return rc;
   }
   return DBFR_OK;
 }
@@ -363,11 +328,11 @@ static int sa_validate(const dbfr_sasa_in& d, const dbfr_sasa_in& h) {
 extern "C" int dbfr_sasa(const dbfr_sasa_in* in, const dbfr_sasa_opts* opts, const dbfr_sasa_out* out, void* hip_stream) {
   if (!in || !out) return sa_err("null argument");
   if (in->n_group < 0 || in->n_frame < 0) return sa_err("negative n_group / n_frame");
-  if (in->max_lig < 0 || in->max_lig > SA_MAX_LIG) return sa_limit_err("max_lig (ligand atoms)", in->max_lig, 0, SA_MAX_LIG);
-  if (in->max_pocket < 0 || in->max_pocket > SA_MAX_POCKET) return sa_limit_err("max_pocket (pocket atoms)", in->max_pocket, 0, SA_MAX_POCKET);
-  if (in->max_res < 0 || in->max_res > SA_MAX_RES) return sa_limit_err("max_res (residue columns)", in->max_res, 0, SA_MAX_RES);
+  if (in->max_lig < 0 || in->max_lig > SA_MAX_LIG) return limit_err("dbfr_sasa", "max_lig (ligand atoms)", in->max_lig, 0, SA_MAX_LIG);
+  if (in->max_pocket < 0 || in->max_pocket > SA_MAX_POCKET) return limit_err("dbfr_sasa", "max_pocket (pocket atoms)", in->max_pocket, 0, SA_MAX_POCKET);
+  if (in->max_res < 0 || in->max_res > SA_MAX_RES) return limit_err("dbfr_sasa", "max_res (residue columns)", in->max_res, 0, SA_MAX_RES);
   if (in->cand_cap != 0 && (in->cand_cap < SA_THREADS || in->cand_cap > SA_CAND_MAX))
-    return sa_limit_err("cand_cap (receptor atoms kept in LDS)", in->cand_cap, SA_THREADS, SA_CAND_MAX);
+    return limit_err("dbfr_sasa", "cand_cap (receptor atoms kept in LDS)", in->cand_cap, SA_THREADS, SA_CAND_MAX);
   if (in->n_points < 64 || in->n_points > SA_MAX_POINTS || in->n_points % 64 != 0)
     return sa_err("n_points " + std::to_string(in->n_points) + " must be a multiple of 64 in [64, 512]");
   dbfr_sasa_opts o = {1.4f};
@@ -393,9 +358,6 @@ extern "C" int dbfr_sasa(const dbfr_sasa_in* in, const dbfr_sasa_opts* opts, con
   a.probe = o.probe;
   a.cap = in->cand_cap ? in->cand_cap : SA_CAND;
   const size_t lds = 20 * (size_t)a.cap + 4 * (size_t)in->max_res + 16;
-  if (lds > 32 * 1024)
-    HIPCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sasa), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(k_sasa, dim3((unsigned)in->n_frame), dim3(SA_THREADS), lds, (hipStream_t)hip_stream, a);
-  HIPCHECK(hipGetLastError());
+  HIPCHECK(launch_frames(k_sasa, in->n_frame, SA_THREADS, lds, hip_stream, a));
   return DBFR_OK;
 }

@@ -57,12 +57,11 @@ project's rules, RDKit's perception may differ):
 There is no CPU path: CPU tensors raise ``DbfrError``.  Limits: 256 ligand atoms, 32 ligand rings plus charge centres and
 16 384 residues per complex; a frame with a non-finite or |x| > 1e4 A coordinate gets counts of -1 and an all-zero row.
 """
-import ctypes as C
 
 import numpy as np
 import torch
 
-from . import lib as L
+from . import frames as fb, lib as L
 from .lib import DbfrError, InteractionsIn, InteractionsOpts, InteractionsOut
 from .vina import _tables, ligand_types, parse_molblock, receptor_type_table
 
@@ -300,19 +299,12 @@ def ligand_features(molblock):
 
 # ------------------------------------------------------------------------------------------------ device call
 def _opts(**opts):
-    bad = set(opts) - set(DEFAULTS)
-    if bad:
-        raise DbfrError(f"unknown interaction options {sorted(bad)} (known: {sorted(DEFAULTS)})")
-    o = {**DEFAULTS, **opts}
+    o = fb.check_opts(opts, DEFAULTS, "interaction")
     for k, v in o.items():
         hi = 180.0 if k in _ANGLES else 100.0
         if not 0.0 <= float(v) <= hi:            # NaN fails too
             raise DbfrError(f"{k} must lie in [0, {hi:g}] and must not be NaN")
     return InteractionsOpts(*[float(o[k]) for k in DEFAULTS])
-
-
-def _ptr(counts, dev, dtype=np.int32):
-    return torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(dtype), device=dev)
 
 
 def fingerprint_launcher(groups, **opts):
@@ -322,20 +314,14 @@ def fingerprint_launcher(groups, **opts):
     o = _opts(**opts)
     if not groups:
         raise DbfrError("no groups to fingerprint")
-    dev = groups[0]["lig"].device if torch.is_tensor(groups[0]["lig"]) else torch.device("cpu")
-    if dev.type != "cuda":
-        raise DbfrError("the interaction fingerprints run on the GPU only (no CPU path): the poses are on " + str(dev))
+    dev = fb.device_of(groups[0]["lig"], "the interaction fingerprints run on the GPU only (no CPU path): the poses are on ")
     G = len(groups)
     lig, pocket, ltype, lnbr, lgrp, pmeta, stat, smeta, rgrp = ([] for _ in range(9))
     F, N, M, S, NR = (np.zeros(G, np.int64) for _ in range(5))
     for g, gr in enumerate(groups):
-        x, ft = gr["lig"], gr["feat"]
-        if not torch.is_tensor(x) or x.device != dev or (gr.get("pocket") is not None and
-                                                         (not torch.is_tensor(gr["pocket"]) or gr["pocket"].device != dev)):
-            raise DbfrError(f"group {g}: poses and pocket atoms must be device tensors on {dev} (no CPU path)")
-        if x.dim() != 3 or x.shape[2] != 3 or x.shape[1] < 1:
-            raise DbfrError(f"group {g}: ligand poses must be [F, N >= 1, 3]")
-        F[g], N[g] = x.shape[0], x.shape[1]
+        ft = gr["feat"]
+        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
+        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N >= 1, 3]", min_atoms=1)
         if N[g] > MAX_LIG:
             raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
         lt = np.asarray(ft["types"], np.int8).reshape(-1)
@@ -349,12 +335,7 @@ def fingerprint_launcher(groups, **opts):
             raise DbfrError(f"group {g}: a ligand neighbour or group atom index lies outside its {N[g]} atoms")
         if lg.size and ((lg[:, 0] < 0).any() or (lg[:, 0] > 2).any() or (lg[:, 1] < 0).any()):
             raise DbfrError(f"group {g}: a ligand group needs a kind in 0..2 and at least one atom")
-        p = gr.get("pocket")
-        if p is None:
-            p = torch.zeros(int(F[g]), 0, 3, device=dev)
-        if p.dim() != 3 or p.shape[0] != F[g] or p.shape[2] != 3:
-            raise DbfrError(f"group {g}: pocket atoms must be [F, M, 3] with the frames of the poses")
-        M[g] = p.shape[1]
+        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
         pm = np.asarray(gr.get("pocket_meta", np.zeros((0, 4))), np.int32).reshape(-1, 4)
         st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
         sm = np.asarray(gr.get("static_meta", np.zeros((0, 4))), np.int32).reshape(-1, 4)
@@ -373,36 +354,26 @@ def fingerprint_launcher(groups, **opts):
                 raise DbfrError(f"group {g}: a {name} names a residue outside its {NR[g]} or an atom outside its {MR}")
         if rg.size and ((rg[:, 0] & 255) > 2).any():
             raise DbfrError(f"group {g}: a receptor group needs a kind in 0..2")
-        lig.append(x.detach().reshape(-1).to(torch.float32))
-        pocket.append(p.detach().reshape(-1).to(torch.float32))
+        lig.append(x), pocket.append(p)
         ltype.append(lt), lnbr.append(ln), lgrp.append(lg), pmeta.append(pm), stat.append(st), smeta.append(sm), rgrp.append(rg)
-    zf = torch.zeros(1, device=dev)
-    cat = lambda xs, dt, w: torch.as_tensor(np.concatenate([np.asarray(a, dt).reshape(-1) for a in xs] + [np.zeros(w, dt)]), device=dev)
-    t = dict(frame_ptr=_ptr(F, dev), lig_ptr=_ptr(N, dev), lig_pos_off=_ptr(F * N, dev, np.int64)[:-1].contiguous(),
-             lig_pos=torch.cat(lig + [zf]), lig_type=cat(ltype, np.int8, 1), lig_nbr=cat(lnbr, np.int32, 3),
-             lgrp_ptr=_ptr([len(a) for a in lgrp], dev), lgrp=cat(lgrp, np.int32, 8),
-             pocket_ptr=_ptr(M, dev), pocket_pos_off=_ptr(F * M, dev, np.int64)[:-1].contiguous(),
-             pocket_pos=torch.cat(pocket + [zf]), pocket_meta=cat(pmeta, np.int32, 4),
-             static_ptr=_ptr(S, dev), static_pos=cat(stat, np.float32, 3), static_meta=cat(smeta, np.int32, 4),
-             rgrp_ptr=_ptr([len(a) for a in rgrp], dev), rgrp=cat(rgrp, np.int32, 8),
-             res_ptr=_ptr(NR, dev), bits_off=_ptr(F * NR, dev, np.int64)[:-1].contiguous())
+    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
+    ptr, cat = fb.ptr, fb.cat
+    host = dict(frame_ptr=ptr(F), lig_ptr=ptr(N), lig_pos_off=lig_off, lig_type=cat(ltype, np.int8, 1), lig_nbr=cat(lnbr, np.int32, 3),
+                lgrp_ptr=ptr([len(a) for a in lgrp]), lgrp=cat(lgrp, np.int32, 8), pocket_ptr=ptr(M), pocket_pos_off=pocket_off,
+                pocket_meta=cat(pmeta, np.int32, 4), static_ptr=ptr(S), static_pos=cat(stat, np.float32, 3),
+                static_meta=cat(smeta, np.int32, 4), rgrp_ptr=ptr([len(a) for a in rgrp]), rgrp=cat(rgrp, np.int32, 8), res_ptr=ptr(NR),
+                bits_off=ptr(F * NR, np.int64)[:-1].copy())
+    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
+    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
     n_frame, n_bits = int(F.sum()), int((F * NR).sum())
     bits = torch.zeros(n_bits + 1, dtype=torch.int16, device=dev)
     counts = torch.zeros(n_frame + 1, 10, dtype=torch.int32, device=dev)
     mx = lambda a: int(max(a)) if len(a) else 0
-    cin = InteractionsIn(G, n_frame, *[t[k].data_ptr() for k in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_type", "lig_nbr",
-                                                                 "lgrp_ptr", "lgrp", "pocket_ptr", "pocket_pos_off", "pocket_pos",
-                                                                 "pocket_meta", "static_ptr", "static_pos", "static_meta", "rgrp_ptr",
-                                                                 "rgrp", "res_ptr", "bits_off")],
-                         mx(N), mx([len(a) for a in lgrp]), mx(NR))
+    order = ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_type", "lig_nbr", "lgrp_ptr", "lgrp", "pocket_ptr", "pocket_pos_off",
+             "pocket_pos", "pocket_meta", "static_ptr", "static_pos", "static_meta", "rgrp_ptr", "rgrp", "res_ptr", "bits_off")
     cout = InteractionsOut(bits.data_ptr(), counts.data_ptr())
-
-    def launch(_staged=t):                # (the staged tensors live as long as the closure)
-        with torch.cuda.device(dev):
-            L.check(lib.dbfr_interactions(C.byref(cin), C.byref(o), C.byref(cout),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-
-    off = np.concatenate([[0], np.cumsum(F * NR)])
+    launch = fb.launcher(lib.dbfr_interactions, InteractionsIn, (G, n_frame), order, (mx(N), mx([len(a) for a in lgrp]), mx(NR)), t, dev, o, cout)
+    off = ptr(F * NR, np.int64)
     rows = [bits[off[g]:off[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)]
     return launch, rows, counts[:n_frame]
 
@@ -551,9 +522,7 @@ def fingerprint_entries(entries, poses=None, reference=None, **opts):
         return [], np.zeros((0, len(KINDS)), np.int64), []
     bits, counts = fingerprint(groups, **opts)
     words = [b.cpu().numpy() for b in bits]
-    first = np.concatenate([[0], np.cumsum([p + extra for p in n_pose])])
-    keep = np.concatenate([np.arange(first[k], first[k] + n_pose[k]) for k in range(len(entries))]).astype(np.int64)
-    cnt = counts.cpu().numpy().astype(np.int64)[keep]
+    cnt = counts.cpu().numpy().astype(np.int64)[fb.frame_rows(n_pose, extra)[1]]
     return [w[:p] for w, p in zip(words, n_pose)], cnt, [w[p] if extra else None for w, p in zip(words, n_pose)]
 
 
@@ -575,11 +544,9 @@ def annotate(entries, pd_df, poses=None, reference=None, **opts):
     df = pd_df.copy()
     for q, kind in enumerate(KINDS):
         df[f"ifp_n_{kind.lower()}"] = cnt[:, q]
-    tags, contacts = {}, []
-    for e, w in zip(entries, words):                   # (entries often share a topology: its residue tags are made once)
-        if id(e.topology) not in tags:
-            tags[id(e.topology)] = residue_tags(e.topology)
-        contacts += contact_names(w, e.topology, tags[id(e.topology)])
+    contacts = []
+    for e, w, tags in zip(entries, words, fb.residue_tag_cache(entries)):
+        contacts += contact_names(w, e.topology, tags)
     df["ifp_contacts"] = contacts
     if reference is not None:
         sims = [similarity(w, r) for w, r in zip(words, refs)]

@@ -37,13 +37,12 @@ and static-static pairs (they cannot change); ligand-protein pairs (``posecheck`
 There is no CPU path: CPU tensors raise ``DbfrError``.  Limits: 8 192 pocket atoms, 16 384 residue columns, exclusion lists
 (the atoms within 3 bonds of a movable atom) of at most 32 atoms.
 """
-import ctypes as C
 from collections import deque
 
 import numpy as np
 import torch
 
-from . import lib as L
+from . import frames as fb, lib as L
 from .lib import DbfrError, PocketCheckIn, PocketCheckOpts, PocketCheckOut
 
 DEFAULTS = dict(clash_ratio=0.75, bond_tol=0.3, max_clashes=0)
@@ -161,10 +160,7 @@ def receptor_topology(aatype, pocket_atoms, static_atoms, input_pos, res=None):
 
 # ------------------------------------------------------------------------------------------------ device call
 def _opts(**opts):
-    bad = set(opts) - set(DEFAULTS)
-    if bad:
-        raise DbfrError(f"unknown pocket-check options {sorted(bad)} (known: {sorted(DEFAULTS)})")
-    o = {**DEFAULTS, **opts}
+    o = fb.check_opts(opts, DEFAULTS, "pocket-check")
     if not 0.0 < float(o["clash_ratio"]) <= 10.0:            # NaN fails too
         raise DbfrError("clash_ratio must lie in (0, 10] and must not be NaN")
     if not 0.0 <= float(o["bond_tol"]) <= 100.0:
@@ -174,10 +170,6 @@ def _opts(**opts):
     return PocketCheckOpts(float(o["clash_ratio"]), float(o["bond_tol"]), int(o["max_clashes"]))
 
 
-def _ptr(counts, dtype=np.int32):
-    return np.concatenate([[0], np.cumsum(counts)]).astype(dtype)
-
-
 def check_launcher(groups, cand_cap=0, **opts):
     """The launch of ``check`` prepared once: (launch() -> None, dict of outputs as ``check`` returns them).  Every launch()
     recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
@@ -185,21 +177,15 @@ def check_launcher(groups, cand_cap=0, **opts):
     o = _opts(**opts)
     if not groups:
         raise DbfrError("no groups to check")
-    dev = groups[0]["pocket"].device if torch.is_tensor(groups[0].get("pocket")) else torch.device("cpu")
-    if dev.type != "cuda":
-        raise DbfrError("the pocket checks run on the GPU only (no CPU path): the pocket atoms are on " + str(dev))
+    dev = fb.device_of(groups[0].get("pocket"), "the pocket checks run on the GPU only (no CPU path): the pocket atoms are on ")
     G = len(groups)
     F, M, S, NMOV, NC, NR = (np.zeros(G, np.int64) for _ in range(6))
-    pocket, cols = [], {k: [] for k in ("pocket_rad", "pocket_col", "pocket_rank", "static", "static_rad", "static_col", "mov_atom",
-                                        "excl", "closure", "closure_len")}
+    pocket, cols = [], {k: [] for k in ("pocket_rad", "pocket_col", "pocket_rank", "static", "static_rad", "static_col", "mov_atom", "excl",
+                            "closure", "closure_len")}
     excl_len = []
     for g, gr in enumerate(groups):
-        p = gr["pocket"]
-        if not torch.is_tensor(p) or p.device != dev:
-            raise DbfrError(f"group {g}: pocket atoms must be a device tensor on {dev} (no CPU path)")
-        if p.dim() != 3 or p.shape[2] != 3:
-            raise DbfrError(f"group {g}: pocket atoms must be [F, M, 3]")
-        F[g], M[g] = p.shape[0], p.shape[1]
+        fb.on_device(g, dev, "pocket atoms must be a device tensor", gr["pocket"])
+        p, F[g], M[g] = fb.pose_rows(gr["pocket"], g, dev, "pocket atoms must be [F, M, 3]")
         if M[g] > MAX_POCKET:
             raise DbfrError(f"group {g}: {M[g]} pocket atoms, at most {MAX_POCKET}")
         st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
@@ -220,27 +206,24 @@ def check_launcher(groups, cand_cap=0, **opts):
             raise DbfrError(f"group {g}: one input length per closure bond")
         if not 0 <= NR[g] <= MAX_RES:
             raise DbfrError(f"group {g}: {NR[g]} residue columns, at most {MAX_RES}")
-        pocket.append(p.detach().reshape(-1).to(torch.float32))
+        pocket.append(p)
         excl_len.append(np.diff(ep))
         for k in a:
             cols[k].append(a[k])
         cols["static"].append(st)
         cols["closure"].append(cl)
-    cat = lambda xs, dt, w: np.concatenate([np.asarray(x, dt).reshape(-1) for x in xs] + [np.zeros(w, dt)])
+    pocket_pos, pocket_off = fb.pose_block(pocket, F, M, dev)
+    cat = fb.cat
     all_len = np.concatenate(excl_len) if excl_len else np.zeros(0, np.int64)
-    host = dict(frame_ptr=_ptr(F), pocket_ptr=_ptr(M), pocket_pos_off=_ptr(F * M, np.int64)[:-1].copy(),
+    host = dict(frame_ptr=fb.ptr(F), pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off,
                 pocket_rad=cat(cols["pocket_rad"], np.float32, 1), pocket_col=cat(cols["pocket_col"], np.int32, 1),
-                pocket_rank=cat(cols["pocket_rank"], np.int32, 1), static_ptr=_ptr(S), static_pos=cat(cols["static"], np.float32, 3),
+                pocket_rank=cat(cols["pocket_rank"], np.int32, 1), static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3),
                 static_rad=cat(cols["static_rad"], np.float32, 1), static_col=cat(cols["static_col"], np.int32, 1),
-                mov_ptr=_ptr(NMOV), mov_atom=cat(cols["mov_atom"], np.int32, 1), excl_ptr=np.append(_ptr(all_len), 0).astype(np.int32),
-                excl=cat(cols["excl"], np.int32, 1), closure_ptr=_ptr(NC), closure_ab=cat(cols["closure"], np.int32, 2),
-                closure_len=cat(cols["closure_len"], np.float32, 1), res_ptr=_ptr(NR), res_off=_ptr(F * NR, np.int64)[:-1].copy())
-    if G == 0 or host["pocket_pos_off"].size == 0:
-        host["pocket_pos_off"] = np.zeros(1, np.int64)
-    if host["res_off"].size == 0:
-        host["res_off"] = np.zeros(1, np.int64)
+                mov_ptr=fb.ptr(NMOV), mov_atom=cat(cols["mov_atom"], np.int32, 1), excl_ptr=np.append(fb.ptr(all_len), 0).astype(np.int32),
+                excl=cat(cols["excl"], np.int32, 1), closure_ptr=fb.ptr(NC), closure_ab=cat(cols["closure"], np.int32, 2),
+                closure_len=cat(cols["closure_len"], np.float32, 1), res_ptr=fb.ptr(NR), res_off=fb.ptr(F * NR, np.int64)[:-1].copy())
     t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["pocket_pos"] = torch.cat(pocket + [torch.zeros(1, device=dev)])
+    t["pocket_pos"] = pocket_pos
     n_frame, n_row = int(F.sum()), int((F * NR).sum())
     out = dict(n_clash=torch.zeros(n_frame + 1, 3, dtype=torch.int32, device=dev),
                min_ratio=torch.zeros(n_frame + 1, dtype=torch.float32, device=dev),
@@ -254,18 +237,10 @@ def check_launcher(groups, cand_cap=0, **opts):
              "closure_len", "res_ptr", "res_off")
     mx = lambda a: int(max(a)) if len(a) else 0
     maxima = (mx(M), mx(all_len), mx(NR), int(cand_cap))
-    hin = PocketCheckIn(G, n_frame, *[host[k].ctypes.data if k in host else None for k in order], *maxima, None)
-    cin = PocketCheckIn(G, n_frame, *[t[k].data_ptr() for k in order], *maxima, C.addressof(hin))
     cout = PocketCheckOut(*[out[k].data_ptr() for k in ("n_clash", "min_ratio", "worst_pair", "res_clash", "n_broken", "max_bond_dev",
                                                        "passed")])
-
-    def launch(_staged=(t, host, hin)):   # (the staged tensors and the host copies live as long as the closure)
-        with torch.cuda.device(dev):
-            L.check(lib.dbfr_pocket_check(C.byref(cin), C.byref(o), C.byref(cout),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        cin.host = None                   # validated once: later launches of the same staged inputs skip the host walk
-
-    off = np.concatenate([[0], np.cumsum(F * NR)])
+    launch = fb.launcher(lib.dbfr_pocket_check, PocketCheckIn, (G, n_frame), order, maxima, t, dev, o, cout, host)
+    off = fb.ptr(F * NR, np.int64)
     res = {k: v[:n_frame] for k, v in out.items() if k != "res_clash"}
     res["res_clash"] = [out["res_clash"][off[g]:off[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)]
     return launch, res
@@ -352,8 +327,7 @@ def check_entries(entries, frames=None, baseline=False, **opts):
     r = check(groups, **opts)
     rows = [x.cpu().numpy() for x in r.pop("res_clash")]
     host = {k: v.cpu().numpy() for k, v in r.items()}
-    first = np.concatenate([[0], np.cumsum([n + extra for n in n_frame])])
-    keep = np.concatenate([np.arange(first[k], first[k] + n_frame[k]) for k in range(len(entries))]).astype(np.int64)
+    first, keep = fb.frame_rows(n_frame, extra)
     out = {k: v[keep] for k, v in host.items()}
     out["res_clash"] = [w[:n] for w, n in zip(rows, n_frame)]
     base = [dict({k: v[first[k2] + n_frame[k2]] for k, v in host.items()}, res_clash=rows[k2][n_frame[k2]]) if extra else None
@@ -377,7 +351,6 @@ def annotate(entries, pd_df, baseline=True, frames=None, **opts):
     (``;``-joined residue tags), ``pk_n_broken_bonds``, ``pk_max_bond_dev``; with ``baseline`` also ``pk_n_clash_input`` (the
     clashes of the entry's input structure) and ``pk_new_clash_residues`` (the residues that clash in the pose and not in the
     input).  ``frames`` / ``opts``: see ``check_entries`` / ``check``."""
-    from .interactions import residue_tags
     n_pose = [int(e.protein_traj.shape[0]) if frames is None else int(len(frames[k])) for k, e in enumerate(entries)]
     if sum(n_pose) != len(pd_df):
         raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
@@ -393,11 +366,8 @@ def annotate(entries, pd_df, baseline=True, frames=None, **opts):
         df[f"pk_n_clash_{cat}"] = nc[:, q]
     df["pk_min_ratio"] = r["min_ratio"].astype(np.float64)
     worst, clashing, fresh, n_input = [], [], [], []
-    tag_cache, i = {}, 0
-    for e, topo, rows, b in zip(entries, topos, r["res_clash"], base):
-        if id(e.topology) not in tag_cache:
-            tag_cache[id(e.topology)] = residue_tags(e.topology)
-        tags = tag_cache[id(e.topology)]
+    i = 0
+    for e, tags, topo, rows, b in zip(entries, fb.residue_tag_cache(entries), topos, r["res_clash"], base):
         atoms = atom_tags(e, topo, tags)
         for f in range(rows.shape[0]):
             a, c = (int(v) for v in r["worst_pair"][i])

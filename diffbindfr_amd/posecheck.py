@@ -35,14 +35,13 @@ field) or the cofactor and water checks (the pipeline carries neither).
 
 There is no CPU path: CPU tensors raise ``DbfrError``.  Limits: 256 ligand atoms, 64 flatness and 64 stereo bonds per ligand.
 """
-import ctypes as C
 import warnings
 from collections import deque
 
 import numpy as np
 import torch
 
-from . import lib as L
+from . import frames as fb, lib as L
 from .lib import DbfrError, PoseCheckIn, PoseCheckOpts, PoseCheckOut
 
 RADII = {"H": 1.20, "C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "P": 1.80, "S": 1.80, "Cl": 1.75, "Br": 1.85, "I": 1.98}
@@ -187,10 +186,7 @@ def ligand_chemistry(molblock, ref_pos=None):
 
 # ------------------------------------------------------------------------------------------------ device call
 def _opts(**opts):
-    bad = set(opts) - set(DEFAULTS)
-    if bad:
-        raise DbfrError(f"unknown pose-check options {sorted(bad)} (known: {sorted(DEFAULTS)})")
-    o = {**DEFAULTS, **opts}
+    o = fb.check_opts(opts, DEFAULTS, "pose-check")
     if not 0.05 <= o["grid"] <= 1.0:
         raise DbfrError("grid must lie in [0.05, 1] A")
     if not 0 < o["vol_scale"] <= 2.0:
@@ -200,10 +196,6 @@ def _opts(**opts):
     return PoseCheckOpts(*[float(o[k]) for k in DEFAULTS])
 
 
-def _ptr(counts, dev, dtype=np.int32):
-    return torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(dtype), device=dev)
-
-
 def check_launcher(groups, cand_cap=0, **opts):
     """The launch of ``check`` prepared once: (launch() -> None, dict of per-frame output tensors).  Every launch() recomputes
     the outputs from the staged inputs on the current stream (benchmarks)."""
@@ -211,28 +203,17 @@ def check_launcher(groups, cand_cap=0, **opts):
     o = _opts(**opts)
     if not groups:
         raise DbfrError("no groups to check")
-    dev = groups[0]["lig"].device if torch.is_tensor(groups[0]["lig"]) else torch.device("cpu")
-    if dev.type != "cuda":
-        raise DbfrError("the pose checks run on the GPU only (no CPU path): the poses are on " + str(dev))
+    dev = fb.device_of(groups[0]["lig"], "the pose checks run on the GPU only (no CPU path): the poses are on ")
     G = len(groups)
     lig, pocket, lrad, prad, stat, srad, pairs, flat, stereo, sign = [], [], [], [], [], [], [], [], [], []
     F, N, M, S = (np.zeros(G, np.int64) for _ in range(4))
     for g, gr in enumerate(groups):
-        x, ch = gr["lig"], gr["chem"]
-        if not torch.is_tensor(x) or x.device != dev or (gr.get("pocket") is not None and
-                                                         (not torch.is_tensor(gr["pocket"]) or gr["pocket"].device != dev)):
-            raise DbfrError(f"group {g}: poses and pocket atoms must be device tensors on {dev} (no CPU path)")
-        if x.dim() != 3 or x.shape[2] != 3:
-            raise DbfrError(f"group {g}: ligand poses must be [F, N, 3]")
-        F[g], N[g] = x.shape[0], x.shape[1]
+        ch = gr["chem"]
+        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
+        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3]")
         if len(ch["radii"]) != N[g]:
             raise DbfrError(f"group {g}: {len(ch['radii'])} ligand radii for {N[g]} atoms")
-        p = gr.get("pocket")
-        if p is None:
-            p = torch.zeros(int(F[g]), 0, 3, device=dev)
-        if p.dim() != 3 or p.shape[0] != F[g] or p.shape[2] != 3:
-            raise DbfrError(f"group {g}: pocket atoms must be [F, M, 3] with the frames of the poses")
-        M[g] = p.shape[1]
+        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
         pr = np.asarray(gr.get("pocket_rad", np.zeros(0)), np.float32).reshape(-1)
         if pr.size != M[g]:
             raise DbfrError(f"group {g}: {pr.size} pocket radii for {M[g]} pocket atoms")
@@ -252,37 +233,28 @@ def check_launcher(groups, cand_cap=0, **opts):
             raise DbfrError(f"group {g}: a flatness bond needs its two atoms and at least 4 atoms in all")
         if sg.size != sq.shape[0] or not np.isin(sg, (-1, 1)).all():
             raise DbfrError(f"group {g}: one input sign (+1 / -1) per stereo bond")
-        lig.append(x.detach().reshape(-1).to(torch.float32))
-        pocket.append(p.detach().reshape(-1).to(torch.float32))
+        lig.append(x), pocket.append(p)
         lrad.append(np.asarray(ch["radii"], np.float32))
         prad.append(pr), stat.append(st), srad.append(sr)
         pairs.append(pq), flat.append(fl), stereo.append(sq), sign.append(sg)
-    zf = torch.zeros(1, device=dev)
-    cat = lambda xs, dt, w: torch.as_tensor(np.concatenate([np.asarray(a, dt).reshape(-1) for a in xs] + [np.zeros(w, dt)]), device=dev)
-    t = dict(frame_ptr=_ptr(F, dev), lig_ptr=_ptr(N, dev), lig_pos_off=_ptr(F * N, dev, np.int64)[:-1].contiguous(),
-             lig_pos=torch.cat(lig + [zf]), lig_rad=cat(lrad, np.float32, 1),
-             pocket_ptr=_ptr(M, dev), pocket_pos_off=_ptr(F * M, dev, np.int64)[:-1].contiguous(),
-             pocket_pos=torch.cat(pocket + [zf]), pocket_rad=cat(prad, np.float32, 1),
-             static_ptr=_ptr(S, dev), static_pos=cat(stat, np.float32, 3), static_rad=cat(srad, np.float32, 1),
-             pair_ptr=_ptr([len(p) for p in pairs], dev), pair_ij=cat(pairs, np.int32, 2),
-             flat_ptr=_ptr([len(p) for p in flat], dev), flat_atoms=cat(flat, np.int32, FLAT_WIDTH),
-             stereo_ptr=_ptr([len(p) for p in stereo], dev), stereo_atoms=cat(stereo, np.int32, 4),
-             stereo_sign=cat(sign, np.int8, 1))
+    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
+    ptr, cat = fb.ptr, fb.cat
+    host = dict(frame_ptr=ptr(F), lig_ptr=ptr(N), lig_pos_off=lig_off, lig_rad=cat(lrad, np.float32, 1), pocket_ptr=ptr(M),
+                pocket_pos_off=pocket_off, pocket_rad=cat(prad, np.float32, 1), static_ptr=ptr(S), static_pos=cat(stat, np.float32, 3),
+                static_rad=cat(srad, np.float32, 1), pair_ptr=ptr([len(p) for p in pairs]), pair_ij=cat(pairs, np.int32, 2),
+                flat_ptr=ptr([len(p) for p in flat]), flat_atoms=cat(flat, np.int32, FLAT_WIDTH),
+                stereo_ptr=ptr([len(p) for p in stereo]), stereo_atoms=cat(stereo, np.int32, 4), stereo_sign=cat(sign, np.int8, 1))
+    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
+    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
     n_frame = int(F.sum())
     out = {k: torch.empty(n_frame + 1, dtype=torch.int32 if k in _INT_OUTPUTS else torch.float32, device=dev) for k in OUTPUTS}
     mx = lambda a: int(max(a)) if len(a) else 0
-    cin = PoseCheckIn(G, n_frame, *[t[k].data_ptr() for k in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "pocket_ptr",
-                                                              "pocket_pos_off", "pocket_pos", "pocket_rad", "static_ptr", "static_pos",
-                                                              "static_rad", "pair_ptr", "pair_ij", "flat_ptr", "flat_atoms",
-                                                              "stereo_ptr", "stereo_atoms", "stereo_sign")],
-                      mx(N), mx([len(p) for p in pairs]), mx([len(p) for p in flat]), mx([len(p) for p in stereo]), int(cand_cap))
+    order = ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "pocket_ptr", "pocket_pos_off", "pocket_pos", "pocket_rad",
+             "static_ptr", "static_pos", "static_rad", "pair_ptr", "pair_ij", "flat_ptr", "flat_atoms", "stereo_ptr", "stereo_atoms",
+             "stereo_sign")
+    maxima = (mx(N), mx([len(p) for p in pairs]), mx([len(p) for p in flat]), mx([len(p) for p in stereo]), int(cand_cap))
     cout = PoseCheckOut(*[out[k].data_ptr() for k in OUTPUTS])
-
-    def launch(_staged=t):                # (the staged tensors live as long as the closure)
-        with torch.cuda.device(dev):
-            L.check(lib.dbfr_pose_check(C.byref(cin), C.byref(o), C.byref(cout),
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-
+    launch = fb.launcher(lib.dbfr_pose_check, PoseCheckIn, (G, n_frame), order, maxima, t, dev, o, cout)
     return launch, {k: v[:n_frame] for k, v in out.items()}
 
 

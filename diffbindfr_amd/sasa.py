@@ -29,12 +29,10 @@ A frame with a non-finite or |x| > 1e4 A coordinate gets -1 in every count and t
 There is no CPU path: CPU tensors raise ``DbfrError``.  Limits: 256 ligand atoms, 8 192 pocket atoms, 16 384 residue columns;
 static atoms are not limited.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import lib as L
+from . import frames as fb, lib as L
 from .lib import DbfrError, SasaIn, SasaOpts, SasaOut
 
 DEFAULTS = dict(probe=1.4)
@@ -67,17 +65,10 @@ def area_weights(radii, probe=DEFAULTS["probe"], n_points=N_POINTS):
 
 # ------------------------------------------------------------------------------------------------ device call
 def _opts(**opts):
-    bad = set(opts) - set(DEFAULTS)
-    if bad:
-        raise DbfrError(f"unknown surface-area options {sorted(bad)} (known: {sorted(DEFAULTS)})")
-    o = {**DEFAULTS, **opts}
+    o = fb.check_opts(opts, DEFAULTS, "surface-area")
     if not 0.0 <= float(o["probe"]) <= 2.0:                  # NaN fails too
         raise DbfrError("probe must lie in [0, 2] A and must not be NaN")
     return SasaOpts(float(o["probe"]))
-
-
-def _ptr(counts, dtype=np.int32):
-    return np.concatenate([[0], np.cumsum(counts)]).astype(dtype)
 
 
 def burial_launcher(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
@@ -87,9 +78,7 @@ def burial_launcher(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
     o = _opts(**opts)
     if not groups:
         raise DbfrError("no groups to evaluate")
-    dev = groups[0]["lig"].device if torch.is_tensor(groups[0].get("lig")) else torch.device("cpu")
-    if dev.type != "cuda":
-        raise DbfrError("the surface areas are computed on the GPU only (no CPU path): the poses are on " + str(dev))
+    dev = fb.device_of(groups[0].get("lig"), "the surface areas are computed on the GPU only (no CPU path): the poses are on ")
     pts = sphere_points(n_points) if points is None else np.ascontiguousarray(points, np.float32).reshape(-1, 3)
     n_points = int(pts.shape[0])
     G = len(groups)
@@ -98,19 +87,11 @@ def burial_launcher(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
     cols = {k: [] for k in ("lig_rad", "lig_polar", "pocket_rad", "pocket_col", "pocket_polar", "static", "static_rad", "static_col",
                             "static_polar")}
     for g, gr in enumerate(groups):
-        x, p = gr["lig"], gr.get("pocket")
-        if not torch.is_tensor(x) or x.device != dev or (p is not None and (not torch.is_tensor(p) or p.device != dev)):
-            raise DbfrError(f"group {g}: poses and pocket atoms must be device tensors on {dev} (no CPU path)")
-        if x.dim() != 3 or x.shape[2] != 3:
-            raise DbfrError(f"group {g}: ligand poses must be [F, N, 3]")
-        F[g], N[g] = x.shape[0], x.shape[1]
+        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
+        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3]")
         if N[g] > MAX_LIG:
             raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
-        if p is None:
-            p = torch.zeros(int(F[g]), 0, 3, device=dev)
-        if p.dim() != 3 or p.shape[0] != F[g] or p.shape[2] != 3:
-            raise DbfrError(f"group {g}: pocket atoms must be [F, M, 3] with the frames of the poses")
-        M[g] = p.shape[1]
+        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
         if M[g] > MAX_POCKET:
             raise DbfrError(f"group {g}: {M[g]} pocket atoms, at most {MAX_POCKET}")
         st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
@@ -127,24 +108,23 @@ def burial_launcher(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
         NR[g] = int(gr.get("n_res", 0))
         if not 0 <= NR[g] <= MAX_RES:
             raise DbfrError(f"group {g}: {NR[g]} residue columns, at most {MAX_RES}")
-        lig.append(x.detach().reshape(-1).to(torch.float32))
-        pocket.append(p.detach().reshape(-1).to(torch.float32))
+        lig.append(x), pocket.append(p)
         for k in a:
             cols[k].append(a[k])
         cols["static"].append(st)
-    cat = lambda xs, dt, w: np.concatenate([np.asarray(x, dt).reshape(-1) for x in xs] + [np.zeros(w, dt)])
-    host = dict(frame_ptr=_ptr(F), lig_ptr=_ptr(N), lig_pos_off=_ptr(F * N, np.int64)[:-1].copy(), lig_rad=cat(cols["lig_rad"], np.float32, 1),
-                lig_polar=cat(cols["lig_polar"], np.uint8, 1), pocket_ptr=_ptr(M), pocket_pos_off=_ptr(F * M, np.int64)[:-1].copy(),
+    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
+    cat = fb.cat
+    host = dict(frame_ptr=fb.ptr(F), lig_ptr=fb.ptr(N), lig_pos_off=lig_off, lig_rad=cat(cols["lig_rad"], np.float32, 1),
+                lig_polar=cat(cols["lig_polar"], np.uint8, 1), pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off,
                 pocket_rad=cat(cols["pocket_rad"], np.float32, 1), pocket_col=cat(cols["pocket_col"], np.int32, 1),
-                pocket_polar=cat(cols["pocket_polar"], np.uint8, 1), static_ptr=_ptr(S), static_pos=cat(cols["static"], np.float32, 3),
+                pocket_polar=cat(cols["pocket_polar"], np.uint8, 1), static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3),
                 static_rad=cat(cols["static_rad"], np.float32, 1), static_col=cat(cols["static_col"], np.int32, 1),
-                static_polar=cat(cols["static_polar"], np.uint8, 1), res_ptr=_ptr(NR), res_off=_ptr(F * NR, np.int64)[:-1].copy(),
+                static_polar=cat(cols["static_polar"], np.uint8, 1), res_ptr=fb.ptr(NR), res_off=fb.ptr(F * NR, np.int64)[:-1].copy(),
                 points=pts.reshape(-1))
     for k in ("lig", "pocket", "static"):
         host[k + "_w"] = area_weights(host[k + "_rad"], float(opts.get("probe", DEFAULTS["probe"])), max(n_points, 1))
     t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"] = torch.cat(lig + [torch.zeros(1, device=dev)])
-    t["pocket_pos"] = torch.cat(pocket + [torch.zeros(1, device=dev)])
+    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
     n_frame, n_lrow, n_row = int(F.sum()), int((F * N).sum()), int((F * NR).sum())
     out = dict(lig_free=torch.zeros(n_lrow + 1, dtype=torch.int32, device=dev), lig_bound=torch.zeros(n_lrow + 1, dtype=torch.int32, device=dev),
                res_buried=torch.zeros(n_row + 1, dtype=torch.int32, device=dev),
@@ -152,16 +132,9 @@ def burial_launcher(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
     order = [f for f, _ in SasaIn._fields_][2:25]
     mx = lambda a: int(max(a)) if len(a) else 0
     tail = (n_points, mx(N), mx(M), mx(NR), int(cand_cap))
-    hin = SasaIn(G, n_frame, *[host[k].ctypes.data if k in host else None for k in order], *tail, None)
-    cin = SasaIn(G, n_frame, *[t[k].data_ptr() for k in order], *tail, C.addressof(hin))
     cout = SasaOut(*[out[k].data_ptr() for k in ("lig_free", "lig_bound", "res_buried", "totals")])
-
-    def launch(_staged=(t, host, hin)):   # (the staged tensors and the host copies live as long as the closure)
-        with torch.cuda.device(dev):
-            L.check(lib.dbfr_sasa(C.byref(cin), C.byref(o), C.byref(cout), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        cin.host = None                   # validated once: later launches of the same staged inputs skip the host walk
-
-    loff, roff = _ptr(F * N, np.int64), _ptr(F * NR, np.int64)
+    launch = fb.launcher(lib.dbfr_sasa, SasaIn, (G, n_frame), order, tail, t, dev, o, cout, host)
+    loff, roff = fb.ptr(F * N, np.int64), fb.ptr(F * NR, np.int64)
     res = {k: [out[k][loff[g]:loff[g + 1]].view(int(F[g]), int(N[g])) for g in range(G)] for k in ("lig_free", "lig_bound")}
     res["res_buried"] = [out["res_buried"][roff[g]:roff[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)]
     res["totals"] = out["totals"][:n_frame]
@@ -251,8 +224,7 @@ def burial_entries(entries, poses=None, reference=None, **opts):
         return dict(totals=np.zeros((0, 6), np.int64), lig_free=[], lig_bound=[], res_buried=[]), []
     r = burial(groups, **opts)
     tot = r["totals"].cpu().numpy()
-    first = np.concatenate([[0], np.cumsum([p + extra for p in n_pose])])
-    keep = np.concatenate([np.arange(first[k], first[k] + n_pose[k]) for k in range(len(entries))]).astype(np.int64)
+    first, keep = fb.frame_rows(n_pose, extra)
     rows = [x.cpu().numpy() for x in r["res_buried"]]
     out = dict(totals=tot[keep], res_buried=[w[:p] for w, p in zip(rows, n_pose)])
     for key in ("lig_free", "lig_bound"):
@@ -282,7 +254,6 @@ def annotate(entries, pd_df, poses=None, reference=None, interface_area=1.0, **o
     positions of a reference pose; it is evaluated as one extra frame of the same launch against the input pocket
     ``atom14_position`` and adds ``sasa_buried_frac_ref`` and ``sasa_interface_recovery`` (the share of the reference's interface
     residues that are also in the pose's interface; NaN when the reference has none).  ``opts``: ``probe``, ``n_points``."""
-    from .interactions import residue_tags
     n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
     if n_rows != len(pd_df):
         raise DbfrError(f"{len(pd_df)} frame rows for {n_rows} poses of the entries")
@@ -300,11 +271,8 @@ def annotate(entries, pd_df, poses=None, reference=None, interface_area=1.0, **o
     df["sasa_buried_lig_polar"] = area(tot[:, 2] - tot[:, 3])
     df["sasa_buried_rec_polar"] = area(tot[:, 5])
     limit = float(interface_area) * UNIT
-    tag_cache, n_int, names, frac_ref, recovery, i = {}, [], [], [], [], 0
-    for e, rows, ref in zip(entries, r["res_buried"], refs if refs else [None] * len(entries)):
-        if id(e.topology) not in tag_cache:
-            tag_cache[id(e.topology)] = residue_tags(e.topology)
-        tags = tag_cache[id(e.topology)]
+    n_int, names, frac_ref, recovery, i = [], [], [], [], 0
+    for tags, rows, ref in zip(fb.residue_tag_cache(entries), r["res_buried"], refs if refs else [None] * len(entries)):
         ref_hit = np.flatnonzero(ref["res_buried"] >= limit) if ref is not None else None
         for f in range(rows.shape[0]):
             hit = np.flatnonzero(rows[f] >= limit)

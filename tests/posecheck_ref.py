@@ -88,3 +88,58 @@ def pairs_4_apart(n, bonds):
     for k in range(n):
         D = np.minimum(D, D[:, k:k + 1] + D[k:k + 1, :])
     return [(i, j) for i in range(n) for j in range(i + 1, n) if D[i, j] >= 4]
+
+
+# ------------------------------------------------------------------------------------------------ the ragged batch of the kernel tests
+RADII = np.array([1.70, 1.55, 1.52, 1.80, 1.47, 1.75])
+# (n, F, M, S) and what the group lacks: no receptor at all | no static atoms, no pairs | no double bonds | beyond one tile
+BATCH = (((17, 3, 60, 200), {}), ((5, 1, 0, 0), {}), ((31, 4, 140, 0), dict(pairs=False)), ((9, 2, 25, 50), dict(bonds=False)),
+         ((44, 2, 300, 1500), {}))
+
+
+def rot(rng, spread=None):
+    q = rng.standard_normal(4)
+    if spread is not None:
+        q[0], q[1:] = 1.0, q[1:] * spread
+    q /= np.linalg.norm(q)
+    w, x, y, z = q
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def random_group(rng, n, F, M, S, pairs=True, bonds=True):
+    """A synthetic ligand of n atoms in F frames (rigid moves of its conformer about a pocket at the origin), M pocket atoms per
+    frame and S static atoms around it, random pair / flatness / stereo lists; a host group (numpy)."""
+    from diffbindfr_amd import synthetic
+    lg = synthetic.make_ligand(rng, n)
+    x0 = lg["lig_pos_ref"] - lg["lig_pos_ref"].mean(0)
+    lig = np.stack([x0 @ rot(rng).T + rng.normal(scale=1.0, size=3) for _ in range(F)]).astype(np.float32)
+    chem = {"radii": rng.choice(RADII, n).astype(np.float32)}
+    iu = np.array(np.triu_indices(n, 1)).T
+    chem["pairs"] = iu[rng.random(len(iu)) < 0.6].astype(np.int32) if pairs else np.zeros((0, 2), np.int32)
+    nf = int(rng.integers(1, 6)) if bonds else 0
+    flat = -np.ones((nf, 8), np.int32)
+    for b in range(nf):
+        k = int(rng.integers(4, min(8, n) + 1))
+        flat[b, :k] = rng.choice(n, k, replace=False)
+    chem["flat"] = flat
+    ns = int(rng.integers(1, 6)) if bonds else 0
+    chem["stereo"] = np.array([rng.choice(n, 4, replace=False) for _ in range(ns)], np.int32).reshape(-1, 4)
+    chem["stereo_sign"] = rng.choice([-1, 1], ns).astype(np.int8)
+    # pocket atoms: a shell 2.5-6 A around each frame's ligand atoms (some close enough to clash and overlap)
+    pocket = np.zeros((F, M, 3), np.float32)
+    for f in range(F):
+        anchor = lig[f][rng.integers(0, n, M)]
+        d = rng.standard_normal((M, 3))
+        pocket[f] = anchor + d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(2.0, 6.0, (M, 1))
+    static = rng.uniform(-14, 14, (S, 3)).astype(np.float32)
+    return dict(lig=lig, chem=chem, pocket=pocket,
+                pocket_rad=rng.choice(RADII[:4], M).astype(np.float32), static=static,
+                static_rad=rng.choice(RADII[:4], S).astype(np.float32))
+
+
+def random_batch(seed):
+    """The batch of tests/test_posecheck_gpu.py::test_kernel_matches_the_float64_restatement (seed 11), host groups."""
+    rng = np.random.default_rng(seed)
+    return [random_group(rng, *shape, **kind) for shape, kind in BATCH]

@@ -15,50 +15,14 @@ import posecheck_ref  # noqa: E402  (a module next to the test files: pytest put
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-RADII = np.array([1.70, 1.55, 1.52, 1.80, 1.47, 1.75])
 FLOATS = ("min_dist", "min_ratio", "int_min_ratio")
 COUNTS = ("n_clash", "n_int_clash", "n_stereo_flip")
 
 
-def _rot(rng, spread=None):
-    q = rng.standard_normal(4)
-    if spread is not None:
-        q[0], q[1:] = 1.0, q[1:] * spread
-    q /= np.linalg.norm(q)
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def _random_group(rng, n, F, M, S, pairs=True, bonds=True):
-    """A synthetic ligand of n atoms in F frames (rigid moves of its conformer about a pocket at the origin), M pocket atoms per
-    frame and S static atoms around it, random pair / flatness / stereo lists."""
-    lg = synthetic.make_ligand(rng, n)
-    x0 = lg["lig_pos_ref"] - lg["lig_pos_ref"].mean(0)
-    lig = np.stack([x0 @ _rot(rng).T + rng.normal(scale=1.0, size=3) for _ in range(F)]).astype(np.float32)
-    chem = {"radii": rng.choice(RADII, n).astype(np.float32)}
-    iu = np.array(np.triu_indices(n, 1)).T
-    chem["pairs"] = iu[rng.random(len(iu)) < 0.6].astype(np.int32) if pairs else np.zeros((0, 2), np.int32)
-    nf = int(rng.integers(1, 6)) if bonds else 0
-    flat = -np.ones((nf, 8), np.int32)
-    for b in range(nf):
-        k = int(rng.integers(4, min(8, n) + 1))
-        flat[b, :k] = rng.choice(n, k, replace=False)
-    chem["flat"] = flat
-    ns = int(rng.integers(1, 6)) if bonds else 0
-    chem["stereo"] = np.array([rng.choice(n, 4, replace=False) for _ in range(ns)], np.int32).reshape(-1, 4)
-    chem["stereo_sign"] = rng.choice([-1, 1], ns).astype(np.int8)
-    # pocket atoms: a shell 2.5-6 A around each frame's ligand atoms (some close enough to clash and overlap)
-    pocket = np.zeros((F, M, 3), np.float32)
-    for f in range(F):
-        anchor = lig[f][rng.integers(0, n, M)]
-        d = rng.standard_normal((M, 3))
-        pocket[f] = anchor + d / np.linalg.norm(d, axis=1, keepdims=True) * rng.uniform(2.0, 6.0, (M, 1))
-    static = rng.uniform(-14, 14, (S, 3)).astype(np.float32)
-    return dict(lig=torch.as_tensor(lig, device=DEV), chem=chem, pocket=torch.as_tensor(pocket, device=DEV),
-                pocket_rad=rng.choice(RADII[:4], M).astype(np.float32), static=static,
-                static_rad=rng.choice(RADII[:4], S).astype(np.float32))
+def _random_group(rng, *shape, **kind):
+    """``posecheck_ref.random_group`` with its poses and pocket atoms on the device."""
+    gr = posecheck_ref.random_group(rng, *shape, **kind)
+    return dict(gr, lig=torch.as_tensor(gr["lig"], device=DEV), pocket=torch.as_tensor(gr["pocket"], device=DEV))
 
 
 def _ref(gr, f, **opts):
@@ -76,10 +40,7 @@ def _frames(groups):
 
 
 def _batch(rng):
-    return [_random_group(rng, 17, 3, 60, 200), _random_group(rng, 5, 1, 0, 0),             # no receptor at all
-            _random_group(rng, 31, 4, 140, 0, pairs=False),                                    # no static atoms, no pairs
-            _random_group(rng, 9, 2, 25, 50, bonds=False),                                     # no double bonds
-            _random_group(rng, 44, 2, 300, 1500)]
+    return [_random_group(rng, *shape, **kind) for shape, kind in posecheck_ref.BATCH]
 
 
 def test_kernel_matches_the_float64_restatement():

@@ -206,6 +206,25 @@ class HoloMetricsOut(C.Structure):
                                           "plddt_num", "lddt_num")]
 
 
+class HeteroCheckIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "lig_cov", "lig_flags", "het_ptr",
+                                          "het_pos", "het_rad", "het_cov", "het_class", "het_metal", "pocket_ptr", "pocket_pos_off",
+                                          "pocket_pos", "pocket_polar", "pocket_col", "static_ptr", "static_pos", "static_polar",
+                                          "static_col", "res_ptr")] + \
+               [(n, C.c_int32) for n in ("max_lig", "max_pocket", "max_res", "cand_cap")] + [("host", C.c_void_p)]
+
+
+class HeteroCheckOpts(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("clash_ratio", "displace_dist", "metal_dist", "hbond_dist", "grid")] + \
+               [("vol_scale", C.c_float * 3), ("vol_overlap_max", C.c_float * 3), ("max_event", C.c_int32)]
+
+
+class HeteroCheckOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("min_dist", "min_ratio", "worst", "n_clash", "vol_lig", "vol_overlap", "n_displaced", "n_bridge",
+                                          "n_coord", "passed", "event_i", "event_f", "n_event")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -246,7 +265,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
-           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics"]
+           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check"]
 
 _lib = None
 
@@ -343,6 +362,7 @@ def load():
     lib.dbfr_seq_align.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32]
     lib.dbfr_holo_site.argtypes = [C.POINTER(HoloSiteIn), vp, vp]
     lib.dbfr_holo_metrics.argtypes = [C.POINTER(HoloMetricsIn), C.POINTER(HoloMetricsOpts), C.POINTER(HoloMetricsOut), vp]
+    lib.dbfr_hetero_check.argtypes = [C.POINTER(HeteroCheckIn), C.POINTER(HeteroCheckOpts), C.POINTER(HeteroCheckOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

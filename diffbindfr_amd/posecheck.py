@@ -31,7 +31,7 @@ receptor atom's element comes from its atom37 name.
 ``pb_valid`` = all six.  Not evaluated (rigid motions and rotations about bridge bonds -- all the sampler, the Kabsch
 re-alignment and the Vina minimiser do -- preserve them, so every pose gets the input's verdict): bond lengths, bond angles,
 aromatic ring flatness, tetrahedral chirality, sanitization / connectivity / formula / bonds.  Nor internal energy (a force
-field) or the cofactor and water checks (the pipeline carries neither).
+field).  The cofactor and water checks are evaluated by ``diffbindfr_amd.hetero`` (docs/hetero.md), not here.
 
 There is no CPU path: CPU tensors raise ``DbfrError``.  Limits: 256 ligand atoms, 64 flatness and 64 stereo bonds per ligand.
 """

@@ -46,7 +46,8 @@ extern "C" {
                                    dbfr_interactions, dbfr_pocket_check_in, dbfr_pocket_check_opts, dbfr_pocket_check_out,
                                    dbfr_pocket_check, dbfr_sasa_in, dbfr_sasa_opts, dbfr_sasa_out, dbfr_sasa, dbfr_seq_align,
                                    dbfr_holo_site_in, dbfr_holo_site, dbfr_holo_metrics_in, dbfr_holo_metrics_opts, dbfr_holo_metrics_out,
-                                   dbfr_holo_metrics */
+                                   dbfr_holo_metrics, dbfr_hetero_check_in, dbfr_hetero_check_opts, dbfr_hetero_check_out,
+                                   dbfr_hetero_check */
 
 typedef enum {
   DBFR_OK = 0,
@@ -961,6 +962,99 @@ typedef struct {                 /* device arrays; all but pair_dist may be NULL
 
 /* Two launches for the whole batch: the pairs of every group, then every frame.  opts NULL = defaults.                      */
 int dbfr_holo_metrics(const dbfr_holo_metrics_in* in, const dbfr_holo_metrics_opts* opts, const dbfr_holo_metrics_out* out,
+                      void* hip_stream);
+
+/* ---- Checks of poses against cofactors, metal ions and waters (csrc/hetero.hip; docs/hetero.md).  A batch of G groups (one
+ * group = the frames of one ligand in one complex), group g holding F_g frames of N_g ligand heavy atoms (L), H_g hetero atoms
+ * shared by its frames, M_g pocket atoms per frame and S_g static receptor atoms shared by its frames (receptor atom b of a
+ * frame: pocket atom b for b < M_g, static atom b - M_g otherwise; read for water bridges only) and n_res_g residue columns.
+ * A ligand atom has a vdW radius, a covalent radius and flag bits (1 polar, 2 coordinating); a hetero atom a class (0 organic
+ * cofactor, 1 inorganic cofactor, 2 water), a vdW radius, a covalent radius and a metal flag; a receptor atom a polar flag and
+ * a residue column.  d_ah = sqrt of the sum of the squared coordinate differences (float32, every operation rounded);
+ * R_ah = vdW + vdW for the classes 0 and 2, covalent + covalent for class 1.  Per hetero atom h: d_h = min_a d_ah, a_h the
+ * lowest a attaining it, rho_h = min_a d_ah / R_ah.
+ * Per frame and class c ([n_frame, 3]):
+ *   min_dist    min d_h over the class, min_ratio  min rho_h (+inf: the class is empty), worst  the lowest h attaining it (-1)
+ *   n_clash     pairs with d_ah / R_ah < clash_ratio
+ *   vol_lig     lattice points {grid k, k in Z^3} strictly within vol_scale[c] vdW_a of some ligand atom
+ *   vol_overlap those of them strictly within vol_scale[c] vdW_h of some hetero atom of class c
+ * Events, one per hetero atom, bits or'ed: 1 CLASH rho_h < clash_ratio; 2 DISPLACED a water with d_h < displace_dist; 4 COORD a
+ * metal with n_coord_h >= 1 coordinating ligand atoms at d_ah <= metal_dist; 8 LIGPOLAR a water that is not DISPLACED with a
+ * polar ligand atom at d_ah <= hbond_dist (p_h: the nearest, lowest index on a tie); 16 BRIDGE LIGPOLAR and a polar receptor
+ * atom at d <= hbond_dist of the water (b_h: the nearest, lowest index on a tie).  An atom with any of the bits 1, 2, 4, 16 is
+ * emitted, in hetero-atom order: event_i {h, bits, a_h, n_coord_h, p_h or -1, b_h or -1}, event_f {d_h, rho_h, d(h, b_h) or
+ * NaN}; slots not used hold -1 / NaN; n_event is the true count even above max_event.
+ * Per frame: n_displaced / n_bridge / n_coord = the hetero atoms with that bit; passed: bits 0..2 min_ratio[c] >= clash_ratio
+ * for c = 0, 1, 2, bits 3..5 vol_overlap[c] <= vol_overlap_max[c] vol_lig[c], bit 6 all six (an empty class passes both).
+ * Every reduction is a min, a max or an integer sum: a frame's outputs are bitwise the same alone, in any batch and for any
+ * cand_cap.  A frame with a non-finite or out-of-range (|x| > 1e4) coordinate or a radius outside (0, 4] gets NaN / -1 in every
+ * output and passed 0.  Limits (DBFR_ERR_ARG beyond them): N_g <= 256, M_g <= 8192, n_res_g <= 16384, max_event in [1, 256];
+ * hetero and static atoms are not limited.                                                                                  */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; per-frame outputs are indexed by frame                 */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_rad / _cov / _flags (N_g atoms per frame)          */
+  const int64_t* lig_pos_off;    /* [G] frame k of g at rows lig_pos_off[g] + k N_g of lig_pos                               */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const float*   lig_rad;        /* [lig_ptr[G]] vdW radii in (0, 4]                                                        */
+  const float*   lig_cov;        /* [lig_ptr[G]] covalent radii in (0, 4]                                                   */
+  const uint8_t* lig_flags;      /* [lig_ptr[G]] 1 = polar (N, O), 2 = coordinating (N, O, S)                                */
+  const int32_t* het_ptr;        /* [G+1] first hetero atom of every group in het_pos / _rad / _cov / _class / _metal (may be 0) */
+  const float*   het_pos;        /* [het_ptr[G], 3] in the frame of lig_pos                                                 */
+  const float*   het_rad;        /* vdW radii in (0, 4]                                                                     */
+  const float*   het_cov;        /* covalent radii in (0, 4]                                                                */
+  const uint8_t* het_class;      /* 0 organic cofactor, 1 inorganic cofactor, 2 water                                       */
+  const uint8_t* het_metal;      /* 1 = a metal                                                                             */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_polar / _col (may be 0 atoms)            */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                         */
+  const float*   pocket_pos;     /* [rows, 3]                                                                               */
+  const uint8_t* pocket_polar;   /* 1 = polar (N, O)                                                                        */
+  const int32_t* pocket_col;     /* residue column, 0 .. n_res_g - 1 (validated; the caller names b_h's residue with it)     */
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / _polar / _col, or NULL = none           */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of lig_pos                                              */
+  const uint8_t* static_polar;
+  const int32_t* static_col;
+  const int32_t* res_ptr;        /* [G+1]: n_res_g = res_ptr[g+1] - res_ptr[g]                                               */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 8192, 16384)                                 */
+  int32_t        max_pocket;
+  int32_t        max_res;
+  int32_t        cand_cap;       /* hetero atoms kept in LDS for the lattice passes, 0 = 1024 (same bits whatever the value;
+                                    tests; 1 .. 1024); with more candidates the passes read the hetero atoms from memory    */
+  const void*    host;           /* NULL, or a dbfr_hetero_check_in whose pointers are HOST copies of the same arrays (the three
+                                    position arrays are not read): every count, class, radius and residue column is then
+                                    validated before the launch (DBFR_ERR_ARG)                                              */
+} dbfr_hetero_check_in;
+
+typedef struct {
+  float   clash_ratio;           /* 0.75                                                                                    */
+  float   displace_dist;         /* A, 2.0                                                                                  */
+  float   metal_dist;            /* A, 2.8                                                                                  */
+  float   hbond_dist;            /* A, 3.5, in (0, 8]                                                                       */
+  float   grid;                  /* A, 0.25, in [0.05, 1]                                                                   */
+  float   vol_scale[3];          /* per class, 0.8 / 0.5 / 0.5, each in (0, 2]                                              */
+  float   vol_overlap_max[3];    /* per class, 0.075                                                                        */
+  int32_t max_event;             /* K, 32, in [1, 256]                                                                      */
+} dbfr_hetero_check_opts;
+
+typedef struct {                 /* device arrays; any may be NULL                                                          */
+  float*   min_dist;             /* [n_frame, 3]                                                                            */
+  float*   min_ratio;            /* [n_frame, 3]                                                                            */
+  int32_t* worst;                /* [n_frame, 3]                                                                            */
+  int32_t* n_clash;              /* [n_frame, 3]                                                                            */
+  int32_t* vol_lig;              /* [n_frame, 3]                                                                            */
+  int32_t* vol_overlap;          /* [n_frame, 3]                                                                            */
+  int32_t* n_displaced;          /* [n_frame]                                                                               */
+  int32_t* n_bridge;             /* [n_frame]                                                                               */
+  int32_t* n_coord;              /* [n_frame]                                                                               */
+  int32_t* passed;               /* [n_frame]                                                                               */
+  int32_t* event_i;              /* [n_frame, K, 6]                                                                         */
+  float*   event_f;              /* [n_frame, K, 3]                                                                         */
+  int32_t* n_event;              /* [n_frame]                                                                               */
+} dbfr_hetero_check_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_hetero_check(const dbfr_hetero_check_in* in, const dbfr_hetero_check_opts* opts, const dbfr_hetero_check_out* out,
                       void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file

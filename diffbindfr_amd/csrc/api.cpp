@@ -149,9 +149,8 @@ struct dbfr_model {
   ConvW2 layer2v[8][4];                       // ... of their l = 1 outputs alone (DBFR_GEMM_REDUCE_FIRST: the scalar outputs go through k_convz)
   ConvZ layerz[8][4], tor_convz, sc_convz;    // reduce-first form of the scalar-output paths (convz.hip)
   int use_conv2;
-  int gemm_split;      // DBFR_GEMM_*; non-zero: the 144 x W GEMM of the K=144 convs runs on the bf16 matrix pipe with 3-piece operands (conv2s.hip), any batch size
-  int conv_fuse;       // big batches: the four convs of a layer as one k_conv grid (conv.hip: k_conv_layer)
-  int conv2_layers;    // big batches: interaction layers [0, conv2_layers) still go through k_conv2 (their short W2 favours it)
+  int gemm_split;      // DBFR_GEMM_*; non-zero: the 144 x W GEMM of the K=144 convs runs on the fp16 matrix pipe with two-piece operands (conv2h.hip; reduce_first:
+                       // + convz.hip), any batch size
   int* queue;          // [2] unit queue of k_conv2 (re-armed by the kernel itself)
   std::string fallback_convs;   // ';'-separated names of the convs whose weights two fp16 pieces cannot hold (dbfr_model_fallback_convs)
   std::string rowscaled_convs;  // 'name:depth;' of the convs packed with per-row factors (dbfr_model_rowscaled_convs)
@@ -174,10 +173,6 @@ struct dbfr_model {
   double useful_last;        // fifth: the executed flops that are not padding
   double form_bytes_last;    // sixth: HBM bytes the form that runs has to move (DBFR_GEMM_REDUCE_FIRST: scalar-output message columns once per segment, inputs read by both kernels)
   double conv_ms_acc; int64_t conv_launches_acc;
-  // side streams for small batches: the four convs of an interaction layer (and the three heads) are independent
-  hipStream_t side[3];
-  hipEvent_t ev_fork, ev_a, ev_b, ev_join[3];
-  bool streams_ready;
 };
 
 template <typename T>
@@ -888,6 +883,20 @@ extern "C" int dbfr_model_create(const dbfr_model_cfg* cfg, const dbfr_tensor* t
   }
 }
 
+// Every layout of one K=144 conv (an interaction-layer conv or a torsion conv): k_conv's, k_conv2 / k_conv2h's, the vector-output rows alone
+// (w2v; null for the torsion convs, whose outputs are all scalars) and k_convz's.  A conv that two fp16 pieces cannot hold sets `fallback_bit` of
+// layer_fallback and is named in fallback_convs, one packed with per-row factors in rowscaled_convs.
+static int pack_conv144(dbfr_model* m, const TMap& tm, const std::string& name, int kind, ConvW* w, ConvW2* w2, ConvW2* w2v, ConvZ* z, uint32_t fallback_bit) {
+  int rc = pack_conv(m, tm, name, kind, w);
+  if (!rc) rc = pack_conv2(m, tm, name, kind, *w, w2);
+  if (rc) return rc;
+  if (w2->f16_depth > f16_depth_ok()) { m->layer_fallback |= fallback_bit; m->fallback_convs += name + ";"; }
+  if (w2->W2rinv || w2->W1rinv) m->rowscaled_convs += name + ":" + std::to_string(w2->f16_depth_run) + ";";
+  if (w2v) rc = pack_conv2(m, tm, name, kind, *w, w2v, true);
+  if (!rc) rc = pack_convz(m, tm, name, kind, *w2, z);
+  return rc;
+}
+
 static int model_create_impl(const dbfr_model_cfg* cfg, const dbfr_tensor* tensors, int32_t n_tensors, dbfr_model** out) {
   if (!cfg || !tensors || !out) return fail(DBFR_ERR_ARG, "null argument");
   if (cfg->ns != NS || cfg->nv != NV || cfg->sh_lmax != 2 || cfg->distance_embed_dim != EMB ||
@@ -903,7 +912,6 @@ static int model_create_impl(const dbfr_model_cfg* cfg, const dbfr_tensor* tenso
   dbfr_model* m = new dbfr_model();
   m->cfg = *cfg;
   m->profile = 0; m->ev_used = 0; m->flops_dev = nullptr; m->fused_bytes_last = 0; m->executed_last = 0; m->useful_last = 0; m->form_bytes_last = 0; m->conv_ms_acc = 0; m->conv_launches_acc = 0;
-  m->streams_ready = false;
   m->edge_log = nullptr; m->edge_log_steps = 0; m->edge_log_graphs = 0; m->layer_fallback = 0;
   m->tie_log = nullptr; m->tie_log_steps = 0; m->tie_log_graphs = 0; m->tie_tol = 0.f;
   // which fused-conv kernel the K=144 convs use: k_conv2 (persistent, one launch per layer, tail split) wins while a layer
@@ -912,30 +920,13 @@ static int model_create_impl(const dbfr_model_cfg* cfg, const dbfr_tensor* tenso
   m->use_conv2 = getenv("DBFR_CONV2") ? atoi(getenv("DBFR_CONV2")) : -1;
   m->gemm_split = gemm_from_env();
   if (m->gemm_split < 0) rc = fail(DBFR_ERR_ARG, std::string("DBFR_GEMM=") + getenv("DBFR_GEMM") + ": unknown or retired value (f32 | split_f16 | reduce_first)");
-  m->conv2_layers = getenv("DBFR_CONV2_LAYERS") ? atoi(getenv("DBFR_CONV2_LAYERS")) : 0;
-  m->conv_fuse = getenv("DBFR_CONV_FUSE") ? atoi(getenv("DBFR_CONV_FUSE")) : 1;
   const char* fam[4] = {"lig_conv_layers", "cross_al_conv_layers", "atom_conv_layers", "cross_la_conv_layers"};
   for (int l = 0; l < cfg->num_conv_layers && !rc; ++l)
     for (int f = 0; f < 4 && !rc; ++f)
-    {
-      rc = pack_conv(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), &m->layer[l][f]);
-      if (!rc) rc = pack_conv2(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), m->layer[l][f], &m->layer2[l][f]);
-      if (!rc && m->layer2[l][f].f16_depth > f16_depth_ok()) { m->layer_fallback |= 1u << l; m->fallback_convs += std::string(fam[f]) + "." + std::to_string(l) + ";"; }
-      if (!rc && (m->layer2[l][f].W2rinv || m->layer2[l][f].W1rinv)) m->rowscaled_convs += std::string(fam[f]) + "." + std::to_string(l) + ":" + std::to_string(m->layer2[l][f].f16_depth_run) + ";";
-      if (!rc) rc = pack_conv2(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), m->layer[l][f], &m->layer2v[l][f], true);
-      if (!rc) rc = pack_convz(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), m->layer2[l][f], &m->layerz[l][f]);
-    }
+      rc = pack_conv144(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), &m->layer[l][f], &m->layer2[l][f], &m->layer2v[l][f], &m->layerz[l][f], 1u << l);
   if (!rc) rc = pack_conv(m, tm, "final_conv", 4, &m->final_conv);
-  if (!rc) rc = pack_conv(m, tm, "tor_bond_conv", 5, &m->tor_conv);
-  if (!rc) rc = pack_conv2(m, tm, "tor_bond_conv", 5, m->tor_conv, &m->tor_conv2);
-  if (!rc && m->tor_conv2.f16_depth > f16_depth_ok()) { m->layer_fallback |= 1u << 31; m->fallback_convs += "tor_bond_conv;"; }
-  if (!rc && (m->tor_conv2.W2rinv || m->tor_conv2.W1rinv)) m->rowscaled_convs += "tor_bond_conv:" + std::to_string(m->tor_conv2.f16_depth_run) + ";";
-  if (!rc) rc = pack_convz(m, tm, "tor_bond_conv", 5, m->tor_conv2, &m->tor_convz);
-  if (!rc && !cfg->no_sc_torsion) rc = pack_conv(m, tm, "sc_tor_bond_conv", 5, &m->sc_conv);
-  if (!rc && !cfg->no_sc_torsion) rc = pack_conv2(m, tm, "sc_tor_bond_conv", 5, m->sc_conv, &m->sc_conv2);
-  if (!rc && !cfg->no_sc_torsion && m->sc_conv2.f16_depth > f16_depth_ok()) { m->layer_fallback |= 1u << 31; m->fallback_convs += "sc_tor_bond_conv;"; }
-  if (!rc && !cfg->no_sc_torsion && (m->sc_conv2.W2rinv || m->sc_conv2.W1rinv)) m->rowscaled_convs += "sc_tor_bond_conv:" + std::to_string(m->sc_conv2.f16_depth_run) + ";";
-  if (!rc && !cfg->no_sc_torsion) rc = pack_convz(m, tm, "sc_tor_bond_conv", 5, m->sc_conv2, &m->sc_convz);
+  if (!rc) rc = pack_conv144(m, tm, "tor_bond_conv", 5, &m->tor_conv, &m->tor_conv2, nullptr, &m->tor_convz, 1u << 31);
+  if (!rc && !cfg->no_sc_torsion) rc = pack_conv144(m, tm, "sc_tor_bond_conv", 5, &m->sc_conv, &m->sc_conv2, nullptr, &m->sc_convz, 1u << 31);
   if (!rc) rc = pack_mlp(m, tm, "lig_node_embedding", cfg->lig_node_features + EMB, NS, NS, true, &m->lig_node_emb);
   if (!rc) rc = pack_mlp(m, tm, "lig_edge_embedding", cfg->lig_edge_features + 2 * EMB, NS, NS, true, &m->lig_edge_emb);
   if (!rc) rc = pack_mlp(m, tm, "atom_edge_embedding", 2 * EMB, NS, NS, true, &m->atom_edge_emb);
@@ -983,10 +974,6 @@ extern "C" void dbfr_model_destroy(dbfr_model* m) {
   if (!m) return;
   for (void* p : m->allocs) (void)hipFree(p);
   for (auto e : m->ev) (void)hipEventDestroy(e);
-  if (m->streams_ready) {
-    for (int i = 0; i < 3; ++i) { (void)hipStreamDestroy(m->side[i]); (void)hipEventDestroy(m->ev_join[i]); }
-    (void)hipEventDestroy(m->ev_fork); (void)hipEventDestroy(m->ev_a); (void)hipEventDestroy(m->ev_b);
-  }
   delete m;
 }
 
@@ -1014,7 +1001,7 @@ struct Ws {
   EdgeSet set[N_SETS];
   // centre set
   int *c_tgt, *c_gth, *c_row_start, *c_row_cnt, *c_n; float *c_dist, *c_sh, *c_emb;
-  float* msg[4]; int multi; int conv2; float* gp; float *tor_attr, *sc_attr, *tor_feat, *sc_feat;
+  float* msg[4]; int conv2; float* gp; float *tor_attr, *sc_attr, *tor_feat, *sc_feat;
   float *xmax_l, *xmax_a;   // [G] largest |feature| of every graph's ligand / pocket nodes in the current layer (k_row_absmax; k_convz's y scale)
   int* n_edges6;  // [8] device counters
 };
@@ -1068,20 +1055,13 @@ static int plan(const dbfr_model* m, const dbfr_batch* B, const dbfr_limits* lim
   w->c_n = w->n_edges6 ? w->n_edges6 + 6 : nullptr;
   // Which conv path a call takes (measured on MI355X, tools/latency_run.py):
   //   largest edge set <= 128 k edges (predict.py-sized batches: 1 complex x 4 poses, -bs 16): persistent k_conv2, one launch per layer;
-  //   above: k_conv_layer (the four convs of a layer as one k_conv grid) -- faster than k_conv2 from ~40 poses on and faster than
-  //   the former four-streams-per-layer mode at every size (that mode is kept behind DBFR_MULTI_EDGES for comparison only).
-  static const long multi_edges = getenv("DBFR_MULTI_EDGES") ? atol(getenv("DBFR_MULTI_EDGES")) : 0;
+  //   above: k_conv_layer (the four convs of a layer as one k_conv grid) -- faster than k_conv2 from ~40 poses on.
   static const long conv2_edges = getenv("DBFR_CONV2_EDGES") ? atol(getenv("DBFR_CONV2_EDGES")) : 128 * 1024;
-  w->multi = maxcap <= multi_edges;
   w->conv2 = m->gemm_split || m->use_conv2 > 0 || (m->use_conv2 < 0 && maxcap <= conv2_edges);
-  if (w->conv2 || m->conv2_layers > 0 || (m->conv_fuse && !w->multi)) {   // fused launches: every conv of a launch writes its own message buffer, sized by its own edge set
-    // (layers left to k_conv in the mixed mode push all four convs through msg[0])
-    const bool all_fused = w->conv2 || (m->conv_fuse && !w->multi && m->conv2_layers <= 0);
-    const long mc[4] = {all_fused ? std::max({caps[SET_LL], (long)NL, cap_t, cap_s}) : maxcap, std::max(caps[SET_AL], cap_s), caps[SET_AA], caps[SET_LA]};
-    for (int i = 0; i < 4; ++i) w->msg[i] = b.take<float>((size_t)std::max(mc[i], 1L) * MAXD, i == 0 ? "msg" : nullptr);
-    if (w->conv2) w->multi = 0;
-  } else
-  for (int i = 0; i < 4; ++i) w->msg[i] = (i == 0 || w->multi) ? b.take<float>((size_t)maxcap * MAXD, i == 0 ? "msg" : nullptr) : nullptr;
+  // every conv of a fused launch writes its own message buffer, sized by its own edge set; msg[0] also serves the centre set and the torsion heads
+  // (msg[1]: the side-chain head next to the ligand head in one fused launch)
+  const long mc[4] = {std::max({caps[SET_LL], (long)NL, cap_t, cap_s}), std::max(caps[SET_AL], cap_s), caps[SET_AA], caps[SET_LA]};
+  for (int i = 0; i < 4; ++i) w->msg[i] = b.take<float>((size_t)std::max(mc[i], 1L) * MAXD, i == 0 ? "msg" : nullptr);
   w->gp = b.take<float>((size_t)G * 12, "gp");
   w->xmax_l = b.take<float>(G, "xmax_l"); w->xmax_a = b.take<float>(G, "xmax_a");
   w->tor_attr = b.take<float>((size_t)(B->NTOR + 1) * NS, "tor_attr"); w->sc_attr = b.take<float>((size_t)(B->NSC + 1) * NS);
@@ -1118,16 +1098,66 @@ static void prof_events(dbfr_model* m, hipEvent_t* e0, hipEvent_t* e1) {
   *e0 = m->ev[m->ev_used++]; *e1 = m->ev[m->ev_used++];
 }
 
-static void conv_call(dbfr_model* m, const ConvW& cw, const int* n_edges, int max_edges, const int* tgt, const int* gth,
-                      const float* emb, const float* sh, const float* tab1, int ld1, const int* idx1, const float* tab2,
-                      int ld2, const int* idx2, const float* x, int ldx, float* msg, hipStream_t st) {
+// One conv site: where a conv finds its edges, the two node tables of its radial MLP (rows idx1 / idx2 of tab1 / tab2 next to the edge embedding), its
+// input rows (x, gathered by gth) and where its messages go -- and, for what follows the conv, the CSR rows of the reduction over target nodes.  The
+// arguments of every kernel that serves the site (k_conv, k_conv2 / k_conv2h, k_convz) are derived from this one description.
+struct ConvSite {
+  const int* n_edges; int max_edges; const int *tgt, *gth; const float *emb, *sh;
+  const float* tab1; int ld1; const int* idx1;
+  const float* tab2; int ld2; const int* idx2;
+  const float* x; int ldx;
+  float* msg;
+  const int *row_start, *row_cnt; const uint8_t* seg_first;                        // the reduction's view (null where the site is not reduced by its builder)
+  const int *chunk_es, *chunk_gl, *n_chunks; int max_chunks; const float* xmax;    // k_convz: the chunk table of the edge list, the y scale (or null)
+};
+
+static ConvSite flat_site(const int* n_edges, int max_edges, const int* tgt, const int* gth, const float* emb, const float* sh, const float* tab1, int ld1,
+                          const int* idx1, const float* tab2, int ld2, const int* idx2, const float* x, int ldx, float* msg) {
+  ConvSite s;
+  memset(&s, 0, sizeof s);
+  s.n_edges = n_edges; s.max_edges = max_edges; s.tgt = tgt; s.gth = gth; s.emb = emb; s.sh = sh;
+  s.tab1 = tab1; s.ld1 = ld1; s.idx1 = idx1; s.tab2 = tab2; s.ld2 = ld2; s.idx2 = idx2; s.x = x; s.ldx = ldx; s.msg = msg;
+  return s;
+}
+
+// ... on an edge set of the workspace; xmax: the per-graph |x| maximum of the node set x belongs to (launch_row_absmax)
+static ConvSite conv_site(const EdgeSet& S, int G, const float* tab1, int ld1, const int* idx1, const float* tab2, int ld2, const int* idx2, const float* x,
+                          int ldx, float* msg, const float* xmax) {
+  ConvSite s = flat_site(S.n_edges, S.cap, S.tgt, S.gth, S.emb, S.sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg);
+  s.row_start = S.row_start; s.row_cnt = S.row_cnt; s.seg_first = S.seg_first;
+  s.chunk_es = S.chunk_es; s.chunk_gl = S.chunk_gl; s.n_chunks = S.chunk0 + G; s.max_chunks = S.chunk_cap; s.xmax = xmax;
+  return s;
+}
+
+static ConvArgs conv_args(const ConvSite& s, const ConvW& cw) {
   ConvArgs a;
-  a.n_edges = n_edges; a.max_edges = max_edges; a.tgt = tgt; a.gth = gth; a.emb = emb; a.sh = sh; a.sh_sign = 1.f;
-  a.tab1 = tab1; a.ld1 = ld1; a.idx1 = idx1; a.tab2 = tab2; a.ld2 = ld2; a.idx2 = idx2; a.x = x; a.ldx = ldx;
-  a.w = cw; a.msg = msg;
+  a.n_edges = s.n_edges; a.max_edges = s.max_edges; a.tgt = s.tgt; a.gth = s.gth; a.emb = s.emb; a.sh = s.sh; a.sh_sign = 1.f;
+  a.tab1 = s.tab1; a.ld1 = s.ld1; a.idx1 = s.idx1; a.tab2 = s.tab2; a.ld2 = s.ld2; a.idx2 = s.idx2; a.x = s.x; a.ldx = s.ldx;
+  a.w = cw; a.msg = s.msg; a.trace = nullptr;
+  return a;
+}
+
+static Conv2Desc conv2_desc(const ConvSite& s, const ConvW2& cw) {
+  Conv2Desc d;
+  d.n_edges = s.n_edges; d.max_edges = s.max_edges; d.gth = s.gth; d.emb = s.emb; d.sh = s.sh; d.tab1 = s.tab1; d.ld1 = s.ld1; d.idx1 = s.idx1;
+  d.tab2 = s.tab2; d.ld2 = s.ld2; d.idx2 = s.idx2; d.x = s.x; d.ldx = s.ldx; d.w = cw; d.msg = s.msg;
+  return d;
+}
+
+static ConvZDesc convz_desc(const ConvSite& s, const ConvZ& z, int D_out) {
+  ConvZDesc o;
+  o.n_edges = s.n_edges; o.max_edges = s.max_edges; o.tgt = s.tgt; o.gth = s.gth; o.emb = s.emb; o.sh = s.sh;
+  o.tab1 = s.tab1; o.ld1 = s.ld1; o.idx1 = s.idx1; o.tab2 = s.tab2; o.ld2 = s.ld2; o.idx2 = s.idx2; o.x = s.x; o.ldx = s.ldx;
+  o.w = z; o.msg = s.msg; o.D_out = D_out; o.chunk_es = s.chunk_es; o.chunk_gl = s.chunk_gl; o.n_chunks = s.n_chunks; o.max_chunks = s.max_chunks; o.xmax = s.xmax;
+  return o;
+}
+
+// one k_conv launch
+static void conv_call(dbfr_model* m, const ConvW& cw, const ConvSite& site, hipStream_t st) {
+  const ConvArgs a = conv_args(site, cw);
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  // the dominant kernel k_conv<144> only (k_conv<96>: 3 short launches per step).  profile 1: HIP events around every
-  // launch (convs serialised on the main stream) + flop counter; profile 2: flop counter only, streams as in production
+  // the dominant kernel k_conv<144> only (k_conv<96>: one short launch per step).  profile 1: HIP events around every launch + flop counter;
+  // profile 2: flop counter only
   const bool prof = m->profile == 1 && cw.K == 144;
   const bool count = m->profile && cw.K == 144;
   if (prof) {
@@ -1140,26 +1170,8 @@ static void conv_call(dbfr_model* m, const ConvW& cw, const int* n_edges, int ma
     // algorithmic flops per edge: radial MLP 2K(K + W) + tensor-product contraction 2*(sum_paths mul1*mulo*dim_o)
     // second counter: HBM bytes the reference's two-kernel form moves per edge (the [E,W] weights once,
     // gathered irreps, harmonics, two int64 indices); the fused kernel never materialises them
-    launch_acc_flops(n_edges, 2.0 * cw.K * ((double)cw.K + cw.W), 4.0 * (cw.W + cw.D_in + 9) + 16.0, fused_bytes(cw.D_in, cw.D_out), m->flops_dev, st);
+    launch_acc_flops(a.n_edges, 2.0 * cw.K * ((double)cw.K + cw.W), 4.0 * (cw.W + cw.D_in + 9) + 16.0, fused_bytes(cw.D_in, cw.D_out), m->flops_dev, st);
   }
-}
-
-static Conv2Desc conv2_desc(const ConvW2& cw, const int* n_edges, int max_edges, const int* gth, const float* emb, const float* sh,
-                            const float* tab1, int ld1, const int* idx1, const float* tab2, int ld2, const int* idx2, const float* x,
-                            int ldx, float* msg) {
-  Conv2Desc d;
-  d.n_edges = n_edges; d.max_edges = max_edges; d.gth = gth; d.emb = emb; d.sh = sh; d.tab1 = tab1; d.ld1 = ld1; d.idx1 = idx1;
-  d.tab2 = tab2; d.ld2 = ld2; d.idx2 = idx2; d.x = x; d.ldx = ldx; d.w = cw; d.msg = msg;
-  return d;
-}
-
-static ConvZDesc convz_desc(const Conv2Desc& d, const ConvZ& z, const int* tgt, int D_out, const int* chunk_es, const int* chunk_gl, const int* n_chunks, int max_chunks,
-                            const float* xmax = nullptr) {
-  ConvZDesc o;
-  o.n_edges = d.n_edges; o.max_edges = d.max_edges; o.tgt = tgt; o.gth = d.gth; o.emb = d.emb; o.sh = d.sh;
-  o.tab1 = d.tab1; o.ld1 = d.ld1; o.idx1 = d.idx1; o.tab2 = d.tab2; o.ld2 = d.ld2; o.idx2 = d.idx2; o.x = d.x; o.ldx = d.ldx;
-  o.w = z; o.msg = d.msg; o.D_out = D_out; o.chunk_es = chunk_es; o.chunk_gl = chunk_gl; o.n_chunks = n_chunks; o.max_chunks = max_chunks; o.xmax = xmax;
-  return o;
 }
 
 // one fused k_conv2 launch over up to four K=144 convs (an interaction layer, or the two torsion heads)
@@ -1288,38 +1300,27 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     const float *lx = w.lig_x[cur], *ax = w.atom_x[cur];
     float *lnew = w.lig_x[cur ^ 1], *anew = w.atom_x[cur ^ 1];
     const EdgeSet &LL = w.set[SET_LL], &AA = w.set[SET_AA], &AL = w.set[SET_AL], &LA = w.set[SET_LA];
-    if (w.conv2 || l < m->conv2_layers) {   // all four convs of the layer in ONE persistent launch (conv2.hip)
-      const bool rf = m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !((m->layer_fallback >> l) & 1u);
-      const ConvW2* L2 = rf ? m->layer2v[l] : m->layer2[l];
-      const Conv2Desc ds[4] = {
-          conv2_desc(L2[0], LL.n_edges, LL.cap, LL.gth, LL.emb, LL.sh, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0]),
-          conv2_desc(L2[1], AL.n_edges, AL.cap, AL.gth, AL.emb, AL.sh, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1]),
-          conv2_desc(L2[2], AA.n_edges, AA.cap, AA.gth, AA.emb, AA.sh, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2]),
-          conv2_desc(L2[3], LA.n_edges, LA.cap, LA.gth, LA.emb, LA.sh, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3])};
-      const int Ws[4] = {m->layer[l][0].W, m->layer[l][1].W, m->layer[l][2].W, m->layer[l][3].W};
-      if (rf) {   // the y scale of k_convz: largest |x| per graph and node set (x = the rows a conv gathers: LL, LA read ligand rows, AL, AA pocket rows)
-        launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, Di, Di, G, NA, st);
-      }
-      auto zd = [&](int i, const EdgeSet& S, const float* xmax) { return convz_desc(ds[i], m->layerz[l][i], S.tgt, Do, S.chunk_es, S.chunk_gl, S.chunk0 + G, S.chunk_cap, xmax); };
-      const ConvZDesc zs[4] = {zd(0, LL, w.xmax_l), zd(1, AL, w.xmax_a), zd(2, AA, w.xmax_a), zd(3, LA, w.xmax_l)};
-      conv2_call(m, ds, Ws, 4, st, (m->layer_fallback >> l) & 1u, rf ? zs : nullptr);
-      ReduceLayerArgs ra;
-      const EdgeSet* es[4] = {&LL, &AL, &AA, &LA};
+    // the four convs of the layer, in family order: the radial MLP reads the target node's row and the source node's, the tensor product the source's;
+    // all four read the OLD features
+    const ConvSite sites[4] = {conv_site(LL, G, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], w.xmax_l),    // 0 ligand <- ligand
+                               conv_site(AL, G, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1], w.xmax_a),    // 1 ligand <- pocket
+                               conv_site(AA, G, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2], w.xmax_a),    // 2 pocket <- pocket
+                               conv_site(LA, G, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3], w.xmax_l)};   // 3 pocket <- ligand
+    const bool fallback = (m->layer_fallback >> l) & 1u;
+    const bool rf = w.conv2 && m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;
+    if (w.conv2) {   // all four convs of the layer in ONE persistent launch (conv2.hip), or the k_convz + k_conv2h pair
+      Conv2Desc ds[4]; ConvZDesc zs[4]; int Ws[4];
       for (int i = 0; i < 4; ++i) {
-        ra.msg[i] = w.msg[i]; ra.row_start[i] = es[i]->row_start; ra.row_cnt[i] = es[i]->row_cnt; ra.ln[i] = m->layer[l][i].ln;
-        ra.first[i] = rf ? es[i]->seg_first : nullptr; ra.sc_lanes[i] = rf ? convz_sc_lanes(m->layerz[l][i]) : 0;
+        ds[i] = conv2_desc(sites[i], rf ? m->layer2v[l][i] : m->layer2[l][i]);
+        zs[i] = convz_desc(sites[i], m->layerz[l][i], Do);
+        Ws[i] = m->layer[l][i].W;
       }
-      ra.NL = NL; ra.NA = NA; ra.D = Do; ra.D_old = Di; ra.old_l = lx; ra.old_a = ax; ra.out_l = lnew; ra.out_a = anew;
-      launch_reduce_ln_layer(ra, st);
-    } else if (m->conv_fuse && !w.multi) {   // bench-sized batches: the layer's four convs as ONE k_conv grid, one reduction launch
-      auto mk = [&](const ConvW& cw, const EdgeSet& S, const float* tab1, const int* idx1, const float* tab2, const int* idx2, const float* x, float* msg) {
-        ConvArgs a;
-        a.n_edges = S.n_edges; a.max_edges = S.cap; a.tgt = S.tgt; a.gth = S.gth; a.emb = S.emb; a.sh = S.sh; a.sh_sign = 1.f;
-        a.tab1 = tab1; a.ld1 = Di; a.idx1 = idx1; a.tab2 = tab2; a.ld2 = Di; a.idx2 = idx2; a.x = x; a.ldx = Di; a.w = cw; a.msg = msg; a.trace = nullptr;
-        return a;
-      };
-      const ConvArgs c4[4] = {mk(m->layer[l][0], LL, lx, LL.tgt, lx, LL.gth, lx, w.msg[0]), mk(m->layer[l][1], AL, lx, AL.tgt, ax, AL.gth, ax, w.msg[1]),
-                              mk(m->layer[l][2], AA, ax, AA.tgt, ax, AA.gth, ax, w.msg[2]), mk(m->layer[l][3], LA, ax, LA.tgt, lx, LA.gth, lx, w.msg[3])};
+      // the y scale of k_convz: largest |x| per graph and node set (x = the rows a conv gathers: LL, LA read ligand rows, AL, AA pocket rows)
+      if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, Di, Di, G, NA, st);
+      conv2_call(m, ds, Ws, 4, st, fallback, rf ? zs : nullptr);
+    } else {   // bench-sized batches in f32 mode: the layer's four convs as ONE k_conv grid
+      ConvArgs c4[4];
+      for (int i = 0; i < 4; ++i) c4[i] = conv_args(sites[i], m->layer[l][i]);
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (m->profile == 1) {
         prof_events(m, &e0, &e1);
@@ -1330,57 +1331,19 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
       if (m->profile)
         for (int i = 0; i < 4; ++i)
           launch_acc_flops(c4[i].n_edges, 2.0 * 144 * (144.0 + m->layer[l][i].W), 4.0 * (m->layer[l][i].W + Di + 9) + 16.0, fused_bytes(Di, Do), m->flops_dev, st);
-      ReduceLayerArgs ra;
-      const EdgeSet* es[4] = {&LL, &AL, &AA, &LA};
-      for (int i = 0; i < 4; ++i) { ra.msg[i] = w.msg[i]; ra.row_start[i] = es[i]->row_start; ra.row_cnt[i] = es[i]->row_cnt; ra.ln[i] = m->layer[l][i].ln; ra.first[i] = nullptr; ra.sc_lanes[i] = 0; }
-      ra.NL = NL; ra.NA = NA; ra.D = Do; ra.D_old = Di; ra.old_l = lx; ra.old_a = ax; ra.out_l = lnew; ra.out_a = anew;
-      launch_reduce_ln_layer(ra, st);
-    } else if (!w.multi || m->profile == 1) {   // profiling times each conv alone on the main stream
-      conv_call(m, m->layer[l][0], LL.n_edges, LL.cap, LL.tgt, LL.gth, LL.emb, LL.sh, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], st);
-      launch_reduce_ln(w.msg[0], LL.row_start, LL.row_cnt, NL, Do, m->layer[l][0].ln, lx, Di, lnew, Do, 0, st);
-      conv_call(m, m->layer[l][1], AL.n_edges, AL.cap, AL.tgt, AL.gth, AL.emb, AL.sh, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[0], st);
-      launch_reduce_ln(w.msg[0], AL.row_start, AL.row_cnt, NL, Do, m->layer[l][1].ln, nullptr, 0, lnew, Do, 1, st);
-      conv_call(m, m->layer[l][2], AA.n_edges, AA.cap, AA.tgt, AA.gth, AA.emb, AA.sh, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[0], st);
-      launch_reduce_ln(w.msg[0], AA.row_start, AA.row_cnt, NA, Do, m->layer[l][2].ln, ax, Di, anew, Do, 0, st);
-      conv_call(m, m->layer[l][3], LA.n_edges, LA.cap, LA.tgt, LA.gth, LA.emb, LA.sh, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[0], st);
-      launch_reduce_ln(w.msg[0], LA.row_start, LA.row_cnt, NA, Do, m->layer[l][3].ln, nullptr, 0, anew, Do, 1, st);
-    } else {
-      // fork: all four convs read the OLD features; the two reductions into one node set stay ordered by an event
-      hipStream_t s0 = m->side[0], s1 = m->side[1], s2 = m->side[2];
-      HIPCHECK(hipEventRecord(m->ev_fork, st));
-      for (int i = 0; i < 3; ++i) HIPCHECK(hipStreamWaitEvent(m->side[i], m->ev_fork, 0));
-      conv_call(m, m->layer[l][0], LL.n_edges, LL.cap, LL.tgt, LL.gth, LL.emb, LL.sh, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], st);
-      conv_call(m, m->layer[l][1], AL.n_edges, AL.cap, AL.tgt, AL.gth, AL.emb, AL.sh, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1], s0);
-      conv_call(m, m->layer[l][2], AA.n_edges, AA.cap, AA.tgt, AA.gth, AA.emb, AA.sh, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2], s1);
-      conv_call(m, m->layer[l][3], LA.n_edges, LA.cap, LA.tgt, LA.gth, LA.emb, LA.sh, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3], s2);
-      launch_reduce_ln(w.msg[0], LL.row_start, LL.row_cnt, NL, Do, m->layer[l][0].ln, lx, Di, lnew, Do, 0, st);
-      HIPCHECK(hipEventRecord(m->ev_a, st));
-      HIPCHECK(hipStreamWaitEvent(s0, m->ev_a, 0));
-      launch_reduce_ln(w.msg[1], AL.row_start, AL.row_cnt, NL, Do, m->layer[l][1].ln, nullptr, 0, lnew, Do, 1, s0);
-      launch_reduce_ln(w.msg[2], AA.row_start, AA.row_cnt, NA, Do, m->layer[l][2].ln, ax, Di, anew, Do, 0, s1);
-      HIPCHECK(hipEventRecord(m->ev_b, s1));
-      HIPCHECK(hipStreamWaitEvent(s2, m->ev_b, 0));
-      launch_reduce_ln(w.msg[3], LA.row_start, LA.row_cnt, NA, Do, m->layer[l][3].ln, nullptr, 0, anew, Do, 1, s2);
-      HIPCHECK(hipEventRecord(m->ev_join[0], s0));
-      HIPCHECK(hipEventRecord(m->ev_join[2], s2));
-      HIPCHECK(hipStreamWaitEvent(st, m->ev_join[0], 0));
-      HIPCHECK(hipStreamWaitEvent(st, m->ev_join[2], 0));
     }
+    ReduceLayerArgs ra;   // one reduction launch: LL then AL into the ligand rows, AA then LA into the pocket rows
+    for (int i = 0; i < 4; ++i) {
+      ra.msg[i] = sites[i].msg; ra.row_start[i] = sites[i].row_start; ra.row_cnt[i] = sites[i].row_cnt; ra.ln[i] = m->layer[l][i].ln;
+      ra.first[i] = rf ? sites[i].seg_first : nullptr; ra.sc_lanes[i] = rf ? convz_sc_lanes(m->layerz[l][i]) : 0;
+    }
+    ra.NL = NL; ra.NA = NA; ra.D = Do; ra.D_old = Di; ra.old_l = lx; ra.old_a = ax; ra.out_l = lnew; ra.out_a = anew;
+    launch_reduce_ln_layer(ra, st);
     cur ^= 1;
   }
   const int D = dims[std::min(cfg.num_conv_layers, 3)];
   if (D != MAXD) return fail(DBFR_ERR_ARG, "heads need num_conv_layers >= 3");
   const float *lx = w.lig_x[cur], *ax = w.atom_x[cur];
-  // ---- the three heads are independent: in the small-batch (multi-stream) regime the two torsion heads run on side streams
-  const bool fork_heads = w.multi && m->profile != 1 && !w.conv2;
-  hipStream_t s_tor = fork_heads ? m->side[0] : st, s_sc = fork_heads ? m->side[1] : st;
-  float* msg_tor = fork_heads ? w.msg[1] : w.msg[0];
-  float* msg_sc = fork_heads ? w.msg[2] : w.msg[0];
-  if (fork_heads) {
-    HIPCHECK(hipEventRecord(m->ev_fork, st));
-    HIPCHECK(hipStreamWaitEvent(s_tor, m->ev_fork, 0));
-    HIPCHECK(hipStreamWaitEvent(s_sc, m->ev_fork, 0));
-  }
   // ---- translation / rotation head
   launch_center_edges(*B, w.c_tgt, w.c_gth, w.c_dist, w.c_sh, w.c_row_start, w.c_row_cnt, st);
   {
@@ -1389,7 +1352,7 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     a.dist = w.c_dist; a.gs_offset = m->gs_center_off; a.gs_coeff = m->gs_center_c; a.out = w.c_emb;
     launch_mlp(a, st);
   }
-  conv_call(m, m->final_conv, w.n_edges6 + 7, NL, w.c_tgt, w.c_gth, w.c_emb, w.c_sh, lx, D, w.c_gth, nullptr, 0, w.c_gth, lx, D, w.msg[0], st);
+  conv_call(m, m->final_conv, flat_site(w.n_edges6 + 7, NL, w.c_tgt, w.c_gth, w.c_emb, w.c_sh, lx, D, w.c_gth, nullptr, 0, w.c_gth, lx, D, w.msg[0]), st);
   launch_reduce_ln(w.msg[0], w.c_row_start, w.c_row_cnt, G, 12, m->final_conv.ln, nullptr, 0, w.gp, 12, 2, st);
   {
     TrRotArgs a; a.gp = w.gp; a.temb = w.temb; a.tr_sigma = c->tr_sigma; a.rot_norm = c->rot_score_norm;
@@ -1397,79 +1360,70 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     a.rot_out = out->rot; a.err = w.err;
     launch_trrot(a, st);
   }
-  if (w.conv2) {   // both torsion heads: embeddings, ONE fused k_conv2 launch, reductions, final MLPs
-    const EdgeSet& T = w.set[SET_TOR];
-    const EdgeSet& S = w.set[SET_SC];
-    const bool do_t = B->NTOR > 0, do_s = !cfg.no_sc_torsion && B->NSC > 0;
-    const bool rf = m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !((m->layer_fallback >> 31) & 1u);
+  // ---- the two torsion heads (ligand bonds, side-chain bonds): bond attributes + edge embedding, the conv, reduction + final MLP
+  struct TorHead {
+    bool on; int n; const EdgeSet* S; ConvSite site;
+    const float* nodes; const int *b0, *b1, *bsel; int stride; float* attr;    // launch_bond_attr
+    const Mlp2* emb; const float *gs_off, *gs_c;                               // the edge embedding
+    const ConvW* cw; const ConvW2* cw2; const ConvZ* cz;
+    const Mlp2* fin; const float* norm2; float *feat, *out;                    // launch_tor_final
+  };
+  const EdgeSet &T = w.set[SET_TOR], &S = w.set[SET_SC];
+  // (one fused launch writes a message buffer per head; one k_conv per head re-uses msg[0])
+  TorHead heads[2];
+  {
+    TorHead& h = heads[0];   // ligand torsions: edges bond <- ligand atom
+    h.on = B->NTOR > 0; h.n = B->NTOR; h.S = &T;
+    h.site = conv_site(T, G, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, w.msg[0], w.xmax_l);
+    h.nodes = lx; h.b0 = B->bond_src; h.b1 = B->bond_dst; h.bsel = B->tor_bond; h.stride = 0; h.attr = w.tor_attr;
+    h.emb = &m->tor_edge_emb; h.gs_off = m->gs_lig_off; h.gs_c = m->gs_lig_c;
+    h.cw = &m->tor_conv; h.cw2 = &m->tor_conv2; h.cz = &m->tor_convz;
+    h.fin = &m->tor_final; h.norm2 = c->tor_score_norm2; h.feat = w.tor_feat; h.out = out->tor;
+  }
+  {
+    TorHead& h = heads[1];   // side-chain torsions: edges bond <- pocket atom
+    h.on = !cfg.no_sc_torsion && B->NSC > 0; h.n = B->NSC; h.S = &S;
+    h.site = conv_site(S, G, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, w.msg[w.conv2 ? 1 : 0], w.xmax_a);
+    h.nodes = ax; h.b0 = B->sc_bond; h.b1 = nullptr; h.bsel = nullptr; h.stride = 2; h.attr = w.sc_attr;
+    h.emb = &m->sc_edge_emb; h.gs_off = m->gs_atom_off; h.gs_c = m->gs_atom_c;
+    h.cw = &m->sc_conv; h.cw2 = &m->sc_conv2; h.cz = &m->sc_convz;
+    h.fin = &m->sc_final; h.norm2 = c->sc_tor_score_norm2; h.feat = w.sc_feat; h.out = out->sc_tor;
+  }
+  const bool fallback = (m->layer_fallback >> 31) & 1u;
+  const bool rf = w.conv2 && m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;
+  auto prologue = [&](const TorHead& h) {
+    launch_bond_attr(h.nodes, D, h.b0, h.b1, h.bsel, h.stride, h.n, h.attr, st);
+    MlpArgs a; memset(&a, 0, sizeof a);
+    a.w = *h.emb; a.mode = IN_G; a.n_rows_dev = h.S->n_edges; a.n_rows_max = h.S->cap; a.dist = h.S->dist;
+    a.gs_offset = h.gs_off; a.gs_coeff = h.gs_c; a.out = h.S->emb;
+    launch_mlp(a, st);
+  };
+  auto epilogue = [&](const TorHead& h) {
+    if (rf) launch_reduce_ln(h.site.msg, h.site.row_start, h.site.row_cnt, h.n, 2 * NS, h.cw->ln, nullptr, 0, h.feat, 2 * NS, 2, st, h.site.seg_first, convz_sc_lanes(*h.cz));
+    else launch_reduce_ln(h.site.msg, h.site.row_start, h.site.row_cnt, h.n, 2 * NS, h.cw->ln, nullptr, 0, h.feat, 2 * NS, 2, st);
+    launch_tor_final(h.feat, *h.fin, h.norm2, cfg.scale_by_sigma, h.n, h.out, st);
+  };
+  if (w.conv2) {   // both prologues, ONE fused launch over the heads present, both epilogues
     Conv2Desc ds[2]; ConvZDesc zs[2]; int Ws[2]; int nd = 0;
-    if (rf) {
-      launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, D, D, G, NA, st);
+    if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, D, D, G, NA, st);
+    for (const TorHead& h : heads) {
+      if (!h.on) continue;
+      prologue(h);
+      ds[nd] = conv2_desc(h.site, *h.cw2);
+      if (rf) ds[nd].w.n_tiles = 0;   // (all outputs of a torsion conv are scalars: k_convz serves every row)
+      zs[nd] = convz_desc(h.site, *h.cz, 2 * NS);
+      Ws[nd++] = h.cw->W;
     }
-    if (do_t) {
-      launch_bond_attr(lx, D, B->bond_src, B->bond_dst, B->tor_bond, 0, B->NTOR, w.tor_attr, st);
-      MlpArgs a; memset(&a, 0, sizeof a);
-      a.w = m->tor_edge_emb; a.mode = IN_G; a.n_rows_dev = T.n_edges; a.n_rows_max = T.cap; a.dist = T.dist;
-      a.gs_offset = m->gs_lig_off; a.gs_coeff = m->gs_lig_c; a.out = T.emb;
-      launch_mlp(a, st);
-      ds[nd] = conv2_desc(m->tor_conv2, T.n_edges, T.cap, T.gth, T.emb, T.sh, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, w.msg[0]);
-      if (rf) { ds[nd].w.n_tiles = 0; zs[nd] = convz_desc(ds[nd], m->tor_convz, T.tgt, 2 * NS, T.chunk_es, T.chunk_gl, T.chunk0 + G, T.chunk_cap, w.xmax_l); }   // (all outputs of a torsion conv are scalars)
-      Ws[nd++] = m->tor_conv.W;
+    if (nd) conv2_call(m, ds, Ws, nd, st, fallback, rf ? zs : nullptr);
+    for (const TorHead& h : heads)
+      if (h.on) epilogue(h);
+  } else {         // one k_conv per head
+    for (const TorHead& h : heads) {
+      if (!h.on) continue;
+      prologue(h);
+      conv_call(m, *h.cw, h.site, st);
+      epilogue(h);
     }
-    if (do_s) {
-      launch_bond_attr(ax, D, B->sc_bond, nullptr, nullptr, 2, B->NSC, w.sc_attr, st);
-      MlpArgs a; memset(&a, 0, sizeof a);
-      a.w = m->sc_edge_emb; a.mode = IN_G; a.n_rows_dev = S.n_edges; a.n_rows_max = S.cap; a.dist = S.dist;
-      a.gs_offset = m->gs_atom_off; a.gs_coeff = m->gs_atom_c; a.out = S.emb;
-      launch_mlp(a, st);
-      ds[nd] = conv2_desc(m->sc_conv2, S.n_edges, S.cap, S.gth, S.emb, S.sh, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, w.msg[1]);
-      if (rf) { ds[nd].w.n_tiles = 0; zs[nd] = convz_desc(ds[nd], m->sc_convz, S.tgt, 2 * NS, S.chunk_es, S.chunk_gl, S.chunk0 + G, S.chunk_cap, w.xmax_a); }
-      Ws[nd++] = m->sc_conv.W;
-    }
-    if (nd) conv2_call(m, ds, Ws, nd, st, (m->layer_fallback >> 31) & 1u, rf ? zs : nullptr);
-    if (do_t) {
-      launch_reduce_ln(w.msg[0], T.row_start, T.row_cnt, B->NTOR, 2 * NS, m->tor_conv.ln, nullptr, 0, w.tor_feat, 2 * NS, 2, st, rf ? T.seg_first : nullptr, rf ? convz_sc_lanes(m->tor_convz) : 0);
-      launch_tor_final(w.tor_feat, m->tor_final, c->tor_score_norm2, cfg.scale_by_sigma, B->NTOR, out->tor, st);
-    }
-    if (do_s) {
-      launch_reduce_ln(w.msg[1], S.row_start, S.row_cnt, B->NSC, 2 * NS, m->sc_conv.ln, nullptr, 0, w.sc_feat, 2 * NS, 2, st, rf ? S.seg_first : nullptr, rf ? convz_sc_lanes(m->sc_convz) : 0);
-      launch_tor_final(w.sc_feat, m->sc_final, c->sc_tor_score_norm2, cfg.scale_by_sigma, B->NSC, out->sc_tor, st);
-    }
-    return DBFR_OK;
-  }
-  // ---- ligand torsion head
-  if (B->NTOR > 0) {
-    const EdgeSet& T = w.set[SET_TOR];
-    launch_bond_attr(lx, D, B->bond_src, B->bond_dst, B->tor_bond, 0, B->NTOR, w.tor_attr, s_tor);
-    {
-      MlpArgs a; memset(&a, 0, sizeof a);
-      a.w = m->tor_edge_emb; a.mode = IN_G; a.n_rows_dev = T.n_edges; a.n_rows_max = T.cap; a.dist = T.dist;
-      a.gs_offset = m->gs_lig_off; a.gs_coeff = m->gs_lig_c; a.out = T.emb;
-      launch_mlp(a, s_tor);
-    }
-    conv_call(m, m->tor_conv, T.n_edges, T.cap, T.tgt, T.gth, T.emb, T.sh, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, msg_tor, s_tor);
-    launch_reduce_ln(msg_tor, T.row_start, T.row_cnt, B->NTOR, 2 * NS, m->tor_conv.ln, nullptr, 0, w.tor_feat, 2 * NS, 2, s_tor);
-    launch_tor_final(w.tor_feat, m->tor_final, c->tor_score_norm2, cfg.scale_by_sigma, B->NTOR, out->tor, s_tor);
-  }
-  // ---- side-chain torsion head
-  if (!cfg.no_sc_torsion && B->NSC > 0) {
-    const EdgeSet& S = w.set[SET_SC];
-    launch_bond_attr(ax, D, B->sc_bond, nullptr, nullptr, 2, B->NSC, w.sc_attr, s_sc);
-    {
-      MlpArgs a; memset(&a, 0, sizeof a);
-      a.w = m->sc_edge_emb; a.mode = IN_G; a.n_rows_dev = S.n_edges; a.n_rows_max = S.cap; a.dist = S.dist;
-      a.gs_offset = m->gs_atom_off; a.gs_coeff = m->gs_atom_c; a.out = S.emb;
-      launch_mlp(a, s_sc);
-    }
-    conv_call(m, m->sc_conv, S.n_edges, S.cap, S.tgt, S.gth, S.emb, S.sh, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, msg_sc, s_sc);
-    launch_reduce_ln(msg_sc, S.row_start, S.row_cnt, B->NSC, 2 * NS, m->sc_conv.ln, nullptr, 0, w.sc_feat, 2 * NS, 2, s_sc);
-    launch_tor_final(w.sc_feat, m->sc_final, c->sc_tor_score_norm2, cfg.scale_by_sigma, B->NSC, out->sc_tor, s_sc);
-  }
-  if (fork_heads) {
-    HIPCHECK(hipEventRecord(m->ev_join[0], s_tor));
-    HIPCHECK(hipEventRecord(m->ev_join[1], s_sc));
-    HIPCHECK(hipStreamWaitEvent(st, m->ev_join[0], 0));
-    HIPCHECK(hipStreamWaitEvent(st, m->ev_join[1], 0));
   }
   return DBFR_OK;
 }
@@ -1487,18 +1441,8 @@ static int begin(dbfr_model* m, const dbfr_batch* B, void* workspace, size_t wby
   rc = plan(m, B, lim, (char*)workspace, wbytes, w, &needb);
   if (rc) return rc;
   if (needb > wbytes) return fail(DBFR_ERR_ARG, "workspace too small: need " + std::to_string(needb) + " bytes");
-  if (w->multi && !m->streams_ready) {
-    for (int i = 0; i < 3; ++i) {
-      HIPCHECK(hipStreamCreateWithFlags(&m->side[i], hipStreamNonBlocking));
-      HIPCHECK(hipEventCreateWithFlags(&m->ev_join[i], hipEventDisableTiming));
-    }
-    HIPCHECK(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
-    HIPCHECK(hipEventCreateWithFlags(&m->ev_a, hipEventDisableTiming));
-    HIPCHECK(hipEventCreateWithFlags(&m->ev_b, hipEventDisableTiming));
-    m->streams_ready = true;
-  }
   HIPCHECK(hipMemsetAsync(workspace, 0, 1024, st));   // err @0, counters @256, n_edges6 @512
-  if (w->conv2 || m->gemm_split || m->conv2_layers > 0) HIPCHECK(hipMemsetAsync(m->queue, 0, 16, st));   // the kernel re-arms it itself; this covers an aborted run
+  if (w->conv2) HIPCHECK(hipMemsetAsync(m->queue, 0, 16, st));   // the kernel re-arms it itself; this covers an aborted run
   launch_set_int(w->n_edges6 + 7, B->NL, st);           // the centre set has exactly one edge per ligand atom
   launch_batch_vectors(*B, w->lig_batch, w->atm_batch, w->is_cab, w->n_cab, w->tor_batch, w->sc_batch, st);
   return DBFR_OK;
@@ -1721,6 +1665,14 @@ static const ConvW* pick_conv(const dbfr_model* m, int layer, int family) {
   if (layer == -3 && !m->cfg.no_sc_torsion) return &m->sc_conv;
   return nullptr;
 }
+// ... and the k_conv2 / k_convz layouts of the same conv (a K=144 conv: not the final one).  w2v, the vector-output rows alone, is null for the
+// torsion convs: all their outputs are scalars.
+struct Conv144 { const ConvW2* w2; const ConvW2* w2v; const ConvZ* z; };
+static Conv144 pick_conv144(const dbfr_model* m, int layer, int family) {
+  if (layer >= 0) return {&m->layer2[layer][family], &m->layer2v[layer][family], &m->layerz[layer][family]};
+  if (layer == -2) return {&m->tor_conv2, nullptr, &m->tor_convz};
+  return {&m->sc_conv2, nullptr, &m->sc_convz};
+}
 
 static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t family, int32_t n_edges, const int32_t* n_edges_dev,
                           const int32_t* tgt, const int32_t* gth, const float* emb, const float* sh, const float* tab1, int32_t ld1,
@@ -1730,13 +1682,14 @@ static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t fami
   g_launch_err = false;
   const ConvW* cw = pick_conv(m, layer, family);
   if (!cw) return fail(DBFR_ERR_ARG, "no such conv");
+  ConvSite site = flat_site(n_edges_dev, n_edges, tgt, gth, emb, sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg);
   if (conv2) {
     if (cw->K != 144) return fail(DBFR_ERR_ARG, "k_conv2 serves the K=144 convs");
-    const ConvW2* cw2 = layer >= 0 ? &m->layer2[layer][family] : layer == -2 ? &m->tor_conv2 : &m->sc_conv2;
-    const bool deep = cw2->f16_depth > f16_depth_ok();
+    const Conv144 c2 = pick_conv144(m, layer, family);
+    const bool deep = c2.w2->f16_depth > f16_depth_ok();
     const bool rf = m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !deep;   // (the message buffer then holds segment sums in the segments' first rows: include/dbfr.h)
-    Conv2Desc d = conv2_desc(rf && layer >= 0 ? m->layer2v[layer][family] : *cw2, n_edges_dev, n_edges, gth, emb, sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg);
-    if (rf && layer < 0) d.w.n_tiles = 0;
+    Conv2Desc d = conv2_desc(site, rf && c2.w2v ? *c2.w2v : *c2.w2);
+    if (rf && !c2.w2v) d.w.n_tiles = 0;
     // k_convz's chunk table for this flat edge list, in a scratch buffer the hook keeps (test hook: one caller at a time): the list is cut every
     // 2048 edges as if those were graphs (parallel walk)
     static int* scratch_dev[16] = {nullptr}; static size_t scratch_dev_ints[16] = {0};   // (per device: the hook may be driven on several)
@@ -1755,14 +1708,15 @@ static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t fami
       }
       launch_flat_chunks(tgt, n_edges_dev, n_edges, span, n_span, scratch, ccap, scratch + n_span + 1, scratch + n_span + 1 + ccap, (hipStream_t)hip_stream);
     }
-    const ConvZDesc z = convz_desc(d, layer >= 0 ? m->layerz[layer][family] : layer == -2 ? m->tor_convz : m->sc_convz, tgt, cw->D_out,
-                                   scratch ? scratch + n_span + 1 : nullptr, scratch ? scratch + n_span + 1 + ccap : nullptr, scratch ? scratch + n_span : nullptr, ccap);
+    if (scratch) { site.chunk_es = scratch + n_span + 1; site.chunk_gl = scratch + n_span + 1 + ccap; site.n_chunks = scratch + n_span; }
+    site.max_chunks = ccap;
+    const ConvZDesc z = convz_desc(site, *c2.z, cw->D_out);
     const int W = cw->W;
     // (k_convz writes the scalar-output columns of a segment's first row only; the hook's documented layout has zeros in the other rows)
     if (rf) HIPCHECK(hipMemsetAsync(msg, 0, (size_t)n_edges * cw->D_out * sizeof(float), (hipStream_t)hip_stream));
     conv2_call(m, &d, &W, 1, (hipStream_t)hip_stream, deep, rf ? &z : nullptr);
   } else {
-    conv_call(m, *cw, n_edges_dev, n_edges, tgt, gth, emb, sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg, (hipStream_t)hip_stream);
+    conv_call(m, *cw, site, (hipStream_t)hip_stream);
   }
   HIPCHECK(hipGetLastError());
   return take_launch_error();
@@ -1822,7 +1776,7 @@ extern "C" int dbfr_test_reduce_ln2(dbfr_model* m, int32_t layer, int32_t family
   unsigned long long lanes = 0;
   if (seg_first) {
     if (layer == -1 || cw->K != 144) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln2: seg_first with a conv that has no reduce-first form");
-    lanes = convz_sc_lanes(layer >= 0 ? m->layerz[layer][family] : layer == -2 ? m->tor_convz : m->sc_convz);
+    lanes = convz_sc_lanes(*pick_conv144(m, layer, family).z);
   }
   launch_reduce_ln(msg, row_start, row_cnt, n_nodes, cw->D_out, cw->ln, old, d_old, out, cw->D_out, mode, (hipStream_t)hip_stream, seg_first, lanes);
   HIPCHECK(hipGetLastError());

@@ -99,7 +99,7 @@ class DiffBindFRHIP(nn.Module):
         recs, steps = self.schedule()
         T = len(recs) if stop is None else max(1, min(int(stop), len(recs)))
         d = pb.dims
-        with torch.cuda.device(dev):        # everything the library creates (streams, events, weights) follows the current device
+        with torch.cuda.device(dev):        # everything the library creates (events, weights) follows the current device
             a14 = torch.zeros(d["NR"], 14, 3, device=dev)
             traj_l = torch.empty(T, d["NL"], 3, device=dev) if visualize else None
             traj_a = torch.empty(T, d["NR"], 14, 3, device=dev) if visualize else None

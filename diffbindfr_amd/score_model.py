@@ -349,7 +349,7 @@ class TensorProductModelHIP(nn.Module):
                    tor=torch.empty(max(pb.dims["NTOR"], 1), device=dev), sc=torch.empty(max(pb.dims["NSC"], 1), device=dev))
         cond = L.Cond(*(C.c_void_p(x.data_ptr()) for x in (t, tr_sigma, rot_score_norm, tor_n2, sc_n2)))
         sc = L.Scores(*(C.c_void_p(out[k].data_ptr()) for k in ("tr", "rot", "tor", "sc")))
-        with torch.cuda.device(dev):            # streams, events and allocations of the library follow the current device
+        with torch.cuda.device(dev):            # events and allocations of the library follow the current device
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             while True:
                 ws = self.workspace(pb, dev)

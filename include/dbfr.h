@@ -1252,8 +1252,8 @@ int dbfr_test_pack_f16_depth(const float* frag, const float* bias, int32_t n_til
  * the launch stream when profiling is enabled.  conv_flops = algorithmic FLOP
  * (2K(K+W) per edge); ref_form_bytes = HBM bytes the reference's two-kernel form
  * of the same launches would move (4(W+D_in+9)+16 per edge).        */
-/* on = 1: events + counters, the independent convs of a layer serialised on the caller's stream so that each is timed
- * alone; on = 2: counters only (launch pattern as in production); 0: off.                                        */
+/* on = 1: events around every fused-conv launch + counters; on = 2: counters only; 0: off.  The launch pattern is the
+ * same in all three: every kernel runs on the caller's stream.                                                   */
 int dbfr_profile_enable(dbfr_model* m, int32_t on);
 int dbfr_profile_read(dbfr_model* m, double* conv_ms, int64_t* conv_launches, double* conv_flops,
                       double* ref_form_bytes, int32_t reset);

@@ -111,11 +111,12 @@ bool dbfr_launch_check(hipError_t e, const char* what) {
   return true;
 }
 // entry points call this behind their launches: a launcher that gave up (dbfr_launch_check) makes the call fail with DBFR_ERR_HIP
-static int take_launch_error() {
+int dbfr_take_launch_error() {
   if (!g_launch_err) return DBFR_OK;
   g_launch_err = false;
   return DBFR_ERR_HIP;
 }
+static int take_launch_error() { return dbfr_take_launch_error(); }
 int dbfr_current_cu_count() {
   static std::atomic<int> cache[64];                     // (zero-initialised; host threads driving different devices may fill it concurrently)
   int dev = 0;

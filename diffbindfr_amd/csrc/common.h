@@ -230,3 +230,5 @@ int dbfr_current_cu_count();
 // A kernel launcher could not prepare its launch (e.g. hipFuncSetAttribute refused the LDS size): recorded on this thread and returned
 // as DBFR_ERR_HIP by the entry point that issued the launch (api.cpp: take_launch_error).  Returns true when `e` is an error.
 bool dbfr_launch_check(hipError_t e, const char* what);
+// DBFR_ERR_HIP once after a dbfr_launch_check that failed on this thread (and clears the record), DBFR_OK otherwise.
+int dbfr_take_launch_error();

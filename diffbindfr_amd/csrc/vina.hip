@@ -14,11 +14,25 @@
 // in the order of k_init_ligand (torsions in tor_bond order about the current bond axis, then the rotation about the
 // centroid, then the translation), and the gradient with respect to those variables is exact: a reverse pass through the
 // torsion sequence (the adjoint of each rotation, including the dependence of later axes on earlier torsions).
+//
+// Flexible pocket side chains (dbfr_vina_flex_*): the same device functions, instantiated a second time with larger capacities
+// (VinaShared<V_FLEX_MAX_TOR>, dynamic LDS).  The pose's flexible receptor atoms become movable slots nl .. nl + nf - 1 behind the
+// ligand's, every fixed end of a flexible torsion's axis (CA, CB) a DUMMY-typed anchor slot behind those that nothing moves; the
+// flexible torsions follow the ligand's in q.  The pair matrix carries ligand-flexible pairs (E_inter) and the allowed
+// flexible-flexible pairs (E_rec); flexible atoms are left out of the candidate list, and a candidate carries its receptor index
+// so that a flexible atom skips the partners on its exclusion list.  Nothing here knows an amino acid: diffbindfr_amd/vina.py
+// (flex_topology) turns residues into these lists.  Everything flexible sits behind `if constexpr (SH::kFlex)`: the rigid
+// instantiation keeps its LDS, its occupancy and, bit for bit, its results (its register allocation moved a little:
+// profiles/r17_vinaflex_resource_usage.txt).
 #include "common.h"
+#include <algorithm>
 
 #define V_MAX_NL 256
 #define V_MAX_TOR 58                  // 6 + 58 = 64 variables: the inverse Hessian (64 x 64 fp32) stays in LDS
-#define V_MAX_VAR (6 + V_MAX_TOR)
+#define V_FLEX_MAX_TOR 122            // the flexible instantiation: 6 + 122 = 128 variables, a 64 KB inverse Hessian in dynamic LDS
+#define V_FLEX_MAX_EXCL 32            // receptor atoms within 3 bonds of a flexible atom (pocketcheck's limit)
+#define V_FLEX_MAX_NA 8192            // pocket atoms of a pose (the flexible-atom bit set)
+#define V_DUMMY 16
 #define V_THREADS 256
 #define V_WAVES (V_THREADS / 64)
 #define V_CUTOFF 8.0f
@@ -61,27 +75,40 @@ struct VinaArgs {
   int* iters;              // [G] or null
   const float* q_rigid;    // [G,6] starting variables (score at q) or null = 0
   const float* q_tor;      // [NTOR] or null = 0
+  // flexible instantiation only (dbfr_vina_flex_in and the flexible outputs)
+  const int32_t *f_ptr, *f_atom, *ft_ptr, *ft_bc, *turn_ptr, *turn, *excl_ptr, *excl;
+  const float* q_flex;     // [NFT] or null = 0
+  float *rec_out, *q_flex_out, *grad_flex;
 };
 
-struct VinaShared {
+template <bool F> struct VinaFlexShared {};
+template <> struct VinaFlexShared<true> {
+  uint32_t fm[V_FLEX_MAX_NA / 32];   // the pocket atoms that are flexible in this pose
+  int fa[V_MAX_NL];                  // pocket index of flexible atom r (slot nl + r)
+};
+template <int MT> struct VinaShared : VinaFlexShared<(MT > V_MAX_TOR)> {
+  static constexpr bool kFlex = MT > V_MAX_TOR;
+  static constexpr int kMaxVar = 6 + MT;
   float x0[3][V_MAX_NL];   // starting conformation
   float y[3][V_MAX_NL];    // after the torsions (before the rigid motion)
   float x[3][V_MAX_NL];    // current positions
   float g[3][V_MAX_NL];    // dE/dx, then the adjoint of y
   float xr[3][V_MAX_NL];   // positions at the last candidate collection
   uint32_t pm[V_MAX_NL][V_MAX_NL / 32];   // intra pairs, symmetric
-  uint32_t tm[V_MAX_TOR][V_MAX_NL / 32];  // rot_node_mask rows
+  uint32_t tm[MT][V_MAX_NL / 32];         // rot_node_mask rows
   int8_t lt[V_MAX_NL];
-  int tu[V_MAX_TOR], tv[V_MAX_TOR];
-  float tQ[V_MAX_TOR][9], tp[V_MAX_TOR][3], ta[V_MAX_TOR][3], tL[V_MAX_TOR];
-  float H[V_MAX_VAR * V_MAX_VAR];
-  float p[V_MAX_VAR], gp[V_MAX_VAR], d[V_MAX_VAR], pn[V_MAX_VAR], gn[V_MAX_VAR], hy[V_MAX_VAR];
+  int tu[MT], tv[MT];
+  float tQ[MT][9], tp[MT][3], ta[MT][3], tL[MT];
+  float H[kMaxVar * kMaxVar];
+  float p[kMaxVar], gp[kMaxVar], d[kMaxVar], pn[kMaxVar], gn[kMaxVar], hy[kMaxVar];
   double red[V_WAVES][8];
   float rf[V_WAVES][8];
   float R[9], c[3], sc[8];
-  double e[6];
+  double e[kFlex ? 8 : 6];  // five inter terms, intra (, E_rec)
   int ncand, flag;
 };
+static_assert(sizeof(VinaShared<V_MAX_TOR>) == 48280, "the rigid instantiation's LDS struct (and with it k_vina's occupancy) must not change");
+static_assert(sizeof(VinaShared<V_FLEX_MAX_TOR>) <= 160 * 1024 - 64, "the flexible instantiation must fit the gfx950 workgroup LDS limit");
 
 __device__ __forceinline__ float wsum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -104,7 +131,7 @@ __device__ void rotvec_to_mat(float vx, float vy, float vz, float* R) {
 }
 
 // Sum of v[0..5] over the block (fixed order: wave butterfly, then waves 0..3); every thread gets the result in out.
-__device__ void block_sum6(VinaShared& S, const float* v, float* out) {
+template <class SH> __device__ void block_sum6(SH& S, const float* v, float* out) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   float r[6];
   for (int k = 0; k < 6; ++k) r[k] = wsum(v[k]);
@@ -143,11 +170,12 @@ __device__ __forceinline__ float pair_terms(int ti, int tj, float r, float* t5) 
   return de;
 }
 
-// Candidate collection: receptor atoms (pocket of graph g, then its extra atoms) within 8 A + margin of any ligand atom.
-__device__ void collect(const VinaArgs& A, VinaShared& S, int g, int nl) {
+// Candidate collection: fixed receptor atoms (pocket of graph g, then its extra atoms) within 8 A + margin of any of the ns slots
+// (the ligand atoms; with flexible side chains also their atoms, which are no candidates themselves).
+template <class SH> __device__ void collect(const VinaArgs& A, SH& S, int g, int ns) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   float4* out = A.cand + (size_t)g * A.cap;
-  for (int i = tid; i < nl; i += V_THREADS) { S.xr[0][i] = S.x[0][i]; S.xr[1][i] = S.x[1][i]; S.xr[2][i] = S.x[2][i]; }
+  for (int i = tid; i < ns; i += V_THREADS) { S.xr[0][i] = S.x[0][i]; S.xr[1][i] = S.x[1][i]; S.xr[2][i] = S.x[2][i]; }
   const float lim = V_CUTOFF + A.margin, lim2 = lim * lim;
   const int a0 = A.b.atm_ptr[g], na = A.b.atm_ptr[g + 1] - a0;
   const int e0 = A.in.ext_ptr ? A.in.ext_ptr[g] : 0, ne = A.in.ext_ptr ? A.in.ext_ptr[g + 1] - e0 : 0;
@@ -163,9 +191,15 @@ __device__ void collect(const VinaArgs& A, VinaShared& S, int g, int nl) {
       const float* pp; int t;
       if (c < na) { pp = A.b.rec_pos + 3 * (size_t)(a0 + c); t = A.in.rec_type[a0 + c]; }
       else { pp = A.in.ext_pos + 3 * (size_t)(e0 + c - na); t = A.in.ext_type[e0 + c - na]; }
-      if (t >= 0 && t < V_NTYPES) {
+      const bool typed = t >= 0 && t < V_NTYPES;
+      bool fixed = true;
+      if constexpr (SH::kFlex) {   // flexible atoms are slots, not candidates; a candidate carries its receptor index above its type
+        fixed = c >= na || !((S.fm[c >> 5] >> (c & 31)) & 1u);
+        t |= c << 5;
+      }
+      if (typed && fixed) {
         rec = make_float4(pp[0], pp[1], pp[2], __int_as_float(t));
-        for (int i = 0; i < nl && !keep; ++i) {
+        for (int i = 0; i < ns && !keep; ++i) {
           float dx = rec.x - S.xr[0][i], dy = rec.y - S.xr[1][i], dz = rec.z - S.xr[2][i];
           keep = dx * dx + dy * dy + dz * dz < lim2;
         }
@@ -187,40 +221,56 @@ __device__ void collect(const VinaArgs& A, VinaShared& S, int g, int nl) {
 }
 
 // Energy terms into S.e[0..5] (five weighted inter terms, intra) and dE/dx into S.g.  Collects again when needed.
-__device__ void evaluate(const VinaArgs& A, VinaShared& S, int g, int nl) {
+// Flexible: slots nl .. ns - 1 are receptor atoms; S.e[6] = E_rec (flexible-fixed pairs off the exclusion list, allowed
+// flexible-flexible pairs); a ligand-flexible pair counts in the inter terms, from the ligand atom's side.
+template <class SH> __device__ void evaluate(const VinaArgs& A, SH& S, int g, int nl, int ns) {
+  constexpr int NE = SH::kFlex ? 7 : 6;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // has an atom moved by more than margin/2 since the last collection?
   int moved = 0;
   const float h2 = 0.25f * A.margin * A.margin;
-  for (int i = tid; i < nl; i += V_THREADS) {
+  for (int i = tid; i < ns; i += V_THREADS) {
     float dx = S.x[0][i] - S.xr[0][i], dy = S.x[1][i] - S.xr[1][i], dz = S.x[2][i] - S.xr[2][i];
     moved |= dx * dx + dy * dy + dz * dz > h2;
   }
   if (__syncthreads_or(moved || S.flag)) {
-    collect(A, S, g, nl);
+    collect(A, S, g, ns);
     if (threadIdx.x == 0) S.flag = 0;
   }
   const float4* cand = A.cand + (size_t)g * A.cap;
   const int nc = S.ncand;
-  double acc[6] = {0, 0, 0, 0, 0, 0};
-  for (int i = w; i < nl; i += V_WAVES) {
+  double acc[NE];
+  for (int k = 0; k < NE; ++k) acc[k] = 0.0;
+  for (int i = w; i < ns; i += V_WAVES) {
     const int ti = S.lt[i];
     float gx = 0.f, gy = 0.f, gz = 0.f;
     if (ti >= 0 && ti < V_NTYPES) {
       const float xi = S.x[0][i], yi = S.x[1][i], zi = S.x[2][i];
+      int ex0 = 0, ex1 = 0;        // a flexible atom's exclusion list (wave-uniform)
+      if constexpr (SH::kFlex)
+        if (i >= nl) { const int f = A.f_ptr[g] + i - nl; ex0 = A.excl_ptr[f]; ex1 = A.excl_ptr[f + 1]; }
       for (int c = lane; c < nc; c += 64) {
         const float4 r4 = cand[c];
         const float dx = xi - r4.x, dy = yi - r4.y, dz = zi - r4.z;
         const float r2 = dx * dx + dy * dy + dz * dz;
         if (r2 >= V_CUTOFF * V_CUTOFF) continue;
+        int tj = __float_as_int(r4.w);
+        if constexpr (SH::kFlex) {
+          const int rj = tj >> 5;
+          tj &= 31;
+          bool skip = false;
+          for (int k = ex0; k < ex1; ++k) skip |= A.excl[k] == rj;
+          if (skip) continue;
+        }
         const float r = sqrtf(r2);
         float t5[5];
-        const float de = pair_terms(ti, __float_as_int(r4.w), r, t5);
-        for (int k = 0; k < 5; ++k) acc[k] += (double)t5[k];
+        const float de = pair_terms(ti, tj, r, t5);
+        if (SH::kFlex && i >= nl) acc[NE - 1] += (double)t5[0] + (double)t5[1] + (double)t5[2] + (double)t5[3] + (double)t5[4];
+        else for (int k = 0; k < 5; ++k) acc[k] += (double)t5[k];
         const float f = r > 0.f ? de / r : 0.f;
         gx += f * dx; gy += f * dy; gz += f * dz;
       }
-      for (int j = lane; j < nl; j += 64) {
+      for (int j = lane; j < ns; j += 64) {
         if (!((S.pm[i][j >> 5] >> (j & 31)) & 1u)) continue;
         const int tj = S.lt[j];
         if (tj < 0 || tj >= V_NTYPES) continue;
@@ -230,7 +280,10 @@ __device__ void evaluate(const VinaArgs& A, VinaShared& S, int g, int nl) {
         const float r = sqrtf(r2);
         float t5[5];
         const float de = pair_terms(ti, tj, r, t5);
-        if (j > i) acc[5] += (double)t5[0] + (double)t5[1] + (double)t5[2] + (double)t5[3] + (double)t5[4];
+        if (SH::kFlex && (i >= nl || j >= nl)) {
+          if (i < nl) { for (int k = 0; k < 5; ++k) acc[k] += (double)t5[k]; }
+          else if (j >= nl && j > i) acc[NE - 1] += (double)t5[0] + (double)t5[1] + (double)t5[2] + (double)t5[3] + (double)t5[4];
+        } else if (j > i) acc[5] += (double)t5[0] + (double)t5[1] + (double)t5[2] + (double)t5[3] + (double)t5[4];
         const float f = r > 0.f ? de / r : 0.f;
         gx += f * dx; gy += f * dy; gz += f * dz;
       }
@@ -238,11 +291,11 @@ __device__ void evaluate(const VinaArgs& A, VinaShared& S, int g, int nl) {
     gx = wsum(gx); gy = wsum(gy); gz = wsum(gz);
     if (lane == 0) { S.g[0][i] = gx; S.g[1][i] = gy; S.g[2][i] = gz; }
   }
-  for (int k = 0; k < 6; ++k) acc[k] = wsumd(acc[k]);
+  for (int k = 0; k < NE; ++k) acc[k] = wsumd(acc[k]);
   if (lane == 0)
-    for (int k = 0; k < 6; ++k) S.red[w][k] = acc[k];
+    for (int k = 0; k < NE; ++k) S.red[w][k] = acc[k];
   __syncthreads();
-  if (tid < 6) {
+  if (tid < NE) {
     double s = 0.0;
     for (int q = 0; q < V_WAVES; ++q) s += S.red[q][tid];
     S.e[tid] = s;
@@ -251,9 +304,10 @@ __device__ void evaluate(const VinaArgs& A, VinaShared& S, int g, int nl) {
 }
 
 // Positions from the variables q = (t[3], rotation vector[3], torsions[nt]): S.y (torsions applied to x0) and S.x.
-__device__ void rebuild(VinaShared& S, const float* q, int nl, int nt) {
+// The torsions act on all ns slots, the centroid and the rigid motion on the nl ligand atoms only.
+template <class SH> __device__ void rebuild(SH& S, const float* q, int nl, int ns, int nt) {
   const int tid = threadIdx.x;
-  for (int i = tid; i < nl; i += V_THREADS) { S.y[0][i] = S.x0[0][i]; S.y[1][i] = S.x0[1][i]; S.y[2][i] = S.x0[2][i]; }
+  for (int i = tid; i < ns; i += V_THREADS) { S.y[0][i] = S.x0[0][i]; S.y[1][i] = S.x0[1][i]; S.y[2][i] = S.x0[2][i]; }
   __syncthreads();
   for (int k = 0; k < nt; ++k) {
     if (tid == 0) {
@@ -270,7 +324,7 @@ __device__ void rebuild(VinaShared& S, const float* q, int nl, int nt) {
     if (q[6 + k] != 0.f) {
       const float* Q = S.tQ[k];
       const float* p = S.tp[k];
-      for (int i = tid; i < nl; i += V_THREADS)
+      for (int i = tid; i < ns; i += V_THREADS)
         if ((S.tm[k][i >> 5] >> (i & 31)) & 1u) {
           const float x = S.y[0][i] - p[0], y = S.y[1][i] - p[1], z = S.y[2][i] - p[2];
           S.y[0][i] = (Q[0] * x + Q[1] * y + Q[2] * z) + p[0];
@@ -288,10 +342,12 @@ __device__ void rebuild(VinaShared& S, const float* q, int nl, int nt) {
   if (tid == 0) rotvec_to_mat(q[3], q[4], q[5], S.R);
   __syncthreads();
   if (q[0] == 0.f && q[1] == 0.f && q[2] == 0.f && q[3] == 0.f && q[4] == 0.f && q[5] == 0.f) {   // no rigid motion: x = y exactly
-    for (int i = tid; i < nl; i += V_THREADS) { S.x[0][i] = S.y[0][i]; S.x[1][i] = S.y[1][i]; S.x[2][i] = S.y[2][i]; }
+    for (int i = tid; i < ns; i += V_THREADS) { S.x[0][i] = S.y[0][i]; S.x[1][i] = S.y[1][i]; S.x[2][i] = S.y[2][i]; }
     __syncthreads();
     return;
   }
+  if constexpr (SH::kFlex)
+    for (int i = nl + tid; i < ns; i += V_THREADS) { S.x[0][i] = S.y[0][i]; S.x[1][i] = S.y[1][i]; S.x[2][i] = S.y[2][i]; }
   for (int i = tid; i < nl; i += V_THREADS) {   // R (y - c) + c + t
     const float x = S.y[0][i] - S.c[0], y = S.y[1][i] - S.c[1], z = S.y[2][i] - S.c[2];
     S.x[0][i] = (S.R[0] * x + S.R[1] * y + S.R[2] * z) + S.c[0] + q[0];
@@ -302,7 +358,8 @@ __device__ void rebuild(VinaShared& S, const float* q, int nl, int nt) {
 }
 
 // Gradient with respect to q from S.g = dE/dx (consumes S.g and S.y).  At q = 0 this is the generalised gradient.
-__device__ void param_grad(VinaShared& S, const float* q, float* gq, int nl, int nt) {
+// Receptor slots (nl .. ns - 1) do not follow the rigid motion: their dE/dx is the adjoint of their y already.
+template <class SH> __device__ void param_grad(SH& S, const float* q, float* gq, int nl, int ns, int nt) {
   const int tid = threadIdx.x;
   float v[6] = {0, 0, 0, 0, 0, 0}, s6[6];
   if (tid < nl) {
@@ -342,7 +399,7 @@ __device__ void param_grad(VinaShared& S, const float* q, float* gq, int nl, int
   __syncthreads();
   for (int k = nt - 1; k >= 0; --k) {
     const float* p = S.tp[k];
-    const bool in = tid < nl && ((S.tm[k][tid >> 5] >> (tid & 31)) & 1u);
+    const bool in = tid < ns && ((S.tm[k][tid >> 5] >> (tid & 31)) & 1u);
     float t6[6] = {0, 0, 0, 0, 0, 0};
     if (in) {
       const float bx = S.g[0][tid], by = S.g[1][tid], bz = S.g[2][tid];
@@ -389,18 +446,114 @@ __device__ void param_grad(VinaShared& S, const float* q, float* gq, int nl, int
   }
 }
 
-__global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
-  __shared__ VinaShared S;
+// The pose's flexible receptor atoms, axis anchors, pairs and torsion masks into the slots behind the ligand's (see the head of
+// the file).  Returns the number of slots, or -1 (uniformly) when a list of the graph is inconsistent or exceeds a capacity.
+template <class SH> __device__ int flex_setup(const VinaArgs& A, SH& S, int g, int nl, int ntl, int na, int ne) {
+  const int tid = threadIdx.x;
+  const int a0 = A.b.atm_ptr[g];
+  const int f0 = A.f_ptr[g], nf = A.f_ptr[g + 1] - f0;
+  const int t0 = A.ft_ptr[g], ntf = A.ft_ptr[g + 1] - t0;
+  for (int i = tid; i < V_FLEX_MAX_NA / 32; i += V_THREADS) S.fm[i] = 0u;
+  __syncthreads();
+  int bad = 0;
+  for (int r = tid; r < nf; r += V_THREADS) {
+    const int a = A.f_atom[f0 + r];
+    if (a < 0 || a >= na) { bad = 1; continue; }
+    S.fa[r] = a;
+    bad |= (atomicOr(&S.fm[a >> 5], 1u << (a & 31)) >> (a & 31)) & 1u;   // listed twice
+    for (int c = 0; c < 3; ++c) S.x0[c][nl + r] = S.x[c][nl + r] = S.xr[c][nl + r] = A.b.rec_pos[3 * (size_t)(a0 + a) + c];
+    S.lt[nl + r] = A.in.rec_type[a0 + a];
+    const int e0 = A.excl_ptr[f0 + r], e1 = A.excl_ptr[f0 + r + 1];
+    bad |= e1 < e0 || e1 - e0 > V_FLEX_MAX_EXCL;
+  }
+  if (__syncthreads_or(bad)) return -1;
+  // the two ends of every flexible torsion's axis: a flexible atom's slot, or -1 - (pocket atom) for an anchor still to place
+  if (tid < 2 * ntf) {
+    const int k = tid >> 1, a = A.ft_bc[2 * (size_t)(t0 + k) + (tid & 1)];
+    int slot = -1 - a;
+    if (a < 0 || a >= na) { bad = 1; slot = 0; }
+    else if ((S.fm[a >> 5] >> (a & 31)) & 1u)
+      for (int r = 0; r < nf; ++r)
+        if (S.fa[r] == a) slot = nl + r;
+    if (tid & 1) S.tu[ntl + k] = slot; else S.tv[ntl + k] = slot;   // pivot b = v, direction b -> c = u - v
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int ns = nl + nf;
+    for (int k = ntl; k < ntl + ntf; ++k)
+      for (int end = 0; end < 2; ++end) {
+        int& s = end ? S.tu[k] : S.tv[k];
+        if (s >= 0) continue;
+        if (ns < V_MAX_NL) {
+          const int a = -1 - s;
+          for (int c = 0; c < 3; ++c) S.x0[c][ns] = S.x[c][ns] = S.xr[c][ns] = A.b.rec_pos[3 * (size_t)(a0 + a) + c];
+          S.lt[ns] = V_DUMMY;
+          s = ns;
+        } else s = 0;
+        ++ns;
+      }
+    S.ncand = ns;   // (the candidate count is not in use yet: it carries the slot count to the other threads)
+  }
+  __syncthreads();
+  const int ns = S.ncand;
+  if (tid < ntf) bad |= S.tu[ntl + tid] == S.tv[ntl + tid];
+  if (__syncthreads_or(bad || ns > V_MAX_NL)) return -1;
+  // pairs: every flexible atom with every ligand atom and every other flexible atom ...
+  const int nm = nl + nf;
+  for (int idx = tid; idx < nf * nm; idx += V_THREADS) {
+    const int s = nl + idx / nm, j = idx % nm;
+    if (j == s) continue;
+    atomicOr(&S.pm[s][j >> 5], 1u << (j & 31));
+    atomicOr(&S.pm[j][s >> 5], 1u << (s & 31));
+  }
+  __syncthreads();
+  // ... but the flexible atoms on its exclusion list
+  for (int r = tid; r < nf; r += V_THREADS) {
+    const int s = nl + r;
+    for (int k = A.excl_ptr[f0 + r]; k < A.excl_ptr[f0 + r + 1]; ++k) {
+      const int a = A.excl[k];
+      if (a < 0 || a >= na + ne) { bad = 1; continue; }
+      if (a >= na || !((S.fm[a >> 5] >> (a & 31)) & 1u)) continue;
+      for (int h = 0; h < nf; ++h)
+        if (S.fa[h] == a) {
+          atomicAnd(&S.pm[s][(nl + h) >> 5], ~(1u << ((nl + h) & 31)));
+          atomicAnd(&S.pm[nl + h][s >> 5], ~(1u << (s & 31)));
+        }
+    }
+  }
+  for (int k = 0; k < ntf; ++k) {
+    const int m0 = A.turn_ptr[t0 + k], m1 = A.turn_ptr[t0 + k + 1];
+    for (int m = m0 + tid; m < m1; m += V_THREADS) {
+      const int r = A.turn[m];
+      if (r < 0 || r >= nf) { bad = 1; continue; }
+      atomicOr(&S.tm[ntl + k][(nl + r) >> 5], 1u << ((nl + r) & 31));
+    }
+  }
+  if (__syncthreads_or(bad)) return -1;
+  return ns;
+}
+
+// A graph the kernel will not touch: NaN terms, iters = -1.
+template <int NT> __device__ __forceinline__ void refuse_pose(const VinaArgs& A, int g) {
+  if (threadIdx.x < NT && A.terms) A.terms[NT * (size_t)g + threadIdx.x] = __int_as_float(0x7fc00000);
+  if (threadIdx.x == 0 && A.iters) A.iters[g] = -1;
+}
+
+template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A, SH& S) {
+  constexpr int NT = SH::kFlex ? 10 : 8;   // terms per pose
   const int g = blockIdx.x, tid = threadIdx.x;
   const VinaBatch& b = A.b;
   const int l0 = b.lig_ptr[g], nl = b.lig_ptr[g + 1] - l0;
-  const int k0 = b.tor_ptr[g], nt = b.tor_ptr[g + 1] - k0;
+  const int k0 = b.tor_ptr[g], ntl = b.tor_ptr[g + 1] - k0;
+  int nt = ntl, ns = nl, nf = 0;
+  if constexpr (SH::kFlex) { nt += A.ft_ptr[g + 1] - A.ft_ptr[g]; nf = A.f_ptr[g + 1] - A.f_ptr[g]; }
   const int n = 6 + nt;
   const int na = b.atm_ptr[g + 1] - b.atm_ptr[g], ne = A.in.ext_ptr ? A.in.ext_ptr[g + 1] - A.in.ext_ptr[g] : 0;
-  if (nl <= 0 || nl > V_MAX_NL || nt < 0 || nt > V_MAX_TOR || na < 0 || ne < 0 || na + ne > A.cap) {
-    // the host-side maxima (max_nl, max_tor, max_na, max_ext) understated this graph: NaN results, nothing touched
-    if (tid < 8 && A.terms) A.terms[8 * (size_t)g + tid] = __int_as_float(0x7fc00000);
-    if (tid == 0 && A.iters) A.iters[g] = -1;
+  bool refuse = nl <= 0 || nl > V_MAX_NL || ntl < 0 || nt > SH::kMaxVar - 6 || na < 0 || ne < 0 || na + ne > A.cap;
+  if constexpr (SH::kFlex) refuse = refuse || nt < ntl || nf < 0 || nl + nf > V_MAX_NL || na > V_FLEX_MAX_NA;
+  if (refuse) {
+    // the host-side maxima (max_nl, max_tor, max_na, max_ext, ...) understated this graph: NaN results, nothing touched
+    refuse_pose<NT>(A, g);
     return;
   }
   for (int i = tid; i < nl; i += V_THREADS) {
@@ -410,6 +563,13 @@ __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
   for (int i = tid; i < V_MAX_NL * (V_MAX_NL / 32); i += V_THREADS) (&S.pm[0][0])[i] = 0u;
   for (int i = tid; i < nt * (V_MAX_NL / 32); i += V_THREADS) (&S.tm[0][0])[i] = 0u;
   __syncthreads();
+  if constexpr (SH::kFlex) {
+    ns = flex_setup(A, S, g, nl, ntl, na, ne);
+    if (ns < 0) {   // an inconsistent flexible list, or more slots than the stated maxima allow: NaN results, nothing touched
+      refuse_pose<NT>(A, g);
+      return;
+    }
+  }
   const int p0 = A.in.pair_ptr[g], np = A.in.pair_ptr[g + 1] - p0;
   for (int k = tid; k < np; k += V_THREADS) {
     const int i = A.in.pair_ij[2 * (size_t)(p0 + k)] - l0, j = A.in.pair_ij[2 * (size_t)(p0 + k) + 1] - l0;
@@ -417,26 +577,27 @@ __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
     atomicOr(&S.pm[i][j >> 5], 1u << (j & 31));   // integer bit sets: order-free
     atomicOr(&S.pm[j][i >> 5], 1u << (i & 31));
   }
-  for (int k = 0; k < nt; ++k) {
+  for (int k = 0; k < ntl; ++k) {
     const uint8_t* m = b.rot_mask + b.rot_mask_off[k0 + k];
     for (int i = tid; i < nl; i += V_THREADS)
       if (m[i]) atomicOr(&S.tm[k][i >> 5], 1u << (i & 31));
   }
   int bad = 0;
-  if (tid < nt) {
+  if (tid < ntl) {
     const int e = b.tor_bond[k0 + tid];
     const int u = b.bond_src[e] - l0, v = b.bond_dst[e] - l0;
     bad = u < 0 || u >= nl || v < 0 || v >= nl || u == v;
     S.tu[tid] = bad ? 0 : u; S.tv[tid] = bad ? 0 : v;
   }
   if (__syncthreads_or(bad)) {   // a torsion bond outside the graph's atoms: NaN results, nothing touched
-    if (tid < 8 && A.terms) A.terms[8 * (size_t)g + tid] = __int_as_float(0x7fc00000);
-    if (tid == 0 && A.iters) A.iters[g] = -1;
+    refuse_pose<NT>(A, g);
     return;
   }
-  for (int k = tid; k < V_MAX_VAR; k += V_THREADS) {
+  for (int k = tid; k < SH::kMaxVar; k += V_THREADS) {
     S.p[k] = 0.f;
-    S.pn[k] = k < 6 ? (A.q_rigid ? A.q_rigid[6 * (size_t)g + k] : 0.f) : (k < n && A.q_tor ? A.q_tor[k0 + k - 6] : 0.f);
+    S.pn[k] = k < 6 ? (A.q_rigid ? A.q_rigid[6 * (size_t)g + k] : 0.f) : (k < 6 + ntl && A.q_tor ? A.q_tor[k0 + k - 6] : 0.f);
+    if constexpr (SH::kFlex)
+      if (k >= 6 + ntl && k < n && A.q_flex) S.pn[k] = A.q_flex[A.ft_ptr[g] + k - 6 - ntl];
   }
   for (int i = tid; i < n * n; i += V_THREADS) S.H[i] = (i / n == i % n) ? 1.f : 0.f;
   if (tid == 0) S.flag = 1;   // collect the candidates at the first evaluation
@@ -445,12 +606,16 @@ __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
   // budget): phase 0 = the start q = 0, 1 = a line-search trial at pn = p + alpha d, 2 = back to p after a stalled search.
   int phase = 0, it = 0, ls = 0;
   bool identity = true;
-  double f = 0.0;
+  double f = 0.0, rec0 = 0.0;
   float alpha = 0.f, slope = 0.f;
   for (;;) {
-    rebuild(S, S.pn, nl, nt);
-    evaluate(A, S, g, nl);
-    const double fn = S.e[0] + S.e[1] + S.e[2] + S.e[3] + S.e[4] + S.e[5];
+    rebuild(S, S.pn, nl, ns, nt);
+    evaluate(A, S, g, nl, ns);
+    double fn = S.e[0] + S.e[1] + S.e[2] + S.e[3] + S.e[4] + S.e[5];
+    if constexpr (SH::kFlex) {
+      fn += S.e[6];
+      if (phase == 0) rec0 = S.e[6];
+    }
     if (phase == 2) break;
     bool take = phase == 0, redirect = false;
     if (phase == 1) {
@@ -473,7 +638,7 @@ __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
       }
     }
     if (take) {
-      param_grad(S, S.pn, S.gn, nl, nt);
+      param_grad(S, S.pn, S.gn, nl, ns, nt);
       __syncthreads();
       if (phase == 1) {
         // BFGS update of the inverse Hessian with s = pn - p, y = gn - g (skipped unless s.y > 0)
@@ -539,22 +704,47 @@ __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
   }
   if (tid == 0) {
     if (A.terms) {
-      float* t = A.terms + 8 * (size_t)g;
+      float* t = A.terms + NT * (size_t)g;
       double inter = 0.0;
       for (int k = 0; k < 5; ++k) { t[k] = (float)S.e[k]; inter += S.e[k]; }
       t[5] = (float)S.e[5];
       t[6] = (float)(inter + S.e[5]);
-      t[7] = (float)(inter / (1.0 + (double)W_NROT * nt));
+      t[7] = (float)(inter / (1.0 + (double)W_NROT * ntl));
+      if constexpr (SH::kFlex) { t[6] = (float)(inter + S.e[5] + S.e[6]); t[8] = (float)S.e[6]; t[9] = (float)rec0; }
     }
     if (A.iters) A.iters[g] = it;
   }
   if (!A.minimize) {
     if (A.grad_rigid && tid < 6) A.grad_rigid[6 * (size_t)g + tid] = S.gp[tid];
-    if (A.grad_tor && tid < nt) A.grad_tor[k0 + tid] = S.gp[6 + tid];
+    if (A.grad_tor && tid < ntl) A.grad_tor[k0 + tid] = S.gp[6 + tid];
+    if constexpr (SH::kFlex)
+      if (A.grad_flex && tid < nt - ntl) A.grad_flex[A.ft_ptr[g] + tid] = S.gp[6 + ntl + tid];
   }
   if (A.pos_out)
     for (int i = tid; i < nl; i += V_THREADS)
       for (int c = 0; c < 3; ++c) A.pos_out[3 * (size_t)(l0 + i) + c] = S.x[c][i];
+  if constexpr (SH::kFlex) {
+    if (A.q_flex_out && tid < nt - ntl) A.q_flex_out[A.ft_ptr[g] + tid] = S.p[6 + ntl + tid];
+    if (A.rec_out) {   // the pocket atoms: fixed ones copied, flexible ones from their slots
+      const size_t a0 = (size_t)b.atm_ptr[g];
+      for (int c = tid; c < na; c += V_THREADS)
+        if (!((S.fm[c >> 5] >> (c & 31)) & 1u))
+          for (int k = 0; k < 3; ++k) A.rec_out[3 * (a0 + c) + k] = b.rec_pos[3 * (a0 + c) + k];
+      for (int r = tid; r < nf; r += V_THREADS)
+        for (int k = 0; k < 3; ++k) A.rec_out[3 * (a0 + S.fa[r]) + k] = S.x[k][nl + r];
+    }
+  }
+}
+
+template <int MT> __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A) {
+  using SH = VinaShared<MT>;
+  if constexpr (SH::kFlex) {   // 105 KB: dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize)
+    extern __shared__ __align__(16) unsigned char v_lds[];
+    vina_pose(A, *reinterpret_cast<SH*>(v_lds));
+  } else {
+    __shared__ SH S;
+    vina_pose(A, S);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -599,11 +789,86 @@ extern "C" int dbfr_vina_workspace_bytes(const dbfr_vina_in* in, size_t* bytes) 
   return DBFR_OK;
 }
 
+// ---- flexible side chains: the checks of dbfr_vina_flex_in
+static int vf_err(const std::string& s) { dbfr_set_error("dbfr_vina_flex: " + s); return DBFR_ERR_ARG; }
+
+// every list of the host copies: CSR shapes, index ranges, the per-graph counts against the stated maxima
+static int vina_flex_validate(const dbfr_vina_flex_in& in, const dbfr_vina_flex_in& h, int G, int max_na, int max_ext) {
+  if (!h.flex_ptr || !h.ftor_ptr || (in.n_flex > 0 && (!h.flex_atom || !h.excl_ptr)) || (in.n_ftor > 0 && (!h.ftor_bc || !h.turn_ptr)))
+    return vf_err("host: a host copy of an index array is missing");
+  if (h.flex_ptr[0] != 0 || h.ftor_ptr[0] != 0 || h.flex_ptr[G] != in.n_flex || h.ftor_ptr[G] != in.n_ftor)
+    return vf_err("flex_ptr / ftor_ptr must run from 0 to n_flex / n_ftor");
+  if (in.n_flex > 0 && h.excl_ptr[0] != 0) return vf_err("excl_ptr must start at 0");
+  if (in.n_ftor > 0 && h.turn_ptr[0] != 0) return vf_err("turn_ptr must start at 0");
+  if ((in.n_flex > 0 && h.excl_ptr[in.n_flex] > 0 && !h.excl) || (in.n_ftor > 0 && h.turn_ptr[in.n_ftor] > 0 && !h.turn))
+    return vf_err("host: a host copy of an index array is missing");
+  for (int g = 0; g < G; ++g) {
+    const int f0 = h.flex_ptr[g], nf = h.flex_ptr[g + 1] - f0, t0 = h.ftor_ptr[g], nt = h.ftor_ptr[g + 1] - t0;
+    const std::string where = "graph " + std::to_string(g) + ": ";
+    if (nf < 0 || nt < 0) return vf_err(where + "flex_ptr / ftor_ptr must not decrease");
+    if (nf > in.max_flex) return vf_err(where + std::to_string(nf) + " flexible atoms, max_flex states " + std::to_string(in.max_flex));
+    if (nt > in.max_ftor) return vf_err(where + std::to_string(nt) + " flexible torsions, max_ftor states " + std::to_string(in.max_ftor));
+    for (int r = 0; r < nf; ++r) {
+      const int a = h.flex_atom[f0 + r];
+      if (a < 0 || a >= max_na) return vf_err(where + "flexible atom " + std::to_string(a) + " is out of range (pocket atoms 0.." + std::to_string(max_na - 1) + ")");
+      if (r && a <= h.flex_atom[f0 + r - 1]) return vf_err(where + "flexible atoms must ascend");
+      const int e0 = h.excl_ptr[f0 + r], e1 = h.excl_ptr[f0 + r + 1];
+      if (e1 < e0) return vf_err(where + "excl_ptr must not decrease");
+      if (e1 - e0 > in.max_excl)
+        return vf_err(where + "exclusion list of " + std::to_string(e1 - e0) + " atoms, max_excl states " + std::to_string(in.max_excl) + " (at most 32)");
+      for (int k = e0; k < e1; ++k)
+        if (h.excl[k] < 0 || h.excl[k] >= max_na + max_ext)
+          return vf_err(where + "excluded receptor atom " + std::to_string(h.excl[k]) + " is out of range");
+    }
+    int anchors = 0;
+    for (int k = 0; k < nt; ++k) {
+      const int bc[2] = {h.ftor_bc[2 * (size_t)(t0 + k)], h.ftor_bc[2 * (size_t)(t0 + k) + 1]};
+      if (bc[0] == bc[1]) return vf_err(where + "a flexible torsion's axis needs two different atoms");
+      for (int a : bc) {
+        if (a < 0 || a >= max_na) return vf_err(where + "torsion axis atom " + std::to_string(a) + " is out of range (pocket atoms 0.." + std::to_string(max_na - 1) + ")");
+        anchors += !std::binary_search(h.flex_atom + f0, h.flex_atom + f0 + nf, a);
+      }
+      const int m0 = h.turn_ptr[t0 + k], m1 = h.turn_ptr[t0 + k + 1];
+      if (m1 < m0) return vf_err(where + "turn_ptr must not decrease");
+      for (int m = m0; m < m1; ++m)
+        if (h.turn[m] < 0 || h.turn[m] >= nf)
+          return vf_err(where + "turned atom " + std::to_string(h.turn[m]) + " is out of range (the graph's " + std::to_string(nf) + " flexible atoms)");
+    }
+    if (anchors > in.max_anchor)
+      return vf_err(where + std::to_string(anchors) + " axis anchors, max_anchor states " + std::to_string(in.max_anchor));
+  }
+  return DBFR_OK;
+}
+
+static int vina_flex_check(const dbfr_vina_flex_in* in, size_t* cap_per_pose) {
+  if (!in || !in->base) { dbfr_set_error("dbfr_vina_flex: null argument"); return DBFR_ERR_ARG; }
+  const int rc = vina_check(in->base, cap_per_pose);
+  if (rc) return rc;
+  const dbfr_batch* b = in->base->batch;
+  if (in->n_flex < 0 || in->n_ftor < 0 || in->max_flex < 0 || in->max_ftor < 0 || in->max_anchor < 0 || in->max_excl < 0)
+    return vf_err("counts and maxima must be >= 0");
+  if (b->max_nl + in->max_flex + in->max_anchor > V_MAX_NL)
+    return vf_err(std::to_string(b->max_nl) + " ligand atoms + " + std::to_string(in->max_flex) + " flexible atoms + " +
+                  std::to_string(in->max_anchor) + " axis anchors: at most 256 together");
+  if (6 + in->base->max_tor + in->max_ftor > 6 + V_FLEX_MAX_TOR)
+    return vf_err(std::to_string(6 + in->base->max_tor + in->max_ftor) + " variables (6 + " + std::to_string(in->base->max_tor) +
+                  " ligand torsions + " + std::to_string(in->max_ftor) + " flexible torsions): at most 128");
+  if (in->max_excl > V_FLEX_MAX_EXCL) return vf_err("exclusion lists of " + std::to_string(in->max_excl) + " atoms: at most 32");
+  if (!in->flex_ptr || !in->ftor_ptr || (in->n_flex > 0 && (!in->flex_atom || !in->excl_ptr)) ||
+      (in->n_ftor > 0 && (!in->ftor_bc || !in->turn_ptr)))
+    return vf_err("null device pointer in the input");
+  if (in->host) return vina_flex_validate(*in, *static_cast<const dbfr_vina_flex_in*>(in->host), b->G, b->max_na,
+                                          in->base->ext_ptr ? in->base->max_ext : 0);
+  return DBFR_OK;
+}
+
+struct VinaFlexOut { const float* q_flex; float *rec_out, *q_flex_out, *grad_flex; };
+
 static int vina_launch(const dbfr_vina_in* in, int minimize, const dbfr_vina_opts* opts, const float* q_rigid, const float* q_tor,
                        float* pos_out, float* terms, float* grad_rigid, float* grad_tor, int32_t* iters, void* ws, size_t ws_bytes,
-                       void* stream) {
+                       void* stream, const dbfr_vina_flex_in* flex = nullptr, const VinaFlexOut* fo = nullptr) {
   size_t cap;
-  int rc = vina_check(in, &cap);
+  int rc = flex ? vina_flex_check(flex, &cap) : vina_check(in, &cap);
   if (rc) return rc;
   const size_t need = (size_t)in->batch->G * cap * sizeof(float4);
   if (!ws || ws_bytes < need) {
@@ -629,7 +894,21 @@ static int vina_launch(const dbfr_vina_in* in, int minimize, const dbfr_vina_opt
   A.minimize = minimize;
   A.q_rigid = q_rigid; A.q_tor = in->batch->NTOR > 0 ? q_tor : nullptr;
   A.pos_out = pos_out; A.terms = terms; A.grad_rigid = grad_rigid; A.grad_tor = grad_tor; A.iters = iters;
-  hipLaunchKernelGGL(k_vina, dim3(in->batch->G), dim3(V_THREADS), 0, (hipStream_t)stream, A);
+  if (flex) {
+    A.f_ptr = flex->flex_ptr; A.f_atom = flex->flex_atom; A.ft_ptr = flex->ftor_ptr; A.ft_bc = flex->ftor_bc;
+    A.turn_ptr = flex->turn_ptr; A.turn = flex->turn; A.excl_ptr = flex->excl_ptr; A.excl = flex->excl;
+    A.q_flex = flex->n_ftor > 0 ? fo->q_flex : nullptr;
+    A.rec_out = fo->rec_out; A.q_flex_out = fo->q_flex_out; A.grad_flex = fo->grad_flex;
+    // (the LDS attribute is set on every launch: it is per device, and a process may drive several)
+    const size_t lds = sizeof(VinaShared<V_FLEX_MAX_TOR>);
+    if (dbfr_launch_check(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vina<V_FLEX_MAX_TOR>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                          "k_vina<flex>: hipFuncSetAttribute(MaxDynamicSharedMemorySize)"))
+      return dbfr_take_launch_error();
+    hipLaunchKernelGGL(k_vina<V_FLEX_MAX_TOR>, dim3(in->batch->G), dim3(V_THREADS), lds, (hipStream_t)stream, A);
+  } else {
+    hipLaunchKernelGGL(k_vina<V_MAX_TOR>, dim3(in->batch->G), dim3(V_THREADS), 0, (hipStream_t)stream, A);
+  }
   HIPCHECK(hipGetLastError());
   return DBFR_OK;
 }
@@ -649,4 +928,31 @@ extern "C" int dbfr_vina_score_at(const dbfr_vina_in* in, const float* q_rigid, 
 extern "C" int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* terms,
                                   int32_t* iters, void* workspace, size_t workspace_bytes, void* hip_stream) {
   return vina_launch(in, 1, opts, nullptr, nullptr, lig_pos_out, terms, nullptr, nullptr, iters, workspace, workspace_bytes, hip_stream);
+}
+
+extern "C" int dbfr_vina_flex_workspace_bytes(const dbfr_vina_flex_in* in, size_t* bytes) {
+  size_t cap;
+  int rc = vina_flex_check(in, &cap);
+  if (rc) return rc;
+  if (!bytes) { dbfr_set_error("dbfr_vina_flex_workspace_bytes: null argument"); return DBFR_ERR_ARG; }
+  *bytes = (size_t)in->base->batch->G * cap * sizeof(float4);
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_vina_flex_score_at(const dbfr_vina_flex_in* in, const float* q_rigid, const float* q_tor, const float* q_flex,
+                                       float* lig_pos_out, float* rec_pos_out, float* terms, float* grad_rigid, float* grad_tor,
+                                       float* grad_flex, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!in || !in->base) { dbfr_set_error("dbfr_vina_flex: null argument"); return DBFR_ERR_ARG; }
+  const VinaFlexOut fo = {q_flex, rec_pos_out, nullptr, grad_flex};
+  return vina_launch(in->base, 0, nullptr, q_rigid, q_tor, lig_pos_out, terms, grad_rigid, grad_tor, nullptr, workspace, workspace_bytes,
+                     hip_stream, in, &fo);
+}
+
+extern "C" int dbfr_vina_flex_minimize(const dbfr_vina_flex_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* rec_pos_out,
+                                       float* q_flex_out, float* terms, int32_t* iters, void* workspace, size_t workspace_bytes,
+                                       void* hip_stream) {
+  if (!in || !in->base) { dbfr_set_error("dbfr_vina_flex: null argument"); return DBFR_ERR_ARG; }
+  const VinaFlexOut fo = {nullptr, rec_pos_out, q_flex_out, nullptr};
+  return vina_launch(in->base, 1, opts, nullptr, nullptr, lig_pos_out, terms, nullptr, nullptr, iters, workspace, workspace_bytes, hip_stream,
+                     in, &fo);
 }

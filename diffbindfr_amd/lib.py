@@ -101,6 +101,12 @@ class VinaIn(C.Structure):
                 ("ext_type", C.c_void_p), ("max_tor", C.c_int32), ("max_ext", C.c_int32)]
 
 
+class VinaFlexIn(C.Structure):
+    _fields_ = [("base", C.c_void_p)] + [(n, C.c_void_p) for n in ("flex_ptr", "flex_atom", "ftor_ptr", "ftor_bc", "turn_ptr", "turn",
+                                                                   "excl_ptr", "excl")] + \
+               [(n, C.c_int32) for n in ("n_flex", "n_ftor", "max_flex", "max_ftor", "max_anchor", "max_excl")] + [("host", C.c_void_p)]
+
+
 class VinaOpts(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("grad_tol", C.c_float), ("margin", C.c_float)]
 
@@ -262,6 +268,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
+           "dbfr_vina_flex_workspace_bytes", "dbfr_vina_flex_score_at", "dbfr_vina_flex_minimize",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
@@ -343,6 +350,9 @@ def load():
     lib.dbfr_vina_score.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_vina_score_at.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_vina_minimize.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_vina_flex_workspace_bytes.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(C.c_size_t)]
+    lib.dbfr_vina_flex_score_at.argtypes = [C.POINTER(VinaFlexIn), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_vina_flex_minimize.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(VinaOpts), vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_pose_rmsd_matrix.argtypes = [C.POINTER(PoseRmsdIn), vp, vp]
     lib.dbfr_select_modes.argtypes = [C.POINTER(PoseRmsdIn), vp, vp, C.POINTER(ModesOpts), vp, vp, vp, vp]
     lib.dbfr_pose_check.argtypes = [C.POINTER(PoseCheckIn), C.POINTER(PoseCheckOpts), C.POINTER(PoseCheckOut), vp]

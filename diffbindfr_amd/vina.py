@@ -36,6 +36,9 @@ HIS ND1 / NE2 N_DA (the tautomer is not perceived), CYS SG / MET SD S_P; UNK has
 Minimisation: BFGS over 6 + n_tor variables per pose with a backtracking line search; positions are rebuilt from the
 starting conformation for every trial (torsions in tor_bond order, then the rotation about the centroid, then the
 translation: the order of the sampler's pose initialisation).  There is no CPU path: CPU tensors raise DbfrError.
+
+Flexible side chains (``flex_topology``, ``select_flexible``, ``VinaFlexBatch``, ``refine_entry_flex``, ``error_correct(flex_dist=)``):
+the pocket side chains near the ligand turn about their chi axes in the same minimisation; docs/vina.md states the model.
 """
 import ctypes as C
 import os
@@ -45,7 +48,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .lib import DbfrError, VinaIn, VinaOpts
+from .lib import DbfrError, VinaFlexIn, VinaIn, VinaOpts
 
 XS_NAMES = ["C_H", "C_P", "N_P", "N_D", "N_A", "N_DA", "O_P", "O_D", "O_A", "O_DA", "S_P", "P_P", "F_H", "Cl_H", "Br_H",
             "I_H", "DUMMY"]
@@ -53,6 +56,9 @@ XS = {n: i for i, n in enumerate(XS_NAMES)}
 DUMMY = XS["DUMMY"]
 TERMS = ["gauss1", "gauss2", "repulsion", "hydrophobic", "hbond", "intra", "objective", "affinity"]
 MAX_TORSIONS = 58
+FLEX_TERMS = TERMS + ["rec", "rec_start"]
+FLEX_MAX_SLOTS, FLEX_MAX_VARS, FLEX_MAX_EXCL = 256, 128, 32     # ligand + flexible atoms + axis anchors; 6 + all torsions
+FLEX_COLUMNS = ["ec_n_flex", "ec_flex_residues", "ec_sc_moved", "ec_rec_energy"]
 
 _HALOGEN = {"F": "F_H", "Cl": "Cl_H", "Br": "Br_H", "I": "I_H"}
 _VALENCE = {"N": 3, "O": 2}
@@ -402,9 +408,8 @@ def _entry_receptor(e, rec_table):
     return rec, rec_type, ext_pos, ext_type
 
 
-def refine_entry(e, lig_types=None, max_iters=100, grad_tol=1e-3):
-    """Minimise the final frame of every pose of one ``export.ComplexOutput`` against its pocket (the pose's side chains) and
-    the rest of the protein (static extra atoms).  Returns (minimised lig_pos [P, N, 3] absolute, terms [P, 8], iters [P])."""
+def _entry_batch(e, lig_types):
+    """(VinaBatch of the final frames of one entry, pocket centre on the device, P, N): the receptor of ``_entry_receptor``."""
     dev = e.ligand_traj.device
     if dev.type != "cuda":
         raise DbfrError("the Vina refinement runs on the GPU only: the trajectories are on " + str(dev))
@@ -420,29 +425,302 @@ def refine_entry(e, lig_types=None, max_iters=100, grad_tol=1e-3):
     pb = PoseBatch(lig, e.ligand_edge_index, rec)
     pairs = intra_pairs(N, e.ligand_edge_index, pb.tor_edge_mask)
     vb = VinaBatch(pb, [lig_types] * P, [pairs] * P, ext=([ext_pos] * P, [ext_type] * P), rec_types=np.tile(rec_type, P))
+    return vb, center, P, N
+
+
+def refine_entry(e, lig_types=None, max_iters=100, grad_tol=1e-3):
+    """Minimise the final frame of every pose of one ``export.ComplexOutput`` against its pocket (the pose's side chains) and
+    the rest of the protein (static extra atoms).  Returns (minimised lig_pos [P, N, 3] absolute, terms [P, 8], iters [P])."""
+    vb, center, P, N = _entry_batch(e, lig_types)
     pos, terms, iters = vb.minimize(max_iters=max_iters, grad_tol=grad_tol)
     return (pos.reshape(P, N, 3) + center), terms, iters
 
 
-def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0):
+# ------------------------------------------------------------------------------------------------ flexible side chains
+class VinaFlexBatch:
+    """The dbfr_vina_flex_in view of a ``VinaBatch`` and one flexible set per graph.  ``flex[g]`` is None (nothing flexible) or a
+    dict: ``atoms`` int [nf] graph-local pocket atom indices; ``tors`` a list of (b, c, turned) -- the axis as two pocket atoms
+    (pivot b, direction b -> c) and the pocket indices of the flexible atoms the torsion turns --, applied in list order;
+    ``excl`` a list per entry of ``atoms`` of the receptor atoms (pocket atoms first, then the extra atoms) within 3 bonds."""
+
+    def __init__(self, vb, flex):
+        self.vb = vb
+        pb = vb.pb
+        G, dev = pb.G, pb.lig_pos.device
+        if len(flex) != G:
+            raise DbfrError(f"{len(flex)} flexible sets for {G} graphs")
+        fp, tp = np.zeros(G + 1, np.int64), np.zeros(G + 1, np.int64)
+        atoms, bc, turn_ptr, turn, excl_ptr, excl, anchors = [], [], [0], [], [0], [], [0]
+        for g, f in enumerate(flex):
+            a = np.zeros(0, np.int64) if f is None else np.asarray(f["atoms"], np.int64).reshape(-1)
+            order = np.argsort(a, kind="stable")
+            a = a[order]
+            tors = [] if f is None else list(f["tors"])
+            ex = [] if f is None else [np.asarray(f["excl"][k], np.int64).reshape(-1) for k in order]
+            if len(ex) != a.size:
+                raise DbfrError(f"graph {g}: one exclusion list per flexible atom ({a.size})")
+            n_anchor = 0
+            for b, c, turned in tors:
+                t = np.asarray(turned, np.int64).reshape(-1)
+                r = np.searchsorted(a, t)
+                if t.size and (a.size == 0 or (r >= a.size).any() or (a[np.minimum(r, a.size - 1)] != t).any()):
+                    raise DbfrError(f"graph {g}: a torsion turns an atom that is not on the flexible list")
+                bc.append((int(b), int(c)))
+                turn += r.tolist()
+                turn_ptr.append(len(turn))
+                n_anchor += int(b not in a) + int(c not in a)
+            for x in ex:
+                excl += x.tolist()
+                excl_ptr.append(len(excl))
+            atoms += a.tolist()
+            anchors.append(n_anchor)
+            fp[g + 1], tp[g + 1] = fp[g] + a.size, tp[g] + len(tors)
+        host = dict(flex_ptr=fp, flex_atom=atoms, ftor_ptr=tp, ftor_bc=bc, turn_ptr=turn_ptr, turn=turn, excl_ptr=excl_ptr, excl=excl)
+        self.host = {k: np.ascontiguousarray(np.asarray(v if len(v) else [0], np.int32).reshape(-1)) for k, v in host.items()}
+        self.t = {k: torch.as_tensor(v, device=dev) for k, v in self.host.items()}
+        self.flex_ptr, self.ftor_ptr = fp, tp
+        self.n_flex, self.n_ftor = int(fp[-1]), int(tp[-1])
+        ex_len = np.diff(np.asarray(excl_ptr))
+        maxima = (self.n_flex, self.n_ftor, int(np.diff(fp).max()), int(np.diff(tp).max()), max(anchors),
+                  int(ex_len.max()) if ex_len.size else 0)
+        names = [n for n, _ in VinaFlexIn._fields_][1:9]
+        self._host_c = VinaFlexIn(None, *[self.host[n].ctypes.data for n in names], *maxima, None)
+        self.c = VinaFlexIn(C.addressof(vb.c), *[self.t[n].data_ptr() for n in names], *maxima, C.addressof(self._host_c))
+        nb = C.c_size_t(0)
+        L.check(L.load().dbfr_vina_flex_workspace_bytes(C.byref(self.c), C.byref(nb)))
+
+    def _out(self):
+        pb, dev = self.vb.pb, self.vb.pb.lig_pos.device
+        return (torch.empty_like(pb.lig_pos), torch.empty_like(pb.t["rec_pos"]), torch.empty(pb.G, 10, device=dev))
+
+    def score_at(self, q_rigid=None, q_tor=None, q_flex=None):
+        """(lig_pos [NL,3], rec_pos [NA,3], terms [G,10] (``FLEX_TERMS``), dE/dq_rigid [G,6], dE/dq_tor [NTOR], dE/dq_flex [n_ftor])
+        at the pose built from q = (q_rigid, q_tor, q_flex); None = 0."""
+        vb, pb, dev = self.vb, self.vb.pb, self.vb.pb.lig_pos.device
+        G, NT, NF = pb.G, pb.dims["NTOR"], self.n_ftor
+        pos, rec, terms = self._out()
+        grig, gtor, gflex = torch.empty(G, 6, device=dev), torch.empty(max(NT, 1), device=dev), torch.empty(max(NF, 1), device=dev)
+        f32 = lambda q, shape: None if q is None else torch.as_tensor(q, dtype=torch.float32, device=dev).reshape(shape).contiguous()
+        qr, qt, qf = f32(q_rigid, (G, 6)), f32(q_tor if NT else None, (NT,)), f32(q_flex if NF else None, (NF,))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        L.check(L.load().dbfr_vina_flex_score_at(C.byref(self.c), ptr(qr), ptr(qt), ptr(qf), pos.data_ptr(), rec.data_ptr(), terms.data_ptr(),
+                                                grig.data_ptr(), gtor.data_ptr(), gflex.data_ptr(), vb.ws.data_ptr(), vb.ws.numel(),
+                                                vb._stream()))
+        return pos, rec, terms, grig, gtor[:NT], gflex[:NF]
+
+    def minimize(self, max_iters=100, grad_tol=1e-3, margin=2.0):
+        """(lig_pos [NL,3], rec_pos [NA,3], q_flex [n_ftor], terms [G,10], iters [G]) after the BFGS refinement of every pose."""
+        vb, pb, dev = self.vb, self.vb.pb, self.vb.pb.lig_pos.device
+        pos, rec, terms = self._out()
+        qf = torch.zeros(max(self.n_ftor, 1), device=dev)
+        iters = torch.empty(pb.G, dtype=torch.int32, device=dev)
+        opts = VinaOpts(int(max_iters), float(grad_tol), float(margin))
+        L.check(L.load().dbfr_vina_flex_minimize(C.byref(self.c), C.byref(opts), pos.data_ptr(), rec.data_ptr(), qf.data_ptr(),
+                                                terms.data_ptr(), iters.data_ptr(), vb.ws.data_ptr(), vb.ws.numel(), vb._stream()))
+        return pos, rec, qf[:self.n_ftor], terms, iters
+
+
+def residue_flex_sets(aatype, mask14, topo):
+    """The one place that turns residues into flexible sets.  aatype [R] and mask14 bool [R, 14] of the pocket residues, whose
+    present atoms are the pocket atoms 0 .. M-1 of ``topo`` (a ``pocketcheck.receptor_topology``) in row-major order.  Returns
+    (atom_index int [R, 14], -1 = absent; list per row of None (not eligible) or a dict: ``atoms`` (the movable atoms: the side
+    chain beyond CB, ``atom14_to_group`` >= 4), ``tors`` (chi k = (b, c, turned): the axis is the chi's two middle atoms,
+    ``chi_atoms14[.., 1:3]``, and the atoms of group >= 4 + k turn: a positive angle increases the chi's IUPAC dihedral), ``excl``
+    (per movable atom the receptor atoms within 3 bonds: ``topo``'s lists), ``n_chi`` and ``n_anchor`` (the axis ends that are not
+    movable: CA and CB of chi1, CB of chi2)).  Eligible: at least one chi, not PRO, no atom in a closure bond (disulfide), every
+    side-chain atom of the residue type present in ``mask14``."""
+    T = _tables()
+    aa = np.asarray(aatype, np.int64)
+    m14 = np.asarray(mask14) > 0.5
+    R = aa.shape[0]
+    idx = np.full((R, 14), -1, np.int64)
+    idx[m14] = np.arange(int(m14.sum()))
+    names3 = [str(x) for x in T["restype_names3"]]
+    closed = set(np.asarray(topo["closure"], np.int64).reshape(-1).tolist())
+    rank, ep, ex = topo["pocket_rank"], topo["excl_ptr"], topo["excl"]
+    out = []
+    for r in range(R):
+        a = int(aa[r]) if 0 <= aa[r] < 20 else 20
+        group = T["atom14_to_group"][a]
+        n_chi = int((T["chi_mask"][a] > 0.5).sum())
+        atoms = [int(idx[r, s]) for s in range(14) if group[s] >= 4 and idx[r, s] >= 0]
+        complete = bool((m14[r] | (T["atom14_mask"][a] < 0.5)).all())
+        if not (n_chi > 0 and names3[a] != "PRO" and complete and atoms) or (set(idx[r][idx[r] >= 0].tolist()) & closed):
+            out.append(None)
+            continue
+        tors, anchors = [], 0
+        for k in range(n_chi):
+            b, c = (int(idx[r, s]) for s in T["chi_atoms14"][a, k, 1:3])
+            tors.append((b, c, [int(idx[r, s]) for s in range(14) if group[s] >= 4 + k and idx[r, s] >= 0]))
+            anchors += int(b not in atoms) + int(c not in atoms)
+        out.append(dict(atoms=atoms, tors=tors, excl=[ex[ep[rank[m]]:ep[rank[m] + 1]].astype(np.int64) for m in atoms],
+                        n_chi=n_chi, n_anchor=anchors))
+    return idx, out
+
+
+def flex_topology(e):
+    """What the flexible refinement needs of one ``export.ComplexOutput``, built once per complex: ``residue_flex_sets`` on
+    ``pocketcheck.entry_topology``.  A dict: ``atom_index`` int [R, 14] (pocket atom of every atom14 slot, -1 = absent),
+    ``eligible`` bool [R], per pocket residue row ``atoms`` / ``tors`` / ``excl`` (empty lists where not eligible), ``n_atoms`` /
+    ``n_slots`` (atoms + axis anchors) / ``n_chi`` int [R]; ``topo`` (the ``receptor_topology``), ``static`` and ``mask14``."""
+    from . import pocketcheck
+    topo, static, m14 = pocketcheck.entry_topology(e)
+    idx, sets = residue_flex_sets(e.aatype, m14, topo)
+    n = lambda f: np.array([f(s) if s else 0 for s in sets], np.int64)
+    return dict(atom_index=idx, eligible=np.array([s is not None for s in sets], bool),
+                atoms=[s["atoms"] if s else [] for s in sets], tors=[s["tors"] if s else [] for s in sets],
+                excl=[s["excl"] if s else [] for s in sets], n_atoms=n(lambda s: len(s["atoms"])),
+                n_slots=n(lambda s: len(s["atoms"]) + s["n_anchor"]), n_chi=n(lambda s: s["n_chi"]), topo=topo, static=static, mask14=m14)
+
+
+def select_flexible(e, lig, atom14, flex_dist=3.5, max_flex_res=12, topo=None):
+    """The flexible residues of every pose, with torch ops on the poses' device.  lig [P, N, 3] and atom14 [P, R, 14, 3] in one
+    frame; ``topo`` = ``flex_topology(e)``.  A residue is selected if it is eligible and one of its movable atoms lies within
+    ``flex_dist`` A of a ligand heavy atom (``e.heavy_mask``); the closest ``max_flex_res`` are kept (ties: the lower row), and of
+    those the farthest are dropped until the pose fits the kernel's limits (``FLEX_MAX_SLOTS`` ligand atoms + flexible atoms + axis
+    anchors, ``FLEX_MAX_VARS`` variables), per pose and with the maxima the library checks over the whole batch (the most flexible
+    atoms of any pose + the most anchors of any pose).  Returns (list per pose of int64 rows, closest first; bool [P]: trimmed)."""
+    topo = flex_topology(e) if topo is None else topo
+    lig = torch.as_tensor(lig, dtype=torch.float32)
+    dev = lig.device
+    atom14 = torch.as_tensor(atom14, dtype=torch.float32, device=dev)
+    P, N = lig.shape[0], lig.shape[1]
+    R = atom14.shape[1]
+    heavy = np.ones(N, bool) if getattr(e, "heavy_mask", None) is None else np.asarray(e.heavy_mask, bool)
+    mov = np.zeros((R, 14), bool)
+    for r in range(R):
+        for a in topo["atoms"][r]:
+            mov[r, np.flatnonzero(topo["atom_index"][r] == a)[0]] = True
+    d = torch.cdist(atom14.reshape(P, R * 14, 3), lig[:, torch.as_tensor(heavy, device=dev)]).amin(-1).reshape(P, R, 14)
+    d = torch.where(torch.as_tensor(mov, device=dev)[None], d, torch.full_like(d, float("inf"))).amin(-1)        # [P, R]
+    d = torch.where(d < flex_dist, d, torch.full_like(d, float("inf")))
+    key, order = torch.sort(d, dim=1, stable=True)                       # ties: the lower row
+    near = torch.isfinite(key)
+    keep = near & (torch.arange(R, device=dev)[None] < int(max_flex_res))
+    slots = torch.as_tensor(topo["n_slots"], device=dev)[order] * keep
+    chis = torch.as_tensor(topo["n_chi"], device=dev)[order] * keep
+    from .ligand import torsion_masks
+    n_tor = int(torsion_masks(N, np.asarray(e.ligand_edge_index, np.int64).reshape(2, -1))[0].sum())
+    fits = (N + slots.cumsum(1) <= FLEX_MAX_SLOTS) & (6 + n_tor + chis.cumsum(1) <= FLEX_MAX_VARS)
+    fits = fits.to(torch.int64).cumprod(1).bool()                        # dropping the farthest first = keeping a prefix
+    n_keep = (keep & fits).sum(1).cpu().numpy()
+    trimmed = (keep.sum(1).cpu().numpy() > n_keep)
+    order = order.cpu().numpy()
+    rows = [order[p, :n_keep[p]].astype(np.int64) for p in range(P)]
+    # the library's limit holds for the batch's maxima: N + max flexible atoms + max anchors.  While it fails, the pose holding
+    # the most slots gives up its farthest residue.
+    n_at, n_sl = np.asarray(topo["n_atoms"], np.int64), np.asarray(topo["n_slots"], np.int64)
+    while P:
+        nf = np.array([n_at[r].sum() for r in rows])
+        na = np.array([(n_sl[r] - n_at[r]).sum() for r in rows])
+        if N + nf.max() + na.max() <= FLEX_MAX_SLOTS:
+            break
+        p = int(np.argmax(nf + na))
+        rows[p] = rows[p][:-1]
+        trimmed[p] = True
+    return rows, trimmed
+
+
+def _flex_sets(topo, rows):
+    """The ``VinaFlexBatch`` sets of per-pose residue rows (each pose's residues in ascending row order)."""
+    out = []
+    for rr in rows:
+        rr = sorted(int(r) for r in rr)
+        out.append(None if not rr else dict(atoms=[a for r in rr for a in topo["atoms"][r]], tors=[t for r in rr for t in topo["tors"][r]],
+                                            excl=[x for r in rr for x in topo["excl"][r]]))
+    return out
+
+
+def refine_entry_flex(e, flex_dist=3.5, max_flex_res=12, max_iters=100, grad_tol=1e-3, lig_types=None):
+    """``refine_entry`` with the pocket side chains near the ligand flexible (``select_flexible`` per pose).  Returns a dict:
+    ``lig`` [P, N, 3] absolute, ``atom14`` [P, R, 14, 3] pocket-centred (the final frame with the flexible atoms moved, every
+    other atom bit for bit), ``terms`` [P, 10] (``FLEX_TERMS``), ``iters`` [P], ``flex_rows`` (list per pose of the flexible pocket
+    residue rows, ascending), ``q_flex`` (list per pose: the final chi changes in radians, residues in ``flex_rows`` order, chi1
+    first), ``trimmed`` bool [P]."""
+    vb, center, P, N = _entry_batch(e, lig_types)
+    topo = flex_topology(e)
+    lig0, a14 = e.ligand_traj[:, -1], e.protein_traj[:, -1]
+    rows, trimmed = select_flexible(e, lig0, a14, flex_dist, max_flex_res, topo)
+    rows = [np.sort(r) for r in rows]
+    fb = VinaFlexBatch(vb, _flex_sets(topo, rows))
+    pos, rec, qf, terms, iters = fb.minimize(max_iters=max_iters, grad_tol=grad_tol)
+    out14 = a14.to(torch.float32).clone()
+    out14[:, torch.as_tensor(topo["mask14"], device=out14.device)] = rec.reshape(P, -1, 3)
+    qf = qf.cpu()
+    return dict(lig=pos.reshape(P, N, 3) + center, atom14=out14, terms=terms, iters=iters, flex_rows=rows,
+                q_flex=[qf[int(fb.ftor_ptr[p]):int(fb.ftor_ptr[p + 1])] for p in range(P)], trimmed=trimmed)
+
+
+def refined_entry(e, lig, atom14):
+    """A copy of the entry whose trajectories hold one frame, the refined one: lig [P, N, 3] absolute and atom14 [P, R, 14, 3]
+    pocket-centred, as ``refine_entry_flex`` (or ``refine_entry``, with ``e.protein_traj[:, -1]``) returns them.  ``posecheck``,
+    ``pocketcheck``, ``interactions``, ``sasa`` and ``hetero`` then annotate the refined poses unchanged."""
+    import dataclasses
+    dev = e.ligand_traj.device
+    center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
+    lig = torch.as_tensor(lig, dtype=torch.float32, device=dev) - center
+    atom14 = torch.as_tensor(atom14, dtype=torch.float32, device=dev)
+    return dataclasses.replace(e, ligand_traj=lig[:, None].contiguous(), protein_traj=atom14[:, None].contiguous())
+
+
+def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_dist=None, max_flex_res=12, refined=None):
     """The error-correction step of the reference's predict.py (:160-170, smina per pose there) over the ``export.ComplexOutput``
     entries and the frame ``export.complex_modeling`` returned for them (rows in entry order, ``n_pose`` per entry, with a
     ``docked_lig`` column): every pose's final frame is minimised on the device (``refine_entry``), written next to its
     ``lig_final.sdf`` as ``lig_final_ec.sdf`` with a ``minimizedAffinity`` data item, and the returned copy of the frame has a
     ``smina_score`` column (the affinity of the minimised pose, kcal/mol) and ``docked_lig`` pointing at the ``_ec`` files --
-    what the reference's ``get_smina_score`` and its top-1 ``groupby`` read."""
+    what the reference's ``get_smina_score`` and its top-1 ``groupby`` read.
+
+    ``flex_dist`` (A; None = the rigid receptor above, unchanged): the side chains within it move too (``refine_entry_flex``); the
+    refined receptor is written as ``pkt_final_ec.pdb`` / ``prot_final_ec.pdb`` next to the file ``protein_pdb`` names, which then
+    points there, and the frame gains ``FLEX_COLUMNS``: ``ec_n_flex``, ``ec_flex_residues`` (``A:LEU83;...``), ``ec_sc_moved`` (the
+    largest displacement of a pocket atom, A) and ``ec_rec_energy`` (E_rec at the end - at the start, kcal/mol).
+    ``refined``: a list that receives one ``refined_entry`` per entry, for the per-pose analyses of the refined poses."""
     df = pd_df.copy()
     if "docked_lig" not in df.columns:
         raise DbfrError("error_correct needs the frame complex_modeling wrote (a docked_lig column)")
     n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
     if n_rows != len(df):
         raise DbfrError(f"{len(df)} frame rows for {n_rows} poses of the entries")
+    if flex_dist is not None:
+        if "protein_pdb" not in df.columns:
+            raise DbfrError("error_correct(flex_dist=) needs the frame's protein_pdb column")
+        import os
+        if any(os.path.basename(str(p)) not in ("prot_final.pdb", "pkt_final.pdb") for p in df["protein_pdb"]):      # before any file
+            raise DbfrError("error_correct(flex_dist=): protein_pdb must name the prot_final.pdb / pkt_final.pdb complex_modeling wrote")
     scores, paths, row = [], [], 0
+    prot_paths, extra = [], {k: [] for k in FLEX_COLUMNS}
     import os
     for e in entries:
         if e.sdf_template is None:
             raise DbfrError(f"{e.name}: error_correct writes SD files from the entry's sdf_template")
-        pos, terms, _ = refine_entry(e, max_iters=max_iters, grad_tol=grad_tol)
+        if flex_dist is None:
+            pos, terms, _ = refine_entry(e, max_iters=max_iters, grad_tol=grad_tol)
+        else:
+            from .interactions import residue_tags
+            r = refine_entry_flex(e, flex_dist=flex_dist, max_flex_res=max_flex_res, max_iters=max_iters, grad_tol=grad_tol)
+            pos, terms = r["lig"], r["terms"]
+            P = pos.shape[0]
+            center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3))
+            final = r["atom14"].cpu() + center
+            old = [str(p) for p in df["protein_pdb"].iloc[row:row + P]]
+            new = [os.path.join(os.path.dirname(p), os.path.splitext(os.path.basename(p))[0] + "_ec.pdb") for p in old]
+            for name, topo in (("prot_final.pdb", e.topology), ("pkt_final.pdb", e.topology.pocket())):
+                sel = [i for i, p in enumerate(old) if os.path.basename(p) == name]
+                if sel:
+                    topo.write_poses(final[sel], [new[i] for i in sel], rows=None if name == "pkt_final.pdb" else e.topology.pocket_rows,
+                                     threads=threads)
+            if refined is not None:
+                refined.append(refined_entry(e, pos, r["atom14"]))
+            prot_paths.extend(new)
+            tags = residue_tags(e.topology)
+            prow = np.asarray(e.topology.pocket_rows, np.int64)
+            moved = (r["atom14"] - e.protein_traj[:, -1]).norm(dim=-1).amax((1, 2)).cpu().tolist()
+            tt = terms.cpu()
+            extra["ec_n_flex"].extend(len(x) for x in r["flex_rows"])
+            extra["ec_flex_residues"].extend(";".join(tags[int(prow[k])] for k in x) for x in r["flex_rows"])
+            extra["ec_sc_moved"].extend(moved)
+            extra["ec_rec_energy"].extend((tt[:, 8] - tt[:, 9]).tolist())
         P = pos.shape[0]
         aff = terms[:, 7].cpu().tolist()
         out = [os.path.join(os.path.dirname(str(p)), "lig_final_ec.sdf") for p in df["docked_lig"].iloc[row:row + P]]
@@ -453,4 +731,8 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0):
         row += P
     df["smina_score"] = scores
     df["docked_lig"] = paths
+    if flex_dist is not None:
+        df["protein_pdb"] = prot_paths
+        for k in FLEX_COLUMNS:
+            df[k] = extra[k]
     return df

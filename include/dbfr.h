@@ -35,7 +35,7 @@ extern "C" {
                                 4: + DBFR_GEMM_REDUCE_FIRST (the new default), dbfr_profile_executed_flops; dbfr_model_set_edge_log takes the graph capacity; DBFR_GEMM_SPLIT_BF16_L1 (k_conv2s) retired; dbfr_test_conv2's message rows in that mode hold segment sums;
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
                                 6: + dbfr_profile_useful_flops, dbfr_model_set_tie_log, dbfr_test_reduce_ln2; dbfr_model_set_edge_log accepts batches with fewer graphs than its capacity; an unknown DBFR_GEMM value fails dbfr_model_create;
-                                   later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize,
+                                   later additions under the same number: dbfr_vina_in, dbfr_vina_opts, dbfr_vina_workspace_bytes, dbfr_vina_score, dbfr_vina_score_at, dbfr_vina_minimize, dbfr_vina_flex_in, dbfr_vina_flex_workspace_bytes, dbfr_vina_flex_score_at, dbfr_vina_flex_minimize,
                                    dbfr_pose_rmsd_in, dbfr_modes_opts, dbfr_pose_rmsd_matrix, dbfr_select_modes,
                                    dbfr_pose_check_in, dbfr_pose_check_opts, dbfr_pose_check_out, dbfr_pose_check,
                                    dbfr_xtc_in, dbfr_xtc_opts, dbfr_xtc_workspace_bytes, dbfr_xtc_encode, dbfr_pdb_atom_map,
@@ -506,6 +506,53 @@ int dbfr_vina_score_at(const dbfr_vina_in* in, const float* q_rigid, const float
  * after max_iters steps, or when not even a steepest-descent step lowers the objective any more.  opts NULL = defaults.     */
 int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* terms, int32_t* iters,
                        void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- The same refinement with flexible pocket side chains (docs/vina.md, "Flexible side chains"; the same kernel code in a
+ * second instantiation).  Receptor atoms of a pose are numbered pocket atoms first (0 .. na_g - 1: rec_pos under atm_ptr), then
+ * the graph's extra atoms (na_g ..).  Each graph lists some pocket atoms as flexible and an ordered list of flexible torsions:
+ * torsion k has the axis (b, c) (two pocket atoms, pivot b, direction b -> c) and turns the listed flexible atoms; torsions are
+ * applied in list order about the current axis, as the ligand's are; the ligand's rigid motion and centroid involve ligand atoms
+ * only.  objective = E_inter + E_intra + E_rec: E_inter over (ligand, receptor) pairs, fixed and flexible receptor atoms alike;
+ * E_rec = the same five weighted terms over (flexible, fixed) and (flexible, flexible) pairs except the partners on the flexible
+ * atom's exclusion list (the receptor atoms within 3 bonds).  affinity = E_inter / (1 + 0.05846 N_rot), N_rot = ligand torsions.
+ * Variables q = (translation, rotation vector, ligand torsions, flexible torsions); BFGS, line search and stop rules as above.
+ * Limits (DBFR_ERR_ARG): max_nl + max_flex + max_anchor <= 256 (an anchor = an axis end that is not flexible, one per end),
+ * 6 + max_tor + max_ftor <= 128 variables, exclusion lists of at most 32 atoms, max_na <= 8192.  A graph that exceeds the stated
+ * maxima or whose lists are inconsistent gets NaN terms and iters = -1 and is not touched.                                     */
+typedef struct {
+  const dbfr_vina_in* base;
+  const int32_t* flex_ptr;    /* [G+1] flexible atoms by graph                                                           */
+  const int32_t* flex_atom;   /* [n_flex] graph-local pocket atom index, ascending within a graph                        */
+  const int32_t* ftor_ptr;    /* [G+1] flexible torsions by graph                                                        */
+  const int32_t* ftor_bc;     /* [n_ftor, 2] axis (b, c), graph-local pocket atom indices                                */
+  const int32_t* turn_ptr;    /* [n_ftor+1] CSR over the torsions of all graphs into turn                                */
+  const int32_t* turn;        /* the atoms a torsion turns, as positions in its graph's flexible atom list               */
+  const int32_t* excl_ptr;    /* [n_flex+1] CSR over the flexible atoms of all graphs into excl                          */
+  const int32_t* excl;        /* receptor atom indices of the graph, at most 32 per list                                 */
+  int32_t        n_flex;      /* flex_ptr[G]                                                                             */
+  int32_t        n_ftor;      /* ftor_ptr[G]                                                                             */
+  int32_t        max_flex;    /* host-known maxima over the graphs: flexible atoms, flexible torsions, axis anchors,     */
+  int32_t        max_ftor;    /* exclusion list length                                                                   */
+  int32_t        max_anchor;
+  int32_t        max_excl;
+  const void*    host;        /* NULL, or a dbfr_vina_flex_in whose eight array pointers are HOST copies of the same arrays
+                                 (base is not read): every list is then validated before the launch (DBFR_ERR_ARG): CSR shapes,
+                                 per-graph counts against the maxima, indices against max_na (+ max_ext for excl)            */
+} dbfr_vina_flex_in;
+
+/* The workspace of dbfr_vina_workspace_bytes(in->base); runs every check of the flexible calls.                           */
+int dbfr_vina_flex_workspace_bytes(const dbfr_vina_flex_in* in, size_t* bytes);
+/* dbfr_vina_score_at with q_flex [n_ftor] (NULL = 0): rec_pos_out [NA,3] receives the pocket atoms (fixed atoms copied bit for
+ * bit), terms [G,10] = the eight of dbfr_vina_score (objective including E_rec), E_rec, E_rec of the first evaluation;
+ * grad_flex [n_ftor] = dE/dq_flex.  Any output may be NULL.                                                                */
+int dbfr_vina_flex_score_at(const dbfr_vina_flex_in* in, const float* q_rigid, const float* q_tor, const float* q_flex,
+                            float* lig_pos_out, float* rec_pos_out, float* terms, float* grad_rigid, float* grad_tor,
+                            float* grad_flex, void* workspace, size_t workspace_bytes, void* hip_stream);
+/* dbfr_vina_minimize over the larger q: q_flex_out [n_ftor] receives the final flexible torsion angles (radians), terms[9] the
+ * E_rec of the starting pose.  With no flexible atoms in any graph the results equal dbfr_vina_minimize's bit for bit.       */
+int dbfr_vina_flex_minimize(const dbfr_vina_flex_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* rec_pos_out,
+                            float* q_flex_out, float* terms, int32_t* iters, void* workspace, size_t workspace_bytes,
+                            void* hip_stream);
 
 /* ---- Distinct binding modes of sampled poses (csrc/modes.hip; docs/modes.md).  A batch of G groups (one group = the poses
  * of one ligand in one pocket frame), group g holding P_g poses of N_g atoms and n_perm_g automorphisms (identity included):

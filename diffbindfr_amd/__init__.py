@@ -18,5 +18,6 @@ from . import pocketcheck  # noqa: F401
 from . import sasa  # noqa: F401
 from . import apoholo  # noqa: F401
 from . import hetero  # noqa: F401
+from . import hydrogens  # noqa: F401
 
 register_into_druglib()

@@ -158,6 +158,7 @@ class ComplexOutput:
     row: Optional[dict] = None                # the pair_frame row copied onto every pose (export.py:143-148)
     heavy_mask: Optional[np.ndarray] = None
     sdf_template: Optional[object] = None     # ligand.SdfTemplate of the input SD record -> lig_final.sdf per pose
+    ligand_record: Optional[str] = None       # the input SD record with its hydrogens (hydrogens.annotate / write_hydrogens)
     hetero: Optional[object] = None           # hetero.HeteroRecord: the structure's cofactors, metal ions and waters (absolute)
 
 

@@ -231,6 +231,23 @@ class HeteroCheckOut(C.Structure):
                                           "n_coord", "passed", "event_i", "event_f", "n_event")]
 
 
+class HydrogensIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_acc", "lig_nbr", "lh_ptr", "lh_i", "lh_f",
+                                          "lrot_ptr", "lrot_i", "lrot_f", "lh_out_off", "lk_off", "pocket_ptr", "pocket_pos_off",
+                                          "pocket_pos", "pocket_meta", "static_ptr", "static_pos", "static_meta", "rh_ptr", "rh_i", "rh_f",
+                                          "rrot_ptr", "rrot_i", "rrot_f", "rh_out_off", "rk_off", "res_ptr", "res_off")] + \
+               [(n, C.c_int32) for n in ("max_lig", "max_lig_h", "max_lig_rot", "max_rec_h", "max_res", "cand_cap")] + [("host", C.c_void_p)]
+
+
+class HydrogensOpts(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("hb_dist", "hb_h_dist", "hb_dha_angle", "hb_acc_angle")] + [("max_bond", C.c_int32)]
+
+
+class HydrogensOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("lig_h", "rec_h", "lig_k", "rec_k", "counts", "n_bond", "bond_i", "bond_f", "res_bits")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -272,7 +289,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
-           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check"]
+           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check", "dbfr_hydrogens"]
 
 _lib = None
 
@@ -373,6 +390,7 @@ def load():
     lib.dbfr_holo_site.argtypes = [C.POINTER(HoloSiteIn), vp, vp]
     lib.dbfr_holo_metrics.argtypes = [C.POINTER(HoloMetricsIn), C.POINTER(HoloMetricsOpts), C.POINTER(HoloMetricsOut), vp]
     lib.dbfr_hetero_check.argtypes = [C.POINTER(HeteroCheckIn), C.POINTER(HeteroCheckOpts), C.POINTER(HeteroCheckOut), vp]
+    lib.dbfr_hydrogens.argtypes = [C.POINTER(HydrogensIn), C.POINTER(HydrogensOpts), C.POINTER(HydrogensOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

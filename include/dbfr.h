@@ -47,7 +47,7 @@ extern "C" {
                                    dbfr_pocket_check, dbfr_sasa_in, dbfr_sasa_opts, dbfr_sasa_out, dbfr_sasa, dbfr_seq_align,
                                    dbfr_holo_site_in, dbfr_holo_site, dbfr_holo_metrics_in, dbfr_holo_metrics_opts, dbfr_holo_metrics_out,
                                    dbfr_holo_metrics, dbfr_hetero_check_in, dbfr_hetero_check_opts, dbfr_hetero_check_out,
-                                   dbfr_hetero_check */
+                                   dbfr_hetero_check, dbfr_hydrogens_in, dbfr_hydrogens_opts, dbfr_hydrogens_out, dbfr_hydrogens */
 
 typedef enum {
   DBFR_OK = 0,
@@ -1103,6 +1103,100 @@ typedef struct {                 /* device arrays; any may be NULL              
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_hetero_check(const dbfr_hetero_check_in* in, const dbfr_hetero_check_opts* opts, const dbfr_hetero_check_out* out,
                       void* hip_stream);
+
+/* ---- Polar hydrogens and angle-checked hydrogen bonds of poses (csrc/hydrogens.hip; docs/hydrogens.md).  The batch layout is
+ * that of the sibling analyses: G groups, group g holding F_g frames of N_g ligand heavy atoms, M_g pocket atoms per frame and
+ * S_g static receptor atoms (receptor atom b: pocket atom b for b < M_g, static atom b - M_g otherwise) and n_res_g residue
+ * columns.  A group has NHL_g ligand hydrogens with NRL_g ligand rotors (indices: ligand atoms) and NHR_g pocket hydrogens with
+ * NRR_g pocket rotors (indices: receptor atoms; the parent is a pocket atom and the hydrogens are sorted by parent).
+ * A hydrogen is {p, q, r, kind, rotor or -1, flags (1: the parent is N, O or S), 0, 0} and four floats:
+ *   kind 0 CARRY   e1 = unit(q - p), e2 = unit((r - p) - ((r - p).e1) e1), e3 = e1 x e2, H = p + f0 e1 + f1 e2 + f2 e3
+ *   kind 1 BISECT  H = p + f0 unit(unit(p - q) + unit(p - r))
+ *   kind 2 AMIDE, kind 3 ROTOR  e1 = unit(p - q), e2 = unit((r - q) - ((r - q).e1) e1), e3 = e1 x e2,
+ *                  H = p + f0 e1 + f1 ((c f2 - s f3) e2 + (s f2 + c f3) e3): f0 = -l cos(theta), f1 = l sin(theta), (f2, f3) = the
+ *                  cosine and sine of the dihedral (r-q-p-H) at k = 0, (c, s) = those of k steps (1, 0 for AMIDE)
+ * A rotor is {first hydrogen, n_h in 1..3 (consecutive hydrogens), K in 1..12, 0} and the cosine and sine of one step; (c, s)
+ * of k steps are k complex products with the step, from (1, 0), every one rounded.  Candidates of a rotor with parent p: for
+ * a ligand rotor the receptor acceptors A with d(p, A) <= hb_dist, for a pocket rotor the ligand acceptors and the receptor
+ * acceptors of another residue column within the same distance.  k = the lowest k attaining  min_k min_j,A d(H_kj, A); 0
+ * without candidates.
+ * Acceptors: ligand atoms with lig_acc != 0, receptor atoms with bit 0 of meta[0] (meta = {acceptor + 256 column, 3 heavy
+ * neighbours as receptor atoms or -1}).  A bond (D, H, A) across the interface: d(D, A) <= hb_dist, d(H, A) <= hb_h_dist,
+ * cos(D-H..A) <= cos(hb_dha_angle), cos(y-A..H) <= cos(hb_acc_angle) for every listed neighbour y of A; one bond per (D, A),
+ * with the passing hydrogen of smallest d(H, A) (the lowest index on a tie).  Bonds are listed ligand donors first, then by D,
+ * then by A: bond_i {side (0: the ligand donates), D, H, A}, bond_f {d(D, A), d(H, A), cos(D-H..A)}; slots not used hold -1 /
+ * NaN and n_bond is the true count even above max_bond.  counts {side-0 bonds, side-1 bonds, ligand hydrogens with flag 1 that
+ * are the hydrogen of no bond}; res_bits: 1 the residue donates to the ligand, 2 it accepts from it.  Minima carry their index,
+ * sums are integer: a frame's bytes are the same alone, in any batch and for any cand_cap.  A frame with a non-finite or
+ * |x| > 1e4 coordinate gets counts and n_bond of -1 and zeros elsewhere (-1 / NaN in the bond list).  Limits (DBFR_ERR_ARG
+ * beyond them): N_g <= 256, NHL_g <= 256, NRL_g <= 64, NHR_g <= 4096, n_res_g <= 16384, max_bond in [1, 64].                */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;
+  const int32_t* frame_ptr;      /* [G+1]                                                                                   */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_acc / lig_nbr                                     */
+  const int64_t* lig_pos_off;    /* [G] frame k of g at rows lig_pos_off[g] + k N_g of lig_pos                               */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const uint8_t* lig_acc;        /* [lig_ptr[G]] 1 = acceptor                                                               */
+  const int32_t* lig_nbr;        /* [lig_ptr[G], 3] heavy neighbours, -1 padded                                             */
+  const int32_t* lh_ptr;         /* [G+1] first ligand hydrogen of every group in lh_i / lh_f                                */
+  const int32_t* lh_i;           /* [lh_ptr[G], 8]                                                                          */
+  const float*   lh_f;           /* [lh_ptr[G], 4]                                                                          */
+  const int32_t* lrot_ptr;       /* [G+1] first ligand rotor of every group in lrot_i / lrot_f                               */
+  const int32_t* lrot_i;         /* [lrot_ptr[G], 4]                                                                        */
+  const float*   lrot_f;         /* [lrot_ptr[G], 2]                                                                        */
+  const int64_t* lh_out_off;     /* [G] frame k of g at rows lh_out_off[g] + k NHL_g of out.lig_h                            */
+  const int64_t* lk_off;         /* [G] frame k of g at lk_off[g] + k NRL_g of out.lig_k                                     */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_meta                                   */
+  const int64_t* pocket_pos_off; /* [G]                                                                                     */
+  const float*   pocket_pos;     /* [rows, 3]                                                                               */
+  const int32_t* pocket_meta;    /* [pocket_ptr[G], 4]                                                                      */
+  const int32_t* static_ptr;     /* [G+1], or NULL = no static atoms                                                        */
+  const float*   static_pos;     /* [static_ptr[G], 3]                                                                      */
+  const int32_t* static_meta;    /* [static_ptr[G], 4]                                                                      */
+  const int32_t* rh_ptr;         /* [G+1] first pocket hydrogen of every group in rh_i / rh_f                                */
+  const int32_t* rh_i;           /* [rh_ptr[G], 8]                                                                          */
+  const float*   rh_f;           /* [rh_ptr[G], 4]                                                                          */
+  const int32_t* rrot_ptr;       /* [G+1]                                                                                   */
+  const int32_t* rrot_i;         /* [rrot_ptr[G], 4]                                                                        */
+  const float*   rrot_f;         /* [rrot_ptr[G], 2]                                                                        */
+  const int64_t* rh_out_off;     /* [G] frame k of g at rows rh_out_off[g] + k NHR_g of out.rec_h                            */
+  const int64_t* rk_off;         /* [G] frame k of g at rk_off[g] + k NRR_g of out.rec_k                                     */
+  const int32_t* res_ptr;        /* [G+1]: n_res_g = res_ptr[g+1] - res_ptr[g]                                               */
+  const int64_t* res_off;        /* [G] frame k of g at res_off[g] + k n_res_g of out.res_bits                               */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 256, 64, 4096, 16384)                        */
+  int32_t        max_lig_h;
+  int32_t        max_lig_rot;
+  int32_t        max_rec_h;
+  int32_t        max_res;
+  int32_t        cand_cap;       /* receptor acceptors kept in LDS, 0 = 2048 (same bytes whatever the value; tests; 1 .. 2048);
+                                    with more the kernel reads the receptor atoms from memory                               */
+  const void*    host;           /* NULL, or a dbfr_hydrogens_in of HOST copies of the index arrays (the position arrays are not
+                                    read): every count, index, kind and rotor is then validated before the launch           */
+} dbfr_hydrogens_in;
+
+typedef struct {
+  float   hb_dist;               /* A, 3.5, in (0, 8]                                                                       */
+  float   hb_h_dist;             /* A, 2.5                                                                                  */
+  float   hb_dha_angle;          /* degrees, 120, in [0, 180]                                                               */
+  float   hb_acc_angle;          /* degrees, 90, in [0, 180]                                                                */
+  int32_t max_bond;              /* 64, in [1, 64]                                                                          */
+} dbfr_hydrogens_opts;
+
+typedef struct {                 /* device arrays, all required                                                             */
+  float*   lig_h;                /* [rows, 3] ligand hydrogen positions                                                     */
+  float*   rec_h;                /* [rows, 3] pocket hydrogen positions                                                     */
+  int32_t* lig_k;                /* [rows] the chosen k of every ligand rotor                                               */
+  int32_t* rec_k;                /* [rows] the chosen k of every pocket rotor                                               */
+  int32_t* counts;               /* [n_frame, 3]                                                                            */
+  int32_t* n_bond;               /* [n_frame]                                                                               */
+  int32_t* bond_i;               /* [n_frame, max_bond, 4]                                                                  */
+  float*   bond_f;               /* [n_frame, max_bond, 3]                                                                  */
+  uint8_t* res_bits;             /* [rows] one word per (frame, residue column)                                             */
+} dbfr_hydrogens_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_hydrogens(const dbfr_hydrogens_in* in, const dbfr_hydrogens_opts* opts, const dbfr_hydrogens_out* out, void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file
  * files; a file is the frames listed for it, in frame order, with one atom map.  Atom k of a frame is atom_map[map_ptr[m] + k]

@@ -157,6 +157,10 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
     const ConvZDesc& d = a.c[c];
     const ConvZ& W = d.w;
     const int E = min(*d.n_edges, d.max_edges);
+    // (the conv's c-tile descriptors set out WITH the chunk table and are put into b_cdesc behind the slot set-up, where the loads of the next hop
+    // have landed anyway: a load and a wait of their own behind the barrier before)
+    unsigned cd_t = 0u;
+    if (tid < (W.ct0[W.n_io - 1] + W.nct[W.n_io - 1]) * 16) cd_t = W.cdesc[tid];
     // ---- my chunk: edges [es, es + len)
     const int ch = ul * NW + wave;
     int es = 0, len = 0, gidx = 0;
@@ -167,15 +171,38 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       len = min(min(gl & 63, 32), max(E - es, 0));
     }
     __syncthreads();   // nothing of the last unit still reads the block-level arrays
-    if (tid < CZ_MAXCT * 16) b_cdesc[tid] = tid < (W.ct0[W.n_io - 1] + W.nct[W.n_io - 1]) * 16 ? W.cdesc[tid] : 0u;
     if (unit != (int)blockIdx.x) tr_n = 1000;                // (the first unit only)
     stamp(1);
-    // ---- slots: lanes 0..31 own slot L (clamped to the chunk's last edge beyond its length; a chunk without edges reads edge 0 of a non-empty conv or nothing)
+    // ---- slots: lanes 0..31 own slot L (clamped to the chunk's last edge beyond its length; a wave without edges reads edge 0 of its conv)
     const int sl = lane & 31;
     const bool have = len > 0;
     const int e_sl = have ? es + min(sl, len - 1) : 0;
-    int tgt_l = 0, gth_l = 0;
-    if (have) { tgt_l = d.tgt[e_sl]; gth_l = d.gth[e_sl]; }
+    // ---- first hop behind the chunk table: EVERYTHING the edge number addresses sets out here as one group -- target, gather row, the nine harmonics
+    // (read once, for w_sh and for the y bound), the graph's |x| bound, and per edge tile the two table indices and the embedding row.  No load hides
+    // behind `have`: a branch round a load is a wait of its own (fourteen serial round trips per unit before, all eight waves in them together), so a
+    // wave without edges loads too and a select drops the value.  What it reads is edge 0 of its conv, the table rows idx1[0] / idx2[0] and xmax[0]:
+    // a unit exists only where the conv has a chunk, a chunk holds at least one edge below E (k_chunk_fill walks [lo, hi) of a graph, hi <= E), so
+    // edge 0 is an edge of the conv with valid indices, and graph 0 exists with it.
+    const int tgt_ld = d.tgt[e_sl], gth_ld = d.gth[e_sl];
+    float s_l[9];
+    {
+      const float* sp = d.sh + (size_t)e_sl * SH_LD;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s_l[k] = sp[k];
+    }
+    const float xmax_g = d.xmax ? d.xmax[gidx] : 0.f;        // per graph, computed once per layer (k_row_absmax)
+    int i1_t[2], i2_t[2];
+    f32x4 Ba_t[2][9];                                        // radial-MLP inputs [edge tile][16 inputs of 144]: embedding row | tab1 row | tab2 row
+#pragma unroll
+    for (int et = 0; et < 2; ++et) {
+      const int e = have ? es + min(16 * et + n, len - 1) : 0;
+      i1_t[et] = d.idx1[e];
+      i2_t[et] = d.idx2[e];
+      const float* r0 = d.emb + (size_t)e * NS;
+#pragma unroll
+      for (int s4 = 0; s4 < 3; ++s4) Ba_t[et][s4] = *reinterpret_cast<const f32x4*>(r0 + 16 * s4 + 4 * g);
+    }
+    const int tgt_l = have ? tgt_ld : 0, gth_l = have ? gth_ld : 0;
     const int tgt_prev = __shfl_up(tgt_l, 1);
     const bool is_first = lane < 32 && sl < len && (sl == 0 || tgt_l != tgt_prev);
     const unsigned long long bal = __ballot(is_first);
@@ -186,18 +213,18 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       w_row[sl] = gth_l * d.ldx;
       w_seg[sl] = seg_l;
       if (is_first) w_first[seg_l] = sl;
-      const float* sp = d.sh + (size_t)e_sl * SH_LD;
 #pragma unroll
-      for (int k = 0; k < 9; ++k) w_sh[sl * 12 + k] = have ? sp[k] : 0.f;
+      for (int k = 0; k < 9; ++k) w_sh[sl * 12 + k] = have ? s_l[k] : 0.f;
       w_sh[sl * 12 + 9] = w_sh[sl * 12 + 10] = w_sh[sl * 12 + 11] = 0.f;
     }
     if (lane == 0) b_nseg[wave] = nseg;
+    if (tid < CZ_MAXCT * 16) b_cdesc[tid] = cd_t;            // (read behind the next barrier)
     // (the scalar columns of the message rows that are not the first of their segment are NOT written: the reductions read those columns of flagged rows
     // only -- EdgeSet::seg_first, conv.hip row_sum; round 5's first kernel zeroed them, 1.5 GB of stores per layer launch, and the reduction read them back)
     // ---- bounds for the y scale: largest |x| over the gathered rows, largest |harmonic|
     float xmx = 0.f, smx = 0.f;
     if (have) {
-      if (d.xmax) xmx = d.xmax[gidx];                       // per graph, computed once per layer (k_row_absmax): no pass over the gathered rows here
+      if (d.xmax) xmx = xmax_g;                             // no pass over the gathered rows here
       else {
         const float* xr = d.x + (size_t)gth_l * d.ldx;
         const int d4 = d.ldx >> 2;
@@ -207,9 +234,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
         }
       }
       if (lane < 32) {
-        const float* sp = d.sh + (size_t)e_sl * SH_LD;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) smx = fmaxf(smx, fabsf(sp[k]));
+        for (int k = 0; k < 9; ++k) smx = fmaxf(smx, fabsf(s_l[k]));
       }
     }
     xmx = cz_wave_max(xmx); smx = cz_wave_max(smx);
@@ -226,19 +252,40 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       const __amdgpu_buffer_rsrc_t rW1 = __builtin_amdgcn_make_buffer_rsrc((void*)W.W1h, 0, KT * CH_TILE_BYTES, 0x00020000);
       u32x4 Ah[2][2][4];                                     // input pieces [edge tile][hi, lo][k-step of 32]
       u32x4 Atc[2];                                          // last 16 k: [lo | hi]
+      const int vW = lane * 16;
+      // W1 fragments: step i = 5 m + s (s < 4: the k-step of 32 of tile m, hi and lo piece; s = 4: the tile's last 16 k [hi | lo] and, in the second
+      // register, my unit's bias) through a ring of three register pairs, requested TWO steps ahead of their MFMAs (a load next to its use waits
+      // out the L1 / L2 latency 45 times per chunk: 59 k of the unit's 270 k cycles in the timeline of round 5)
+      u32x4 F[3][2];
+      auto ldF = [&](auto ic) {
+        constexpr int i = decltype(ic)::value, m = i / 5, sx = i % 5;
+        if constexpr (sx < 4) {
+          F[i % 3][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rW1, vW, m * CH_TILE_BYTES + sx * 1024, 0));
+          F[i % 3][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rW1, vW, m * CH_TILE_BYTES + (4 + sx) * 1024, 0));
+        } else {
+          F[i % 3][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rW1, vW, m * CH_TILE_BYTES + CH_TAIL_OFF, 0));
+          F[i % 3][1][0] = __builtin_amdgcn_raw_buffer_load_b32(rW1, n * 4, m * CH_TILE_BYTES + CH_BIAS_OFF, 0);
+        }
+      };
+      // second hop: the gathered node rows of BOTH edge tiles, all twelve loads out before the first is used (tile 1's used to set out behind tile 0's cutting)
+#pragma unroll
+      for (int et = 0; et < 2; ++et) {
+        const float* r1 = d.tab1 + (size_t)i1_t[et] * d.ld1;
+        const float* r2 = d.tab2 + (size_t)i2_t[et] * d.ld2;
+#pragma unroll
+        for (int s4 = 3; s4 < KT; ++s4) Ba_t[et][s4] = *reinterpret_cast<const f32x4*>((s4 < 6 ? r1 : r2) + 16 * (s4 % 3) + 4 * g);
+      }
+      // (the first two steps of the W1 ring ride on the same hop: they depend on nothing, and behind the cutting they were a round trip in the open)
+      ldF(std::integral_constant<int, 0>{});
+      ldF(std::integral_constant<int, 1>{});
 #pragma unroll
       for (int et = 0; et < 2; ++et) {
         const int slot = 16 * et + n;
-        const int e = have ? es + min(slot, len - 1) : 0;
-        const float* r0 = d.emb + (size_t)e * NS;
-        const float* r1 = d.tab1 + (size_t)(have ? d.idx1[e] : 0) * d.ld1;
-        const float* r2 = d.tab2 + (size_t)(have ? d.idx2[e] : 0) * d.ld2;
         f32x4 Ba[KT];
         float amx = 0.f;
 #pragma unroll
         for (int s4 = 0; s4 < KT; ++s4) {
-          const float* src = s4 < 3 ? r0 : s4 < 6 ? r1 : r2;
-          Ba[s4] = have ? *reinterpret_cast<const f32x4*>(src + 16 * (s4 % 3) + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
+          Ba[s4] = have ? Ba_t[et][s4] : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int q = 0; q < 4; ++q) amx = fmaxf(amx, fabsf(Ba[s4][q]));
         }
@@ -270,23 +317,6 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
       }
       float Hf[KT][2][4];
       float hmx = 0.f;
-      const int vW = lane * 16;
-      // W1 fragments: step i = 5 m + s (s < 4: the k-step of 32 of tile m, hi and lo piece; s = 4: the tile's last 16 k [hi | lo] and, in the second
-      // register, my unit's bias) through a ring of three register pairs, requested TWO steps ahead of their MFMAs (a load next to its use waits
-      // out the L1 / L2 latency 45 times per chunk: 59 k of the unit's 270 k cycles in the timeline of round 5)
-      u32x4 F[3][2];
-      auto ldF = [&](auto ic) {
-        constexpr int i = decltype(ic)::value, m = i / 5, sx = i % 5;
-        if constexpr (sx < 4) {
-          F[i % 3][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rW1, vW, m * CH_TILE_BYTES + sx * 1024, 0));
-          F[i % 3][1] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rW1, vW, m * CH_TILE_BYTES + (4 + sx) * 1024, 0));
-        } else {
-          F[i % 3][0] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rW1, vW, m * CH_TILE_BYTES + CH_TAIL_OFF, 0));
-          F[i % 3][1][0] = __builtin_amdgcn_raw_buffer_load_b32(rW1, n * 4, m * CH_TILE_BYTES + CH_BIAS_OFF, 0);
-        }
-      };
-      ldF(std::integral_constant<int, 0>{});
-      ldF(std::integral_constant<int, 1>{});
       // (tile m's bias arrives with its LAST step; the accumulators start from zero and the bias x the edge's factor is added behind the tile)
       f32x4 acc[2];
       cz_static_for<0, 5 * KT>([&](auto ic) {

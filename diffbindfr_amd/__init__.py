@@ -19,5 +19,6 @@ from . import sasa  # noqa: F401
 from . import apoholo  # noqa: F401
 from . import hetero  # noqa: F401
 from . import hydrogens  # noqa: F401
+from . import decompose  # noqa: F401
 
 register_into_druglib()

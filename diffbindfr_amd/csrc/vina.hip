@@ -37,12 +37,14 @@
 #define V_WAVES (V_THREADS / 64)
 #define V_CUTOFF 8.0f
 #define V_MAX_STEP 0.3f              // largest first-trial change of one variable (A or rad): keeps the minimisation in its basin
-#define V_NTYPES 16                   // XS types 0..15; anything else is DUMMY
+#define V_NTYPES 18                   // XS types 0..15 and Met_D (17); 16 and anything outside 0..17 is DUMMY
 
-// XS type table: radius, hydrophobic, donor, acceptor
-//                       C_H  C_P  N_P  N_D  N_A  N_DA O_P  O_D  O_A  O_DA S_P  P_P  F_H  Cl_H Br_H I_H
-__constant__ float c_rad[V_NTYPES] = {1.9f, 1.9f, 1.8f, 1.8f, 1.8f, 1.8f, 1.7f, 1.7f, 1.7f, 1.7f, 2.0f, 2.1f, 1.5f, 1.8f, 2.0f, 2.2f};
-__constant__ int c_flags[V_NTYPES] = {1, 0, 0, 2, 4, 6, 0, 2, 4, 6, 0, 0, 1, 1, 1, 1};   // 1 hydrophobic, 2 donor, 4 acceptor
+// XS type table: radius, hydrophobic, donor, acceptor (row 16, DUMMY, is never read: v_typed)
+//                       C_H  C_P  N_P  N_D  N_A  N_DA O_P  O_D  O_A  O_DA S_P  P_P  F_H  Cl_H Br_H I_H  DUMMY Met_D
+__constant__ float c_rad[V_NTYPES] = {1.9f, 1.9f, 1.8f, 1.8f, 1.8f, 1.8f, 1.7f, 1.7f, 1.7f, 1.7f, 2.0f, 2.1f, 1.5f, 1.8f, 2.0f, 2.2f, 0.f, 1.2f};
+__constant__ int c_flags[V_NTYPES] = {1, 0, 0, 2, 4, 6, 0, 2, 4, 6, 0, 0, 1, 1, 1, 1, 0, 2};   // 1 hydrophobic, 2 donor, 4 acceptor
+
+__device__ __forceinline__ bool v_typed(int t) { return t >= 0 && t < V_NTYPES && t != V_DUMMY; }
 
 #define W_GAUSS1 (-0.035579f)
 #define W_GAUSS2 (-0.005156f)
@@ -191,7 +193,7 @@ template <class SH> __device__ void collect(const VinaArgs& A, SH& S, int g, int
       const float* pp; int t;
       if (c < na) { pp = A.b.rec_pos + 3 * (size_t)(a0 + c); t = A.in.rec_type[a0 + c]; }
       else { pp = A.in.ext_pos + 3 * (size_t)(e0 + c - na); t = A.in.ext_type[e0 + c - na]; }
-      const bool typed = t >= 0 && t < V_NTYPES;
+      const bool typed = v_typed(t);
       bool fixed = true;
       if constexpr (SH::kFlex) {   // flexible atoms are slots, not candidates; a candidate carries its receptor index above its type
         fixed = c >= na || !((S.fm[c >> 5] >> (c & 31)) & 1u);
@@ -244,7 +246,7 @@ template <class SH> __device__ void evaluate(const VinaArgs& A, SH& S, int g, in
   for (int i = w; i < ns; i += V_WAVES) {
     const int ti = S.lt[i];
     float gx = 0.f, gy = 0.f, gz = 0.f;
-    if (ti >= 0 && ti < V_NTYPES) {
+    if (v_typed(ti)) {
       const float xi = S.x[0][i], yi = S.x[1][i], zi = S.x[2][i];
       int ex0 = 0, ex1 = 0;        // a flexible atom's exclusion list (wave-uniform)
       if constexpr (SH::kFlex)
@@ -273,7 +275,7 @@ template <class SH> __device__ void evaluate(const VinaArgs& A, SH& S, int g, in
       for (int j = lane; j < ns; j += 64) {
         if (!((S.pm[i][j >> 5] >> (j & 31)) & 1u)) continue;
         const int tj = S.lt[j];
-        if (tj < 0 || tj >= V_NTYPES) continue;
+        if (!v_typed(tj)) continue;
         const float dx = xi - S.x[0][j], dy = yi - S.x[1][j], dz = zi - S.x[2][j];
         const float r2 = dx * dx + dy * dy + dz * dz;
         if (r2 >= V_CUTOFF * V_CUTOFF) continue;

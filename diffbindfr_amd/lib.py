@@ -248,6 +248,22 @@ class HydrogensOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("lig_h", "rec_h", "lig_k", "rec_k", "counts", "n_bond", "bond_i", "bond_f", "res_bits")]
 
 
+class VinaDecomposeIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_type", "pocket_ptr", "pocket_pos_off",
+                                          "pocket_pos", "pocket_type", "pocket_col", "static_ptr", "static_pos", "static_type",
+                                          "static_col", "col_ptr", "col_off")] + \
+               [(n, C.c_int32) for n in ("max_lig", "max_col")] + [("host", C.c_void_p)]
+
+
+class VinaDecomposeOpts(C.Structure):
+    _fields_ = [("cutoff", C.c_float)]
+
+
+class VinaDecomposeOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("col_terms", "atom_terms", "totals", "col_fixed", "atom_fixed", "totals_fixed")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -289,7 +305,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
-           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check", "dbfr_hydrogens"]
+           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check", "dbfr_hydrogens", "dbfr_vina_decompose"]
 
 _lib = None
 
@@ -391,6 +407,7 @@ def load():
     lib.dbfr_holo_metrics.argtypes = [C.POINTER(HoloMetricsIn), C.POINTER(HoloMetricsOpts), C.POINTER(HoloMetricsOut), vp]
     lib.dbfr_hetero_check.argtypes = [C.POINTER(HeteroCheckIn), C.POINTER(HeteroCheckOpts), C.POINTER(HeteroCheckOut), vp]
     lib.dbfr_hydrogens.argtypes = [C.POINTER(HydrogensIn), C.POINTER(HydrogensOpts), C.POINTER(HydrogensOut), vp]
+    lib.dbfr_vina_decompose.argtypes = [C.POINTER(VinaDecomposeIn), C.POINTER(VinaDecomposeOpts), C.POINTER(VinaDecomposeOut), vp]
     if lib.dbfr_abi_version() != 7:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

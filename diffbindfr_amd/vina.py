@@ -37,6 +37,16 @@ Minimisation: BFGS over 6 + n_tor variables per pose with a backtracking line se
 starting conformation for every trial (torsions in tor_bond order, then the rotation about the centroid, then the
 translation: the order of the sampler's pose initialisation).  There is no CPU path: CPU tensors raise DbfrError.
 
+Hetero atoms (``hetero_types``; ``hetero=`` of ``refine_entry``, ``refine_entry_flex``, ``error_correct``): the cofactors, ions and
+waters of a ``hetero.HeteroRecord`` are typed and scored as fixed receptor atoms behind the protein's.  The record holds heavy
+atoms only and no bonds, so the bonds are perceived: two atoms of one residue (chain, number, name) are bonded if r <= cov_i +
+cov_j + 0.45 A (``hetero.COVALENT``); a metal (``hetero.is_metal``) bonds to nothing.  Types: a water's atoms are O_DA (DUMMY
+with ``waters=False``: displaceable waters switched off); a metal is ``Met_D`` (code 17: radius 1.2 A, donor, neither hydrophobic
+nor acceptor -- AutoDock Vina's values); C is C_P if bonded to a heavy atom other than carbon, else C_H; O is O_A with two or
+more heavy neighbours or with one that is P or S, otherwise O_DA (a hydroxyl and a carbonyl cannot be told apart without
+hydrogens: the stance ``receptor_type_table`` takes for HIS); N is N_P with three or more heavy neighbours, else N_DA; S, P and
+halogens as in ``ligand_types``; any other element is DUMMY.  Parity with smina's or Vina's typing of cofactors is not claimed.
+
 Flexible side chains (``flex_topology``, ``select_flexible``, ``VinaFlexBatch``, ``refine_entry_flex``, ``error_correct(flex_dist=)``):
 the pocket side chains near the ligand turn about their chi axes in the same minimisation; docs/vina.md states the model.
 """
@@ -51,9 +61,11 @@ from . import lib as L
 from .lib import DbfrError, VinaFlexIn, VinaIn, VinaOpts
 
 XS_NAMES = ["C_H", "C_P", "N_P", "N_D", "N_A", "N_DA", "O_P", "O_D", "O_A", "O_DA", "S_P", "P_P", "F_H", "Cl_H", "Br_H",
-            "I_H", "DUMMY"]
+            "I_H", "DUMMY", "Met_D"]
 XS = {n: i for i, n in enumerate(XS_NAMES)}
 DUMMY = XS["DUMMY"]
+MET_D = XS["Met_D"]
+BOND_TOLERANCE = 0.45                        # A: hetero atoms of one residue are bonded up to cov_i + cov_j + this
 TERMS = ["gauss1", "gauss2", "repulsion", "hydrophobic", "hbond", "intra", "objective", "affinity"]
 MAX_TORSIONS = 58
 FLEX_TERMS = TERMS + ["rec", "rec_start"]
@@ -132,6 +144,59 @@ def ligand_types(molblock):
             t = "DUMMY"
         out.append(XS[t])
     return np.asarray(out, np.int8)
+
+
+def hetero_bonds(record):
+    """The perceived bonds of a ``hetero.HeteroRecord``: a list per atom of its bonded atoms (ascending).  Two atoms of the same
+    residue (chain, resnum, resname) are bonded if r <= cov_i + cov_j + ``BOND_TOLERANCE``; metals bond to nothing."""
+    from .hetero import covalent_radius, is_metal
+    n = len(record)
+    pos = np.asarray(record.pos, np.float64).reshape(-1, 3)
+    cov = np.array([covalent_radius(s) for s in record.element], np.float64)
+    metal = np.array([is_metal(s) for s in record.element], bool)
+    by_res = {}
+    for a in range(n):
+        by_res.setdefault((record.chain[a], int(record.resnum[a]), record.resname[a]), []).append(a)
+    nbr = [[] for _ in range(n)]
+    for atoms in by_res.values():
+        idx = np.asarray(atoms, np.int64)
+        d = np.linalg.norm(pos[idx][:, None] - pos[idx][None], axis=-1)
+        ok = (d <= cov[idx][:, None] + cov[idx][None] + BOND_TOLERANCE) & ~metal[idx][:, None] & ~metal[idx][None]
+        np.fill_diagonal(ok, False)
+        for i, a in enumerate(atoms):
+            nbr[a] = [atoms[j] for j in np.flatnonzero(ok[i])]
+    return nbr
+
+
+def hetero_types(record, waters=True):
+    """XS type codes (int8 [H], file order) of a ``hetero.HeteroRecord`` by the rules of the module docstring.  ``waters=False``
+    types the water atoms DUMMY."""
+    from .hetero import WATER, is_metal
+    nbr = hetero_bonds(record)
+    el = list(record.element)
+    out = np.full(len(record), DUMMY, np.int8)
+    for a, s in enumerate(el):
+        heavy = nbr[a]
+        if int(record.klass[a]) == WATER:
+            t = "O_DA" if waters and s == "O" else "DUMMY"
+        elif is_metal(s):
+            t = "Met_D"
+        elif s == "C":
+            t = "C_P" if any(el[b] != "C" for b in heavy) else "C_H"
+        elif s == "O":
+            t = "O_A" if len(heavy) >= 2 or (len(heavy) == 1 and el[heavy[0]] in ("P", "S")) else "O_DA"
+        elif s == "N":
+            t = "N_P" if len(heavy) >= 3 else "N_DA"
+        elif s == "S":
+            t = "S_P"
+        elif s == "P":
+            t = "P_P"
+        elif s in _HALOGEN:
+            t = _HALOGEN[s]
+        else:
+            t = "DUMMY"
+        out[a] = XS[t]
+    return out
 
 
 _REC_HETERO_C = {   # carbons bonded to N, O or S beyond CA and C (every residue)
@@ -408,8 +473,22 @@ def _entry_receptor(e, rec_table):
     return rec, rec_type, ext_pos, ext_type
 
 
-def _entry_batch(e, lig_types):
-    """(VinaBatch of the final frames of one entry, pocket centre on the device, P, N): the receptor of ``_entry_receptor``."""
+def _entry_arrays(e, rec_table, hetero=None, waters=True):
+    """``_entry_receptor`` with the typed atoms of the ``hetero.HeteroRecord`` (absolute coordinates; every atom of the record, in
+    file order, DUMMY ones included) moved into the pocket-centred frame and appended after the protein's extra atoms.  Returns
+    (rec, rec_type, ext_pos, ext_type, first extra atom of the record).  ``hetero=None``: the arrays of ``_entry_receptor``, untouched."""
+    rec, rec_type, ext_pos, ext_type = _entry_receptor(e, rec_table)
+    n_prot = int(ext_pos.shape[0])
+    if hetero is not None:
+        from .hetero import record_arrays
+        center = np.asarray(e.pocket_center_pos, np.float32).reshape(3)
+        ext_pos = np.concatenate([ext_pos, record_arrays(hetero, center)["het"]]).astype(np.float32)
+        ext_type = np.concatenate([ext_type, hetero_types(hetero, waters).astype(ext_type.dtype)])
+    return rec, rec_type, ext_pos, ext_type, n_prot
+
+
+def _entry_batch(e, lig_types, hetero=None, waters=True):
+    """(VinaBatch of the final frames of one entry, pocket centre on the device, P, N): the receptor of ``_entry_arrays``."""
     dev = e.ligand_traj.device
     if dev.type != "cuda":
         raise DbfrError("the Vina refinement runs on the GPU only: the trajectories are on " + str(dev))
@@ -421,17 +500,19 @@ def _entry_batch(e, lig_types):
     lig = e.ligand_traj[:, -1].contiguous()
     P, N = lig.shape[0], lig.shape[1]
     rec_table = receptor_type_table()
-    rec, rec_type, ext_pos, ext_type = _entry_receptor(e, rec_table)
+    rec, rec_type, ext_pos, ext_type, _ = _entry_arrays(e, rec_table, hetero, waters)
     pb = PoseBatch(lig, e.ligand_edge_index, rec)
     pairs = intra_pairs(N, e.ligand_edge_index, pb.tor_edge_mask)
     vb = VinaBatch(pb, [lig_types] * P, [pairs] * P, ext=([ext_pos] * P, [ext_type] * P), rec_types=np.tile(rec_type, P))
     return vb, center, P, N
 
 
-def refine_entry(e, lig_types=None, max_iters=100, grad_tol=1e-3):
+def refine_entry(e, lig_types=None, max_iters=100, grad_tol=1e-3, hetero=None, waters=True):
     """Minimise the final frame of every pose of one ``export.ComplexOutput`` against its pocket (the pose's side chains) and
-    the rest of the protein (static extra atoms).  Returns (minimised lig_pos [P, N, 3] absolute, terms [P, 8], iters [P])."""
-    vb, center, P, N = _entry_batch(e, lig_types)
+    the rest of the protein (static extra atoms).  ``hetero``: a ``hetero.HeteroRecord`` whose atoms (``hetero_types``; waters
+    only with ``waters``) are scored as further static atoms; None = protein atoms only, as before.  Returns (minimised lig_pos
+    [P, N, 3] absolute, terms [P, 8], iters [P])."""
+    vb, center, P, N = _entry_batch(e, lig_types, hetero, waters)
     pos, terms, iters = vb.minimize(max_iters=max_iters, grad_tol=grad_tol)
     return (pos.reshape(P, N, 3) + center), terms, iters
 
@@ -631,13 +712,14 @@ def _flex_sets(topo, rows):
     return out
 
 
-def refine_entry_flex(e, flex_dist=3.5, max_flex_res=12, max_iters=100, grad_tol=1e-3, lig_types=None):
+def refine_entry_flex(e, flex_dist=3.5, max_flex_res=12, max_iters=100, grad_tol=1e-3, lig_types=None, hetero=None, waters=True):
     """``refine_entry`` with the pocket side chains near the ligand flexible (``select_flexible`` per pose).  Returns a dict:
     ``lig`` [P, N, 3] absolute, ``atom14`` [P, R, 14, 3] pocket-centred (the final frame with the flexible atoms moved, every
     other atom bit for bit), ``terms`` [P, 10] (``FLEX_TERMS``), ``iters`` [P], ``flex_rows`` (list per pose of the flexible pocket
     residue rows, ascending), ``q_flex`` (list per pose: the final chi changes in radians, residues in ``flex_rows`` order, chi1
-    first), ``trimmed`` bool [P]."""
-    vb, center, P, N = _entry_batch(e, lig_types)
+    first), ``trimmed`` bool [P].  ``hetero`` / ``waters``: as in ``refine_entry``; the record's atoms are fixed atoms behind the
+    protein's extra atoms and appear in no exclusion list."""
+    vb, center, P, N = _entry_batch(e, lig_types, hetero, waters)
     topo = flex_topology(e)
     lig0, a14 = e.ligand_traj[:, -1], e.protein_traj[:, -1]
     rows, trimmed = select_flexible(e, lig0, a14, flex_dist, max_flex_res, topo)
@@ -663,7 +745,8 @@ def refined_entry(e, lig, atom14):
     return dataclasses.replace(e, ligand_traj=lig[:, None].contiguous(), protein_traj=atom14[:, None].contiguous())
 
 
-def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_dist=None, max_flex_res=12, refined=None):
+def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_dist=None, max_flex_res=12, refined=None, hetero=None,
+                  waters=True):
     """The error-correction step of the reference's predict.py (:160-170, smina per pose there) over the ``export.ComplexOutput``
     entries and the frame ``export.complex_modeling`` returned for them (rows in entry order, ``n_pose`` per entry, with a
     ``docked_lig`` column): every pose's final frame is minimised on the device (``refine_entry``), written next to its
@@ -675,8 +758,14 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
     refined receptor is written as ``pkt_final_ec.pdb`` / ``prot_final_ec.pdb`` next to the file ``protein_pdb`` names, which then
     points there, and the frame gains ``FLEX_COLUMNS``: ``ec_n_flex``, ``ec_flex_residues`` (``A:LEU83;...``), ``ec_sc_moved`` (the
     largest displacement of a pocket atom, A) and ``ec_rec_energy`` (E_rec at the end - at the start, kcal/mol).
-    ``refined``: a list that receives one ``refined_entry`` per entry, for the per-pose analyses of the refined poses."""
+    ``refined``: a list that receives one ``refined_entry`` per entry, for the per-pose analyses of the refined poses.
+
+    ``hetero`` (None = protein atoms only, unchanged): one ``hetero.HeteroRecord`` or None per entry, in the form ``hetero.annotate``
+    takes; its atoms are scored (``hetero_types``; waters only with ``waters``) and the frame gains ``ec_het_atoms``, the number of
+    scored hetero atoms of the pose's entry."""
     df = pd_df.copy()
+    if hetero is not None and len(hetero) != len(entries):
+        raise DbfrError(f"{len(hetero)} hetero records for {len(entries)} entries")
     if "docked_lig" not in df.columns:
         raise DbfrError("error_correct needs the frame complex_modeling wrote (a docked_lig column)")
     n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
@@ -691,14 +780,16 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
     scores, paths, row = [], [], 0
     prot_paths, extra = [], {k: [] for k in FLEX_COLUMNS}
     import os
-    for e in entries:
+    het_atoms = []
+    for k, e in enumerate(entries):
         if e.sdf_template is None:
             raise DbfrError(f"{e.name}: error_correct writes SD files from the entry's sdf_template")
+        het = {} if hetero is None else dict(hetero=hetero[k], waters=waters)
         if flex_dist is None:
-            pos, terms, _ = refine_entry(e, max_iters=max_iters, grad_tol=grad_tol)
+            pos, terms, _ = refine_entry(e, max_iters=max_iters, grad_tol=grad_tol, **het)
         else:
             from .interactions import residue_tags
-            r = refine_entry_flex(e, flex_dist=flex_dist, max_flex_res=max_flex_res, max_iters=max_iters, grad_tol=grad_tol)
+            r = refine_entry_flex(e, flex_dist=flex_dist, max_flex_res=max_flex_res, max_iters=max_iters, grad_tol=grad_tol, **het)
             pos, terms = r["lig"], r["terms"]
             P = pos.shape[0]
             center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3))
@@ -728,9 +819,13 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
                                    data={"minimizedAffinity": [f"{a:.5f}" for a in aff]})
         scores.extend(aff)
         paths.extend(out)
+        if hetero is not None:
+            het_atoms.extend([0 if hetero[k] is None else int((hetero_types(hetero[k], waters) != DUMMY).sum())] * P)
         row += P
     df["smina_score"] = scores
     df["docked_lig"] = paths
+    if hetero is not None:
+        df["ec_het_atoms"] = het_atoms
     if flex_dist is not None:
         df["protein_pdb"] = prot_paths
         for k in FLEX_COLUMNS:

@@ -47,7 +47,8 @@ extern "C" {
                                    dbfr_pocket_check, dbfr_sasa_in, dbfr_sasa_opts, dbfr_sasa_out, dbfr_sasa, dbfr_seq_align,
                                    dbfr_holo_site_in, dbfr_holo_site, dbfr_holo_metrics_in, dbfr_holo_metrics_opts, dbfr_holo_metrics_out,
                                    dbfr_holo_metrics, dbfr_hetero_check_in, dbfr_hetero_check_opts, dbfr_hetero_check_out,
-                                   dbfr_hetero_check, dbfr_hydrogens_in, dbfr_hydrogens_opts, dbfr_hydrogens_out, dbfr_hydrogens */
+                                   dbfr_hetero_check, dbfr_hydrogens_in, dbfr_hydrogens_opts, dbfr_hydrogens_out, dbfr_hydrogens,
+                                   dbfr_vina_decompose_in, dbfr_vina_decompose_opts, dbfr_vina_decompose_out, dbfr_vina_decompose; XS type code 17 (Met_D) in dbfr_vina_in */
 
 typedef enum {
   DBFR_OK = 0,
@@ -454,8 +455,8 @@ int dbfr_mdn_pocket_features(int32_t n_graph, int32_t n_res, const int32_t* res_
 /* ---- Vina-function refinement of sampled poses (the error-correction stage the reference delegates to `smina --minimize`,
  * DiffBindFR/app/predict.py:156-191; built here as a specified refinement, numeric parity with smina is not pinned).
  * The AutoDock Vina scoring function (Trott & Olson, J. Comput. Chem. 2010) on a rigid receptor, heavy atoms only, XS atom
- * types 0..15 = C_H C_P N_P N_D N_A N_DA O_P O_D O_A O_DA S_P P_P F_H Cl_H Br_H I_H, any other value = DUMMY (takes part in
- * no term).  Pairs with r < 8 A, d = r - R_i - R_j:  gauss1 exp(-(d/0.5)^2) x -0.035579, gauss2 exp(-((d-3)/2)^2) x -0.005156,
+ * types 0..15 = C_H C_P N_P N_D N_A N_DA O_P O_D O_A O_DA S_P P_P F_H Cl_H Br_H I_H and 17 = Met_D (a metal ion: radius 1.2 A,
+ * donor, neither hydrophobic nor acceptor), 16 and any other value = DUMMY (takes part in no term).  Pairs with r < 8 A, d = r - R_i - R_j:  gauss1 exp(-(d/0.5)^2) x -0.035579, gauss2 exp(-((d-3)/2)^2) x -0.005156,
  * repulsion d^2 (d < 0) x 0.840245, hydrophobic (both hydrophobic: 1 below 0.5, linear to 0 at 1.5) x -0.035069, hbond (donor
  * with acceptor, either way: 1 below -0.7, linear to 0 at 0) x -0.587439.  E_inter over (ligand, receptor) pairs, E_intra
  * over the listed ligand pairs; objective = E_inter + E_intra; affinity = E_inter / (1 + 0.05846 N_rot), N_rot = the graph's
@@ -1197,6 +1198,67 @@ typedef struct {                 /* device arrays, all required                 
 
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_hydrogens(const dbfr_hydrogens_in* in, const dbfr_hydrogens_opts* opts, const dbfr_hydrogens_out* out, void* hip_stream);
+
+/* ---- Per-residue and per-atom decomposition of the Vina inter-molecular energy of poses (csrc/decompose.hip;
+ * docs/decompose.md).  The batch layout is that of the sibling analyses: G groups, group g holding F_g frames of N_g ligand
+ * heavy atoms, M_g pocket atoms per frame and S_g static receptor atoms (receptor atom b: pocket atom b for b < M_g, static atom
+ * b - M_g otherwise).  Every ligand and receptor atom carries an XS type (the codes of dbfr_vina_in: 0..15, 17 = Met_D; 16 and
+ * any value outside 0..17 takes part in no term) and every receptor atom a column in 0 .. n_col_g - 1: the caller numbers the
+ * protein's residues first and the hetero residues (cofactors, ions, waters: static atoms) after them.
+ * For every pair (ligand atom i, receptor atom b) with r^2 < cutoff^2 the five weighted fp32 terms t_k(i, b) are those of
+ * dbfr_vina_score (gauss1, gauss2, repulsion, hydrophobic, hbond), each rounded once to an integer q_k = rint(t_k 2^36).
+ *   col_fixed  [sum_g F_g n_col_g, 5]  sum of q_k over the pairs of the column's atoms; frame k of g at rows col_off[g] + k n_col_g
+ *   atom_fixed [sum_g F_g N_g, 5]      sum of q_k over the pairs of the ligand atom; frame k of g at rows lig_pos_off[g] + k N_g
+ *   totals_fixed [n_frame, 6]          sum of q_k over all pairs, and the sum of the five (E_inter)
+ *   col_terms / atom_terms / totals    the same values in kcal/mol: (float)((double)sum 2^-36)
+ * Every sum is an integer sum: a frame's outputs are bitwise the same alone, in any batch and at any position in it, and the
+ * columns and the atoms of a frame both add up to its totals exactly in the integer outputs.  A column without an atom in reach
+ * holds exact zeros.  A frame with a non-finite or out-of-range (|x| > 1e4) coordinate, or (without `host`) a column outside
+ * 0 .. n_col_g - 1, gets NaN in every float row and INT64_MIN in every integer row.  Limits (DBFR_ERR_ARG beyond them):
+ * N_g in 1 .. 256, n_col_g <= 16384; receptor atoms are not limited.                                                          */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; totals are indexed by frame                            */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_type (N_g atoms per frame)                        */
+  const int64_t* lig_pos_off;    /* [G] frame k of g at rows lig_pos_off[g] + k N_g of lig_pos and of atom_terms: the groups'
+                                    rows follow each other without gaps                                                     */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const int8_t*  lig_type;       /* [lig_ptr[G]] XS types                                                                   */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_type / _col (may be 0 atoms)             */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                         */
+  const float*   pocket_pos;     /* [rows, 3]                                                                               */
+  const int8_t*  pocket_type;
+  const int32_t* pocket_col;
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / _type / _col, or NULL = none            */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of lig_pos                                              */
+  const int8_t*  static_type;
+  const int32_t* static_col;
+  const int32_t* col_ptr;        /* [G+1]: n_col_g = col_ptr[g+1] - col_ptr[g]                                               */
+  const int64_t* col_off;        /* [G] frame k of g at rows col_off[g] + k n_col_g of col_terms: without gaps, as lig_pos_off */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 16384)                                       */
+  int32_t        max_col;
+  const void*    host;           /* NULL, or a dbfr_vina_decompose_in whose pointers are HOST copies of the same arrays (positions
+                                    and types are not read): every count, row offset and column is then validated before
+                                    the launch (DBFR_ERR_ARG)                                                               */
+} dbfr_vina_decompose_in;
+
+typedef struct {
+  float cutoff;                  /* A, 8.0, in (0, 16]                                                                      */
+} dbfr_vina_decompose_opts;
+
+typedef struct {                 /* device arrays; any but col_fixed may be NULL                                            */
+  float*   col_terms;            /* [sum_g F_g n_col_g, 5]                                                                  */
+  float*   atom_terms;           /* [sum_g F_g N_g, 5]                                                                      */
+  float*   totals;               /* [n_frame, 6]                                                                            */
+  int64_t* col_fixed;            /* [sum_g F_g n_col_g, 5]: the column sums are accumulated here                             */
+  int64_t* atom_fixed;           /* [sum_g F_g N_g, 5]                                                                      */
+  int64_t* totals_fixed;         /* [n_frame, 6]                                                                            */
+} dbfr_vina_decompose_out;
+
+/* One launch for the whole batch.  opts NULL = defaults.                                                                    */
+int dbfr_vina_decompose(const dbfr_vina_decompose_in* in, const dbfr_vina_decompose_opts* opts, const dbfr_vina_decompose_out* out,
+                        void* hip_stream);
 
 /* ---- XTC trajectory encoding (csrc/xtc.hip; docs/trajectory.md).  A batch of n_frame frames, each written into one of n_file
  * files; a file is the frames listed for it, in frame order, with one atom map.  Atom k of a frame is atom_map[map_ptr[m] + k]

@@ -1795,3 +1795,113 @@ extern "C" int dbfr_test_reduce_ln(dbfr_model* m, int32_t layer, int32_t family,
   HIPCHECK(hipGetLastError());
   return DBFR_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// (ABI 8) Test hooks: the small kernels of the score network alone -- each runs the launcher run_score calls, with the model's own packed weights and
+// tables, on caller-supplied device buffers; nothing is synchronised.
+extern "C" int dbfr_test_time_embed(const dbfr_model* m, const float* t, int32_t G, float* temb_out, void* hip_stream) {
+  if (!m || !t || !temb_out || G <= 0) return fail(DBFR_ERR_ARG, "dbfr_test_time_embed: null argument");
+  launch_time_embed(t, G, m->cfg.emb_scale, temb_out, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mlp(const dbfr_model* m, int32_t which, int32_t n_rows_max, const int32_t* n_rows_dev, const float* temb,
+                             const int32_t* row_graph_tab, const int32_t* tgt, const int32_t* aux, const float* dist, const float* bond_feat,
+                             const float* lig_node, float* out, void* hip_stream) {
+  if (!m || !out) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: null argument");
+  // the weight set, the input mode and the Gaussian tables run_score pairs with it
+  struct { const Mlp2* w; int mode; const float *off, *c; } sets[7] = {
+      {&m->lig_node_emb, IN_LIGNODE, nullptr, nullptr},
+      {&m->lig_edge_emb, IN_LIGEDGE, m->gs_lig_off, m->gs_lig_c},
+      {&m->atom_edge_emb, IN_TG, m->gs_atom_off, m->gs_atom_c},
+      {&m->la_edge_emb, IN_TG, m->gs_cross_off, m->gs_cross_c},
+      {&m->center_edge_emb, IN_TG, m->gs_center_off, m->gs_center_c},
+      {&m->tor_edge_emb, IN_G, m->gs_lig_off, m->gs_lig_c},
+      {&m->sc_edge_emb, IN_G, m->gs_atom_off, m->gs_atom_c}};
+  if (which < 0 || which >= 7 || (which == DBFR_MLP_SC_EDGE && m->cfg.no_sc_torsion)) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: no such weight set");
+  const int mode = sets[which].mode;
+  if (n_rows_max < 0) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: negative row capacity");
+  if (mode != IN_G && (!temb || !row_graph_tab)) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: null time embedding or batch vector");
+  if (mode != IN_LIGNODE && !dist) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: null distances");
+  if (mode == IN_LIGEDGE && (!aux || !bond_feat)) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: null bond index or bond features");
+  if (mode == IN_LIGNODE && !lig_node) return fail(DBFR_ERR_ARG, "dbfr_test_mlp: null ligand node features");
+  MlpArgs a; memset(&a, 0, sizeof a);
+  a.w = *sets[which].w; a.mode = mode; a.n_rows_dev = n_rows_dev; a.n_rows_max = n_rows_max; a.temb = temb; a.row_graph_tab = row_graph_tab;
+  a.tgt = tgt; a.aux = aux; a.dist = dist; a.bond_feat = bond_feat; a.nfeat = m->cfg.lig_edge_features;
+  a.lig_node = lig_node; a.nnode = m->cfg.lig_node_features;
+  a.gs_offset = sets[which].off; a.gs_coeff = sets[which].c; a.out = out;
+  launch_mlp(a, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_atom_encoder(const dbfr_model* m, const float* pocket_feat, const int32_t* atm_batch, const float* temb, int32_t NA,
+                                      float* out, void* hip_stream) {
+  if (!m || !pocket_feat || !atm_batch || !temb || !out || NA < 0) return fail(DBFR_ERR_ARG, "dbfr_test_atom_encoder: null argument");
+  AtomEncArgs a; a.pocket_feat = pocket_feat; a.atm_batch = atm_batch; a.temb = temb;
+  for (int i = 0; i < 5; ++i) { a.emb[i] = m->atom_emb[i]; a.dims[i] = m->atom_dims[i]; }
+  a.lin_t = m->atom_lin_t; a.NA = NA; a.out = out;
+  launch_atom_encoder(a, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_reduce_ln_layer(const dbfr_model* m, int32_t layer, const float* const* msg, const int32_t* const* row_start,
+                                         const int32_t* const* row_cnt, const uint8_t* const* seg_first, int32_t NL, int32_t NA, const float* old_l,
+                                         const float* old_a, float* out_l, float* out_a, void* hip_stream) {
+  if (!m || !msg || !row_start || !row_cnt || !old_l || !old_a || !out_l || !out_a) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln_layer: null argument");
+  if (layer < 0 || layer >= m->cfg.num_conv_layers || NL < 0 || NA < 0) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln_layer: no such layer");
+  ReduceLayerArgs ra;
+  for (int i = 0; i < 4; ++i) {
+    if (!msg[i] || !row_start[i] || !row_cnt[i] || (seg_first && !seg_first[i])) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln_layer: null edge-set argument");
+    ra.msg[i] = msg[i]; ra.row_start[i] = row_start[i]; ra.row_cnt[i] = row_cnt[i]; ra.ln[i] = m->layer[layer][i].ln;
+    ra.first[i] = seg_first ? seg_first[i] : nullptr; ra.sc_lanes[i] = seg_first ? convz_sc_lanes(m->layerz[layer][i]) : 0;
+  }
+  ra.NL = NL; ra.NA = NA; ra.D = m->layer[layer][0].D_out; ra.D_old = m->layer[layer][0].D_in;
+  ra.old_l = old_l; ra.old_a = old_a; ra.out_l = out_l; ra.out_a = out_a;
+  launch_reduce_ln_layer(ra, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_center_edges(const dbfr_batch* b, int32_t* tgt, int32_t* gth, float* dist, float* sh, int32_t* row_start, int32_t* row_cnt,
+                                      void* hip_stream) {
+  if (!b || !tgt || !gth || !dist || !sh || !row_start || !row_cnt || !b->lig_ptr || !b->lig_pos || b->G <= 0)
+    return fail(DBFR_ERR_ARG, "dbfr_test_center_edges: null argument");
+  launch_center_edges(*b, tgt, gth, dist, sh, row_start, row_cnt, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_trrot(const dbfr_model* m, const float* gp, const float* temb, const float* tr_sigma, const float* rot_norm, int32_t G,
+                               float* tr_out, float* rot_out, int32_t* err_word, void* hip_stream) {
+  if (!m || !gp || !temb || !tr_sigma || !rot_norm || !tr_out || !rot_out || !err_word || G <= 0) return fail(DBFR_ERR_ARG, "dbfr_test_trrot: null argument");
+  TrRotArgs a; a.gp = gp; a.temb = temb; a.tr_sigma = tr_sigma; a.rot_norm = rot_norm;
+  a.tr = m->tr_final; a.rot = m->rot_final; a.G = G; a.scale_by_sigma = m->cfg.scale_by_sigma; a.tr_out = tr_out;
+  a.rot_out = rot_out; a.err = err_word;
+  launch_trrot(a, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_bond_attr(const dbfr_model* m, int32_t which, const float* nodes, int32_t ld, const int32_t* b0, const int32_t* b1,
+                                   const int32_t* bsel, int32_t n, float* attr_out, void* hip_stream) {
+  if (!m || !nodes || !b0 || !attr_out || n < 0 || ld < NS) return fail(DBFR_ERR_ARG, "dbfr_test_bond_attr: null argument");
+  if (which == DBFR_TOR_LIGAND) {
+    if (!b1 || !bsel) return fail(DBFR_ERR_ARG, "dbfr_test_bond_attr: the ligand head needs bond_dst and tor_bond");
+    launch_bond_attr(nodes, ld, b0, b1, bsel, 0, n, attr_out, (hipStream_t)hip_stream);
+  } else if (which == DBFR_TOR_SIDECHAIN) {
+    launch_bond_attr(nodes, ld, b0, nullptr, nullptr, 2, n, attr_out, (hipStream_t)hip_stream);
+  } else return fail(DBFR_ERR_ARG, "dbfr_test_bond_attr: no such head");
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_tor_final(const dbfr_model* m, int32_t which, const float* feat, const float* norm2, int32_t n, float* out, void* hip_stream) {
+  if (!m || !feat || !norm2 || !out || n < 0) return fail(DBFR_ERR_ARG, "dbfr_test_tor_final: null argument");
+  if (which != DBFR_TOR_LIGAND && (which != DBFR_TOR_SIDECHAIN || m->cfg.no_sc_torsion)) return fail(DBFR_ERR_ARG, "dbfr_test_tor_final: no such head");
+  launch_tor_final(feat, which == DBFR_TOR_LIGAND ? m->tor_final : m->sc_final, norm2, m->cfg.scale_by_sigma, n, out, (hipStream_t)hip_stream);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
+}

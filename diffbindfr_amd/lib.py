@@ -7,6 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DBFR_LIB") or os.path.join(HERE, "libdbfr.so")      # DBFR_LIB: developer override (kernel variants)
 
 DBFR_OK = 0
+DBFR_ERR_ARG = -1
 DBFR_ERR_CAPACITY = -3
 ERRORS = {-1: "DBFR_ERR_ARG", -2: "DBFR_ERR_HIP", -3: "DBFR_ERR_CAPACITY", -4: "DBFR_ERR_SELFTEST",
           -5: "DBFR_ERR_NUMERIC"}
@@ -298,6 +299,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_sample_range", "dbfr_capacity_report",
            "dbfr_init_poses", "dbfr_extract_templates", "dbfr_status_sync", "dbfr_abi_version", "dbfr_build_id", "dbfr_last_error", "dbfr_wigner3j", "dbfr_conv_paths", "dbfr_test_pack_f16_tiles", "dbfr_test_pack_f16_rows", "dbfr_test_chunk_table", "dbfr_test_pack_f16_depth", "dbfr_probe_mfma_f16",
            "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2", "dbfr_test_sde_step",
+           "dbfr_test_time_embed", "dbfr_test_mlp", "dbfr_test_atom_encoder", "dbfr_test_reduce_ln_layer", "dbfr_test_center_edges", "dbfr_test_trrot", "dbfr_test_bond_attr", "dbfr_test_tor_final",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
@@ -365,6 +367,14 @@ def load():
     lib.dbfr_test_reduce_ln.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp]
     lib.dbfr_test_reduce_ln2.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp]
     lib.dbfr_test_sde_step.argtypes = [vp, C.POINTER(Batch), C.POINTER(Step), C.POINTER(Scores), C.POINTER(Noise), vp, vp, vp]
+    lib.dbfr_test_time_embed.argtypes = [vp, vp, i32, vp, vp]
+    lib.dbfr_test_mlp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.dbfr_test_atom_encoder.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    lib.dbfr_test_reduce_ln_layer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp]
+    lib.dbfr_test_center_edges.argtypes = [C.POINTER(Batch), vp, vp, vp, vp, vp, vp, vp]
+    lib.dbfr_test_trrot.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.dbfr_test_bond_attr.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]
+    lib.dbfr_test_tor_final.argtypes = [vp, i32, vp, vp, i32, vp, vp]
     lib.dbfr_select_pocket.argtypes = [i32, i32, vp, i32, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]
     lib.dbfr_pose_metrics.argtypes = [C.POINTER(PoseMetricsIn), C.POINTER(PoseMetricsOut), vp]
     lib.dbfr_pdb_format.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, i32, i32, vp, C.c_int64]
@@ -408,7 +418,7 @@ def load():
     lib.dbfr_hetero_check.argtypes = [C.POINTER(HeteroCheckIn), C.POINTER(HeteroCheckOpts), C.POINTER(HeteroCheckOut), vp]
     lib.dbfr_hydrogens.argtypes = [C.POINTER(HydrogensIn), C.POINTER(HydrogensOpts), C.POINTER(HydrogensOut), vp]
     lib.dbfr_vina_decompose.argtypes = [C.POINTER(VinaDecomposeIn), C.POINTER(VinaDecomposeOpts), C.POINTER(VinaDecomposeOut), vp]
-    if lib.dbfr_abi_version() != 7:
+    if lib.dbfr_abi_version() != 8:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib
     return lib

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DBFR_ABI_VERSION 7   /* 2: + dbfr_sample_range, dbfr_capacity_report, dbfr_sdf_*, dbfr_mdn_*, dbfr_build_id, dbfr_test_conv2;
+#define DBFR_ABI_VERSION 8   /* 2: + dbfr_sample_range, dbfr_capacity_report, dbfr_sdf_*, dbfr_mdn_*, dbfr_build_id, dbfr_test_conv2;
                                 3: + dbfr_model_set_edge_log, dbfr_model_fallback_convs, dbfr_test_pack_f16_depth, dbfr_probe_mfma_f16 (additions only);
                                 4: + DBFR_GEMM_REDUCE_FIRST (the new default), dbfr_profile_executed_flops; dbfr_model_set_edge_log takes the graph capacity; DBFR_GEMM_SPLIT_BF16_L1 (k_conv2s) retired; dbfr_test_conv2's message rows in that mode hold segment sums;
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
@@ -48,7 +48,8 @@ extern "C" {
                                    dbfr_holo_site_in, dbfr_holo_site, dbfr_holo_metrics_in, dbfr_holo_metrics_opts, dbfr_holo_metrics_out,
                                    dbfr_holo_metrics, dbfr_hetero_check_in, dbfr_hetero_check_opts, dbfr_hetero_check_out,
                                    dbfr_hetero_check, dbfr_hydrogens_in, dbfr_hydrogens_opts, dbfr_hydrogens_out, dbfr_hydrogens,
-                                   dbfr_vina_decompose_in, dbfr_vina_decompose_opts, dbfr_vina_decompose_out, dbfr_vina_decompose; XS type code 17 (Met_D) in dbfr_vina_in */
+                                   dbfr_vina_decompose_in, dbfr_vina_decompose_opts, dbfr_vina_decompose_out, dbfr_vina_decompose; XS type code 17 (Met_D) in dbfr_vina_in;
+                                8: + dbfr_test_time_embed, dbfr_test_mlp, dbfr_test_atom_encoder, dbfr_test_reduce_ln_layer, dbfr_test_center_edges, dbfr_test_trrot, dbfr_test_bond_attr, dbfr_test_tor_final (additions only) */
 
 typedef enum {
   DBFR_OK = 0,
@@ -1516,6 +1517,55 @@ int dbfr_test_reduce_ln2(dbfr_model* m, int32_t layer, int32_t family, const flo
  * first) receives the status bits the kernels raised (2 = the Kabsch determinant check); nothing is synchronised.                             */
 int dbfr_test_sde_step(const dbfr_model* m, const dbfr_batch* b, const dbfr_step* step, const dbfr_scores* scores,
                        const dbfr_noise* z, float* atom14_out, int32_t* err_word_out, void* hip_stream);
+
+/* (ABI 8) Test hooks: the SMALL kernels of the score network alone (tests/test_walk_kernels_gpu.py).  Each runs the launcher the score call runs, with
+ * the model's own packed weights and tables, on caller-supplied DEVICE buffers; each refuses a null argument it needs with DBFR_ERR_ARG and
+ * synchronises nothing.
+ *
+ * dbfr_test_time_embed        k_time_embed: temb_out [G,32] = sinusoidal embedding of cfg.emb_scale * t[g].
+ * dbfr_test_mlp               k_mlp with weight set `which` (DBFR_MLP_*), in the input mode and with the Gaussian table the score call pairs with
+ *                             it: LIG_NODE rows [lig_node(27) | temb[g]], g = row_graph_tab[row]; LIG_EDGE rows [bond_feat[aux] or 0 where
+ *                             aux = -1 | temb[g] | gauss(dist)]; ATOM_EDGE, LA_EDGE, CENTER_EDGE rows [temb[g] | gauss(dist)]; TOR_EDGE, SC_EDGE
+ *                             rows [gauss(dist)].  Edge rows: g = row_graph_tab[tgt[row]], or row_graph_tab[row] where tgt is NULL (the centre
+ *                             set).  n_rows_dev (device int32, or NULL) caps the rows at min(*n_rows_dev, n_rows_max); out [n_rows_max,48],
+ *                             rows past the count are not written.  Arguments a mode does not read may be NULL.
+ * dbfr_test_atom_encoder      k_atom_encoder: pocket_feat [NA,5] (category ids as floats), atm_batch [NA], temb [G,32] -> out [NA,48].
+ * dbfr_test_reduce_ln_layer   k_reduce_ln_layer of interaction layer `layer`: the four reductions of the layer in one launch.  msg, row_start,
+ *                             row_cnt: four device pointers each, in the order ligand<-ligand, ligand<-pocket, pocket<-pocket, pocket<-ligand
+ *                             (messages [edges, D_out], CSR rows of the NL ligand / NA pocket targets); seg_first: NULL (every column of every
+ *                             row is summed), or four flag arrays as dbfr_test_reduce_ln2 takes them.  out_l [NL,D_out] = (pad(old_l [NL,D_in]) +
+ *                             LN(mean 0)) + LN(mean 1), out_a likewise from sets 2 and 3.
+ * dbfr_test_center_edges      k_center_edges: reads b->G, b->lig_ptr, b->lig_pos only; tgt, gth, dist [NL], sh [NL,9], row_start, row_cnt [G].
+ * dbfr_test_trrot             k_trrot: gp [G,12] -> tr_out, rot_out [G,3] with cfg.scale_by_sigma; raises bit 2 of *err_word (device int32, NOT
+ *                             cleared by the hook) where an output is not finite.
+ * dbfr_test_bond_attr         k_bond_attr in the addressing of head `which` (DBFR_TOR_*): LIGAND attr[k] = nodes[b0[bsel[k]]] + nodes[b1[bsel[k]]],
+ *                             SIDECHAIN attr[k] = nodes[b0[2k]] + nodes[b0[2k+1]] (b1, bsel not read); the first 48 columns of rows of `ld` floats.
+ * dbfr_test_tor_final         k_tor_final with the head's final MLP: feat [n,96], norm2 [n] -> out [n], times sqrt(norm2) under cfg.scale_by_sigma. */
+#define DBFR_MLP_LIG_NODE 0
+#define DBFR_MLP_LIG_EDGE 1
+#define DBFR_MLP_ATOM_EDGE 2
+#define DBFR_MLP_LA_EDGE 3
+#define DBFR_MLP_CENTER_EDGE 4
+#define DBFR_MLP_TOR_EDGE 5
+#define DBFR_MLP_SC_EDGE 6
+#define DBFR_TOR_LIGAND 0
+#define DBFR_TOR_SIDECHAIN 1
+int dbfr_test_time_embed(const dbfr_model* m, const float* t, int32_t G, float* temb_out, void* hip_stream);
+int dbfr_test_mlp(const dbfr_model* m, int32_t which, int32_t n_rows_max, const int32_t* n_rows_dev, const float* temb,
+                  const int32_t* row_graph_tab, const int32_t* tgt, const int32_t* aux, const float* dist, const float* bond_feat,
+                  const float* lig_node, float* out, void* hip_stream);
+int dbfr_test_atom_encoder(const dbfr_model* m, const float* pocket_feat, const int32_t* atm_batch, const float* temb, int32_t NA,
+                           float* out, void* hip_stream);
+int dbfr_test_reduce_ln_layer(const dbfr_model* m, int32_t layer, const float* const* msg, const int32_t* const* row_start,
+                              const int32_t* const* row_cnt, const uint8_t* const* seg_first, int32_t NL, int32_t NA, const float* old_l,
+                              const float* old_a, float* out_l, float* out_a, void* hip_stream);
+int dbfr_test_center_edges(const dbfr_batch* b, int32_t* tgt, int32_t* gth, float* dist, float* sh, int32_t* row_start, int32_t* row_cnt,
+                           void* hip_stream);
+int dbfr_test_trrot(const dbfr_model* m, const float* gp, const float* temb, const float* tr_sigma, const float* rot_norm, int32_t G,
+                    float* tr_out, float* rot_out, int32_t* err_word, void* hip_stream);
+int dbfr_test_bond_attr(const dbfr_model* m, int32_t which, const float* nodes, int32_t ld, const int32_t* b0, const int32_t* b1,
+                        const int32_t* bsel, int32_t n, float* attr_out, void* hip_stream);
+int dbfr_test_tor_final(const dbfr_model* m, int32_t which, const float* feat, const float* norm2, int32_t n, float* out, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -199,7 +199,7 @@ def test_new_symbols_resolve_and_the_struct_matches_the_header(tmp_path):
     lib = L.load()
     for sym in ("dbfr_vina_flex_workspace_bytes", "dbfr_vina_flex_score_at", "dbfr_vina_flex_minimize"):
         assert sym in L.SYMBOLS and hasattr(lib, sym)
-    assert lib.dbfr_abi_version() == 7
+    assert lib.dbfr_abi_version() == 8
     structs = {"dbfr_vina_flex_in": L.VinaFlexIn, "dbfr_vina_in": L.VinaIn, "dbfr_vina_opts": L.VinaOpts}
     fields = {s: [f for f, _ in cls._fields_] for s, cls in structs.items()}
     body = "".join(f'printf("{s} %zu\\n", sizeof({s}));' + "".join(f'printf("{s}.{f} %zu\\n", offsetof({s},{f}));' for f in fs)

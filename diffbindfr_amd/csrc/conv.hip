@@ -685,8 +685,141 @@ __global__ __launch_bounds__(256) void k_reduce_ln_layer(ReduceLayerArgs a) {
   }
 }
 
+// The same layer for the three irrep layouts the interaction layers have: 48x0e + 12x1o (NBLK = 2), + 12x1e (3), + 48x0o (4).  Every addition,
+// division and product of the form above, operand for operand -- as hipcc compiles mean_ln under this file's -ffp-contract=fast: v - mean * shift is
+// ONE fused operation there and so is v * v + 0 (the bits of the product), v * (inv * weight) is two products and the bias a separate addition;
+// the fused ones are spelled __builtin_fmaf here and the last product is kept from contracting -- issued in another order:
+//   * the rows of BOTH edge sets are summed before either LayerNorm starts, and the LayerNorm's parameters, one value per lane and block, are
+//     requested in one go behind them (the descriptor loop fetched each behind a wait of its own: three dependent round trips per block);
+//   * a block has at most 48 elements, so lane i keeps element i of every block in a register (the loops `i = lane, lane + 64, ...` have one trip:
+//     a lane's partial sum is 0 + v); LDS only turns the float4-per-lane row sums into that layout;
+//   * the butterflies of all blocks and of both sets -- 16 for the means, 8 for the squares at NBLK = 4 -- run side by side, stage by stage in
+//     the order 32, 16, ..., 1 with the very pairs of __shfl_xor (lanes i and i ^ o; 8, 2 and 1 as DPP row rotations / quad permutations);
+//   * lane i has element i of both sets, so (old + a) + b is formed and stored from registers.
+template <int O> __device__ __forceinline__ float xor_lane(float x) {
+  if constexpr (O == 8) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x128, 0xf, 0xf, false));        // row_ror:8: lane i ^ 8 of its row of 16
+  else if constexpr (O == 2) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4e, 0xf, 0xf, false));   // quad_perm [2, 3, 0, 1]
+  else if constexpr (O == 1) return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xb1, 0xf, 0xf, false));   // quad_perm [1, 0, 3, 2]
+  else return __shfl_xor(x, O);
+}
+
+template <int O, int N> __device__ __forceinline__ void xor_stage(float (&x)[N]) {
+  float y[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) y[i] = xor_lane<O>(x[i]);
+#pragma unroll
+  for (int i = 0; i < N; ++i) x[i] += y[i];
+}
+
+template <int N> __device__ __forceinline__ void xor_butterflies(float (&x)[N]) {
+  xor_stage<32>(x); xor_stage<16>(x); xor_stage<8>(x); xor_stage<4>(x); xor_stage<2>(x); xor_stage<1>(x);
+}
+
+template <int NBLK>
+__global__ __launch_bounds__(256, NBLK == 4 ? 7 : 8) void k_reduce_ln_layer_fixed(ReduceLayerArgs a) {       // (NBLK = 4 takes 65 registers: seven waves per SIMD, measured equal to eight with one register spilled)
+  constexpr int D = NBLK == 2 ? 84 : NBLK == 3 ? 120 : MAXD;
+  constexpr int MUL[4] = {48, 12, 12, 48}, DIM[4] = {1, 3, 3, 1}, OFF[4] = {0, 48, 84, 120}, IW[4] = {0, 48, 60, 72};
+  constexpr int NCH = NBLK == 2 ? 4 : NBLK == 3 ? 7 : 8;      // mean butterflies per set: one per scalar block, three per vector block
+  __shared__ float buf[4][2][MAXD];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nbl = (a.NL + 3) / 4;
+  const bool lig = (int)blockIdx.x < nbl;
+  const int node = (lig ? blockIdx.x : blockIdx.x - nbl) * 4 + wave;
+  const int N = lig ? a.NL : a.NA;
+  if (node >= N) return;                         // waves are independent here (wave-level barriers only)
+  const int s0 = lig ? 0 : 2;
+  const int rs0 = a.row_start[s0][node], rc0 = a.row_cnt[s0][node], rs1 = a.row_start[s0 + 1][node], rc1 = a.row_cnt[s0 + 1][node];
+  f32x4 acc[2];
+  acc[0] = row_sum(a.msg[s0], rs0, rc0, D, lane, a.first[s0], a.sc_lanes[s0]);
+  acc[1] = row_sum(a.msg[s0 + 1], rs1, rc1, D, lane, a.first[s0 + 1], a.sc_lanes[s0 + 1]);
+  // lane i's parameters of element i of every block (lanes behind a block's end read its last element's and drop the result)
+  const float* old = (lig ? a.old_l : a.old_a) + (size_t)node * a.D_old;
+  float shift[2][NBLK], weight[2][NBLK], bias[2], oldv[NBLK];
+  unsigned el[NBLK];
+#pragma unroll
+  for (int b = 0; b < NBLK; ++b) {
+    el[b] = min(lane, MUL[b] * DIM[b] - 1);
+    const unsigned un = IW[b] + (DIM[b] == 3 ? el[b] / 3u : el[b]);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) { shift[s][b] = a.ln[s0 + s].mean_shift[un]; weight[s][b] = a.ln[s0 + s].weight[un]; }
+    oldv[b] = OFF[b] + el[b] < (unsigned)a.D_old ? old[OFF[b] + el[b]] : 0.f;
+  }
+#pragma unroll
+  for (int s = 0; s < 2; ++s) bias[s] = a.ln[s0 + s].bias[el[0]];
+  if (lane < D / 4) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float cntf = (float)max(s ? rc1 : rc0, 1);
+      float* bw = buf[wave][s] + 4 * lane;
+      bw[0] = acc[s][0] / cntf; bw[1] = acc[s][1] / cntf; bw[2] = acc[s][2] / cntf; bw[3] = acc[s][3] / cntf;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  float v[2][NBLK], mean[2 * NCH];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    int ch = s * NCH;
+#pragma unroll
+    for (int b = 0; b < NBLK; ++b) {
+      v[s][b] = buf[wave][s][OFF[b] + el[b]];
+      const bool in = lane < MUL[b] * DIM[b];
+      const int comp = DIM[b] == 3 ? lane % 3 : 0;
+#pragma unroll
+      for (int c = 0; c < DIM[b]; ++c) mean[ch++] = in && comp == c ? 0.f + v[s][b] : 0.f;
+    }
+  }
+  xor_butterflies(mean);
+  float sq[2 * NBLK];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    int ch = s * NCH;
+#pragma unroll
+    for (int b = 0; b < NBLK; ++b) {
+      float m[3];
+#pragma unroll
+      for (int c = 0; c < DIM[b]; ++c) m[c] = mean[ch++] / (float)MUL[b];
+      const int comp = DIM[b] == 3 ? lane % 3 : 0;
+      const float mc = DIM[b] == 3 ? (comp == 0 ? m[0] : comp == 1 ? m[1] : m[2]) : m[0];
+      v[s][b] = __builtin_fmaf(-shift[s][b], mc, v[s][b]);
+      sq[s * NBLK + b] = lane < MUL[b] * DIM[b] ? __builtin_fmaf(v[s][b], v[s][b], 0.f) : 0.f;
+    }
+  }
+  xor_butterflies(sq);
+  float* out = (lig ? a.out_l : a.out_a) + (size_t)node * D;
+#pragma unroll
+  for (int b = 0; b < NBLK; ++b) {
+    float r[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const float inv = 1.0f / sqrtf(sq[s * NBLK + b] / (float)(MUL[b] * DIM[b]) + 1e-5f);
+      r[s] = v[s][b] * (inv * weight[s][b]);
+      asm("" : "+v"(r[s]));      // rounded on its own: nothing may contract this product with the additions behind it (-ffp-contract=fast)
+      if (b == 0) r[s] += bias[s];
+    }
+    if (lane < MUL[b] * DIM[b]) out[OFF[b] + lane] = (oldv[b] + r[0]) + r[1];
+  }
+}
+
+// the layout k_reduce_ln_layer_fixed<nblk> is written for: the same blocks in all four sets, biases on the first block alone
+static int reduce_ln_fixed_layout(const ReduceLayerArgs& a) {
+  static const int mul[4] = {48, 12, 12, 48}, dim[4] = {1, 3, 3, 1}, off[4] = {0, 48, 84, 120};
+  const int nblk = a.ln[0].nblk;
+  if (nblk < 2 || nblk > 4 || a.D != off[nblk - 1] + mul[nblk - 1] * dim[nblk - 1] || a.D_old > a.D) return 0;
+  for (int s = 0; s < 4; ++s) {
+    if (a.ln[s].nblk != nblk) return 0;
+    for (int b = 0; b < nblk; ++b)
+      if (a.ln[s].mul[b] != mul[b] || a.ln[s].dim[b] != dim[b] || a.ln[s].off[b] != off[b] || (a.ln[s].is0e[b] != 0) != (b == 0)) return 0;
+  }
+  return nblk;
+}
+
 void launch_reduce_ln_layer(const ReduceLayerArgs& a, hipStream_t st) {
   const int nb = (a.NL + 3) / 4 + (a.NA + 3) / 4;
   if (nb <= 0) return;
-  hipLaunchKernelGGL(k_reduce_ln_layer, dim3(nb), dim3(256), 0, st, a);
+  switch (reduce_ln_fixed_layout(a)) {
+    case 2: hipLaunchKernelGGL(k_reduce_ln_layer_fixed<2>, dim3(nb), dim3(256), 0, st, a); break;
+    case 3: hipLaunchKernelGGL(k_reduce_ln_layer_fixed<3>, dim3(nb), dim3(256), 0, st, a); break;
+    case 4: hipLaunchKernelGGL(k_reduce_ln_layer_fixed<4>, dim3(nb), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL(k_reduce_ln_layer, dim3(nb), dim3(256), 0, st, a);       // any other layout: the descriptor-driven form
+  }
 }

@@ -788,40 +788,79 @@ struct MlpArgs {
 #define MLP_ROWS 64
 #define MLP_MAXIN 80
 
-__global__ __launch_bounds__(256) void k_mlp(MlpArgs a) {
+// LDS that lanes of a wave wrote is read by other lanes of the SAME wave: the hardware runs a wave's LDS instructions in order; this keeps the
+// compiler from moving the reads in front of the writes.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// KS > 0: the k-steps of layer 1 (kin = 4 KS, the four input widths of the score network), and both layers' A fragments -- the same for every
+// tile of the launch -- live in registers: a lane loads its 3 KS + 36 weights once and no MFMA waits for an LDS read.  Without the 24 KB of
+// staged weights four workgroups fit a CU, so the 1 024 workgroups of a launch are all resident and one's input assembly runs under another's
+// MFMAs.  KS = 0: any other input width, weights staged in LDS.  Same instruction, same k order, same operands: same bits.
+template <int KS>
+__global__ __launch_bounds__(256, KS == 0 ? 2 : KS > 16 ? 3 : 4) void k_mlp(MlpArgs a) {
   __shared__ float xin[MLP_ROWS][MLP_MAXIN + 1];
   __shared__ float hid[MLP_ROWS][NS + 1];
-  __shared__ float w0[MLP_MAXIN * NS];
-  __shared__ float w1[NS * NS];
+  __shared__ float w0[KS ? 1 : MLP_MAXIN * NS];
+  __shared__ float w1[KS ? 1 : NS * NS];
   __shared__ float s_gs[EMB];
   const int nrows = a.n_rows_dev ? min(*a.n_rows_dev, a.n_rows_max) : a.n_rows_max;
   if ((int)blockIdx.x * MLP_ROWS >= nrows) return;
   const int in = a.w.in;
-  // weights once per workgroup, then a grid-stride walk over the 64-row tiles (one tile per workgroup cost 24 KB of weight staging per
-  // 64 rows: 275 us per call on average at the bench batch, 2 % of the step)
-  for (int i = threadIdx.x; i < in * NS; i += 256) w0[i] = a.w.w0t[i];
-  for (int i = threadIdx.x; i < NS * NS; i += 256) w1[i] = a.w.w1t[i];
-  const float coeff = a.gs_coeff ? a.gs_coeff[0] : 0.f;
-  if (threadIdx.x < EMB) s_gs[threadIdx.x] = a.gs_offset ? a.gs_offset[threadIdx.x] : 0.f;
-  __syncthreads();
-  // zero padding of the reduction dim to a multiple of 4 (MFMA k-step)
-  const int kin = (in + 3) & ~3;
-  if (kin > in)
-    for (int i = threadIdx.x; i < (kin - in) * NS; i += 256) w0[in * NS + i] = 0.f;
   typedef float f32x4 __attribute__((ext_vector_type(4)));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
   const int row = 16 * wave + n;
+  // zero padding of the reduction dim to a multiple of 4 (MFMA k-step)
+  const int kin = KS ? 4 * KS : (in + 3) & ~3;
+  // weights once per workgroup, then a grid-stride walk over the 64-row tiles (one tile per workgroup cost 24 KB of weight staging per
+  // 64 rows: 275 us per call on average at the bench batch, 2 % of the step)
+  float a0[KS ? KS : 1][3], a1[NS / 4][3];
+  if (KS) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) a0[ks][t] = 4 * ks + g < in ? a.w.w0t[(4 * ks + g) * NS + 16 * t + n] : 0.f;
+#pragma unroll
+    for (int ks = 0; ks < NS / 4; ++ks)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) a1[ks][t] = a.w.w1t[(4 * ks + g) * NS + 16 * t + n];
+  } else {
+    for (int i = threadIdx.x; i < in * NS; i += 256) w0[i] = a.w.w0t[i];
+    for (int i = threadIdx.x; i < NS * NS; i += 256) w1[i] = a.w.w1t[i];
+  }
+  const float coeff = a.gs_coeff ? a.gs_coeff[0] : 0.f;
+  if (threadIdx.x < EMB) s_gs[threadIdx.x] = a.gs_offset ? a.gs_offset[threadIdx.x] : 0.f;
+  if (!KS && kin > in)
+    for (int i = threadIdx.x; i < (kin - in) * NS; i += 256) w0[in * NS + i] = 0.f;
+  if (kin > in)      // (the padding columns of xin: written here once, no tile touches them)
+    for (int i = threadIdx.x; i < MLP_ROWS * (kin - in); i += 256) xin[i / (kin - in)][in + i % (kin - in)] = 0.f;
+  __syncthreads();
+  // From here on a wave works alone: the four threads that assemble a row (r = 16 wave + lane / 4) and the lanes whose MFMAs read it
+  // (row = 16 wave + lane % 16) are in ONE wave, and so are the writers and readers of a `hid` row -- no workgroup barrier inside the tile
+  // loop, one wave's look-ups run under the other waves' MFMAs.  What belongs to a row -- its graph (tgt -> row_graph_tab: two dependent
+  // loads), its distance, its bond -- is requested one tile ahead, in front of the MFMAs of the tile before.
+  const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
+  int gph_n = 0, bond_n = -1;
+  float dist_n = 0.f;
+  auto row_scalars = [&](int r0) {      // (rows behind the end read the last row's: loaded, never used)
+    const int arow = min(r0 + r, nrows - 1);
+    gph_n = a.mode == IN_G ? 0 : a.row_graph_tab[a.tgt ? a.tgt[arow] : arow];
+    dist_n = a.dist ? a.dist[arow] : 0.f;
+    bond_n = a.mode == IN_LIGEDGE ? a.aux[arow] : -1;
+  };
+  row_scalars(blockIdx.x * MLP_ROWS);
   for (int r0 = blockIdx.x * MLP_ROWS; r0 < nrows; r0 += gridDim.x * MLP_ROWS) {
   const int nr = min(MLP_ROWS, nrows - r0);
-  {   // input assembly: four threads per row (columns q, q + 4, ...); what belongs to the row -- its graph, its clamped distance -- is
-      // fetched once per thread, the Gaussian offsets come from LDS (element-wise assembly with a division and 3-4 dependent global
-      // loads per element was most of this kernel's time)
-    const int r = threadIdx.x >> 2, q = threadIdx.x & 3;
+  {   // input assembly: four threads per row (columns q, q + 4, ...); what belongs to the row is fetched once per thread, the Gaussian
+      // offsets come from LDS (element-wise assembly with a division and 3-4 dependent global loads per element was most of this
+      // kernel's time)
     const bool live = r < nr;
     const int arow = r0 + (live ? r : 0);
-    const int gph = a.mode == IN_G ? 0 : a.row_graph_tab[a.tgt ? a.tgt[arow] : arow];
-    const float dcl = a.dist ? fminf(a.dist[arow], s_gs[EMB - 1]) : 0.f;
-    const int bond = a.mode == IN_LIGEDGE ? a.aux[arow] : -1;
+    const int gph = gph_n, bond = bond_n;
+    const float dcl = a.dist ? fminf(dist_n, s_gs[EMB - 1]) : 0.f;
     for (int c = q; c < in; c += 4) {
       float v = 0.f;
       if (live) {
@@ -846,9 +885,8 @@ __global__ __launch_bounds__(256) void k_mlp(MlpArgs a) {
       xin[r][c] = v;
     }
   }
-  if (kin > in)
-    for (int i = threadIdx.x; i < MLP_ROWS * (kin - in); i += 256) xin[i / (kin - in)][in + i % (kin - in)] = 0.f;
-  __syncthreads();     // (also: every wave has finished reading `hid` of the previous tile)
+  wave_lds_order();
+  if (r0 + (int)gridDim.x * MLP_ROWS < nrows) row_scalars(r0 + gridDim.x * MLP_ROWS);
   // both layers on the matrix cores (v_mfma_f32_16x16x4_f32, exact fp32 products): wave w owns rows 16w..16w+15,
   // D[channel, row] orientation => lane (g, n) holds 4 consecutive output channels of row 16w + n
   f32x4 acc[3];
@@ -856,16 +894,25 @@ __global__ __launch_bounds__(256) void k_mlp(MlpArgs a) {
   for (int t = 0; t < 3; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[t][r] = a.w.b0 ? a.w.b0[16 * t + 4 * g + r] : 0.f;
-  for (int k = 0; k < kin; k += 4) {
-    const float bv = xin[row][k + g];
+  if (KS) {
 #pragma unroll
-    for (int t = 0; t < 3; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[(k + g) * NS + 16 * t + n], bv, acc[t], 0, 0, 0);
+    for (int ks = 0; ks < KS; ++ks) {
+      const float bv = xin[row][4 * ks + g];
+#pragma unroll
+      for (int t = 0; t < 3; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[ks][t], bv, acc[t], 0, 0, 0);
+    }
+  } else {
+    for (int k = 0; k < kin; k += 4) {
+      const float bv = xin[row][k + g];
+#pragma unroll
+      for (int t = 0; t < 3; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[(k + g) * NS + 16 * t + n], bv, acc[t], 0, 0, 0);
+    }
   }
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) hid[row][16 * t + 4 * g + r] = fmaxf(acc[t][r], 0.f);
-  __syncthreads();     // (also: every wave has finished reading `xin` of this tile)
+  wave_lds_order();
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -874,7 +921,7 @@ __global__ __launch_bounds__(256) void k_mlp(MlpArgs a) {
   for (int k = 0; k < NS; k += 4) {
     const float bv = hid[row][k + g];
 #pragma unroll
-    for (int t = 0; t < 3; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[(k + g) * NS + 16 * t + n], bv, acc[t], 0, 0, 0);
+    for (int t = 0; t < 3; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(KS ? a1[k / 4][t] : w1[(k + g) * NS + 16 * t + n], bv, acc[t], 0, 0, 0);
   }
   if (row < nr) {
 #pragma unroll
@@ -886,7 +933,14 @@ __global__ __launch_bounds__(256) void k_mlp(MlpArgs a) {
 void launch_mlp(const MlpArgs& a, hipStream_t st) {
   if (a.n_rows_max <= 0) return;
   const int tiles = (a.n_rows_max + MLP_ROWS - 1) / MLP_ROWS;
-  hipLaunchKernelGGL(k_mlp, dim3(tiles < 1024 ? tiles : 1024), dim3(256), 0, st, a);    // 58 KB of LDS: two workgroups per CU, four tile sequences per CU
+  const dim3 grid(tiles < 1024 ? tiles : 1024);     // 33 KB of LDS and under 128 registers: four workgroups per CU, every tile sequence resident
+  switch (a.w.hid == NS && a.w.out == NS ? a.w.in : 0) {
+    case 32: hipLaunchKernelGGL(k_mlp<8>, grid, dim3(256), 0, st, a); break;     // [gauss]
+    case 59: hipLaunchKernelGGL(k_mlp<15>, grid, dim3(256), 0, st, a); break;    // [lig_node(27) | temb]
+    case 64: hipLaunchKernelGGL(k_mlp<16>, grid, dim3(256), 0, st, a); break;    // [temb | gauss]
+    case 74: hipLaunchKernelGGL(k_mlp<19>, grid, dim3(256), 0, st, a); break;    // [bond_feat(10) | temb | gauss]
+    default: hipLaunchKernelGGL(k_mlp<0>, grid, dim3(256), 0, st, a);            // 58 KB of LDS: two workgroups per CU
+  }
 }
 
 // AtomEncoder (equibind_encoder.py:68-88): sum of 5 categorical embeddings, then

@@ -24,6 +24,11 @@
 // (flex_topology) turns residues into these lists.  Everything flexible sits behind `if constexpr (SH::kFlex)`: the rigid
 // instantiation keeps its LDS, its occupancy and, bit for bit, its results (its register allocation moved a little:
 // profiles/r17_vinaflex_resource_usage.txt).
+//
+// Monte-Carlo search (dbfr_vina_search, k_vina_search): Vina's iterated local search around the same minimiser, one workgroup per
+// (pose, chain).  vina_pose is split for it into vina_setup (the graph into LDS), vina_bfgs (the BFGS loop) and the outputs; the
+// search's LDS struct is the rigid one plus the best pose and the box.  Its random numbers are counter-based (Philox4x32-10), and
+// the generator and the mutation are __host__ __device__ so that the host tests them (dbfr_test_philox4x32, dbfr_test_vina_mutation).
 #include "common.h"
 #include <algorithm>
 
@@ -541,9 +546,12 @@ template <int NT> __device__ __forceinline__ void refuse_pose(const VinaArgs& A,
   if (threadIdx.x == 0 && A.iters) A.iters[g] = -1;
 }
 
-template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A, SH& S) {
-  constexpr int NT = SH::kFlex ? 10 : 8;   // terms per pose
-  const int g = blockIdx.x, tid = threadIdx.x;
+struct VinaDims { int l0, nl, k0, ntl, nt, ns, nf, n, na; };   // what vina_setup found of graph g
+
+// Graph g into LDS: positions, types, pairs, torsion masks and axes (and the flexible slots).  Returns false (uniformly) for a graph
+// the kernel will not touch.
+template <class SH> __device__ __forceinline__ bool vina_setup(const VinaArgs& A, SH& S, int g, VinaDims& D) {
+  const int tid = threadIdx.x;
   const VinaBatch& b = A.b;
   const int l0 = b.lig_ptr[g], nl = b.lig_ptr[g + 1] - l0;
   const int k0 = b.tor_ptr[g], ntl = b.tor_ptr[g + 1] - k0;
@@ -553,11 +561,7 @@ template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A,
   const int na = b.atm_ptr[g + 1] - b.atm_ptr[g], ne = A.in.ext_ptr ? A.in.ext_ptr[g + 1] - A.in.ext_ptr[g] : 0;
   bool refuse = nl <= 0 || nl > V_MAX_NL || ntl < 0 || nt > SH::kMaxVar - 6 || na < 0 || ne < 0 || na + ne > A.cap;
   if constexpr (SH::kFlex) refuse = refuse || nt < ntl || nf < 0 || nl + nf > V_MAX_NL || na > V_FLEX_MAX_NA;
-  if (refuse) {
-    // the host-side maxima (max_nl, max_tor, max_na, max_ext, ...) understated this graph: NaN results, nothing touched
-    refuse_pose<NT>(A, g);
-    return;
-  }
+  if (refuse) return false;   // the host-side maxima (max_nl, max_tor, max_na, max_ext, ...) understated this graph
   for (int i = tid; i < nl; i += V_THREADS) {
     for (int c = 0; c < 3; ++c) S.x0[c][i] = S.x[c][i] = S.xr[c][i] = b.lig_pos[3 * (size_t)(l0 + i) + c];
     S.lt[i] = A.in.lig_type[l0 + i];
@@ -567,10 +571,7 @@ template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A,
   __syncthreads();
   if constexpr (SH::kFlex) {
     ns = flex_setup(A, S, g, nl, ntl, na, ne);
-    if (ns < 0) {   // an inconsistent flexible list, or more slots than the stated maxima allow: NaN results, nothing touched
-      refuse_pose<NT>(A, g);
-      return;
-    }
+    if (ns < 0) return false;   // an inconsistent flexible list, or more slots than the stated maxima allow
   }
   const int p0 = A.in.pair_ptr[g], np = A.in.pair_ptr[g + 1] - p0;
   for (int k = tid; k < np; k += V_THREADS) {
@@ -591,24 +592,21 @@ template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A,
     bad = u < 0 || u >= nl || v < 0 || v >= nl || u == v;
     S.tu[tid] = bad ? 0 : u; S.tv[tid] = bad ? 0 : v;
   }
-  if (__syncthreads_or(bad)) {   // a torsion bond outside the graph's atoms: NaN results, nothing touched
-    refuse_pose<NT>(A, g);
-    return;
-  }
-  for (int k = tid; k < SH::kMaxVar; k += V_THREADS) {
-    S.p[k] = 0.f;
-    S.pn[k] = k < 6 ? (A.q_rigid ? A.q_rigid[6 * (size_t)g + k] : 0.f) : (k < 6 + ntl && A.q_tor ? A.q_tor[k0 + k - 6] : 0.f);
-    if constexpr (SH::kFlex)
-      if (k >= 6 + ntl && k < n && A.q_flex) S.pn[k] = A.q_flex[A.ft_ptr[g] + k - 6 - ntl];
-  }
-  for (int i = tid; i < n * n; i += V_THREADS) S.H[i] = (i / n == i % n) ? 1.f : 0.f;
-  if (tid == 0) S.flag = 1;   // collect the candidates at the first evaluation
-  __syncthreads();
+  if (__syncthreads_or(bad)) return false;   // a torsion bond outside the graph's atoms
+  D = {l0, nl, k0, ntl, nt, ns, nf, n, na};
+  return true;
+}
+
+// BFGS from S.pn (S.p = 0, S.H = I) over the variables of `rebuild`, whose base S.x0 is: at most max_iters accepted steps.  Leaves
+// the final positions in S.x and their terms in S.e; returns the accepted steps.  rec0: E_rec of the first evaluation (flexible).
+template <class SH> __device__ __forceinline__ int vina_bfgs(const VinaArgs& A, SH& S, int g, const VinaDims& D, int max_iters, double& rec0) {
+  const int tid = threadIdx.x;
+  const int nl = D.nl, ns = D.ns, nt = D.nt, n = D.n;
   // One evaluation per pass (a single call site of rebuild / evaluate / param_grad each keeps the scalar registers in
   // budget): phase 0 = the start q = 0, 1 = a line-search trial at pn = p + alpha d, 2 = back to p after a stalled search.
   int phase = 0, it = 0, ls = 0;
   bool identity = true;
-  double f = 0.0, rec0 = 0.0;
+  double f = 0.0;
   float alpha = 0.f, slope = 0.f;
   for (;;) {
     rebuild(S, S.pn, nl, ns, nt);
@@ -673,7 +671,7 @@ template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A,
     if (!A.minimize) break;
     float gmax = 0.f;
     for (int k = 0; k < n; ++k) gmax = fmaxf(gmax, fabsf(S.gp[k]));
-    if (gmax < A.grad_tol || it >= A.max_iters) {
+    if (gmax < A.grad_tol || it >= max_iters) {
       if (!redirect) break;     // the positions in S.x are those of p
       if (tid < n) S.pn[tid] = S.p[tid];
       phase = 2;
@@ -704,6 +702,30 @@ template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A,
     if (tid < n) S.pn[tid] = S.p[tid] + alpha * S.d[tid];
     __syncthreads();
   }
+  return it;
+}
+
+template <class SH> __device__ __forceinline__ void vina_pose(const VinaArgs& A, SH& S) {
+  constexpr int NT = SH::kFlex ? 10 : 8;   // terms per pose
+  const int g = blockIdx.x, tid = threadIdx.x;
+  const VinaBatch& b = A.b;
+  VinaDims D;
+  if (!vina_setup(A, S, g, D)) {   // NaN results, nothing touched
+    refuse_pose<NT>(A, g);
+    return;
+  }
+  const int l0 = D.l0, nl = D.nl, k0 = D.k0, ntl = D.ntl, nt = D.nt, nf = D.nf, n = D.n, na = D.na;
+  for (int k = tid; k < SH::kMaxVar; k += V_THREADS) {
+    S.p[k] = 0.f;
+    S.pn[k] = k < 6 ? (A.q_rigid ? A.q_rigid[6 * (size_t)g + k] : 0.f) : (k < 6 + ntl && A.q_tor ? A.q_tor[k0 + k - 6] : 0.f);
+    if constexpr (SH::kFlex)
+      if (k >= 6 + ntl && k < n && A.q_flex) S.pn[k] = A.q_flex[A.ft_ptr[g] + k - 6 - ntl];
+  }
+  for (int i = tid; i < n * n; i += V_THREADS) S.H[i] = (i / n == i % n) ? 1.f : 0.f;
+  if (tid == 0) S.flag = 1;   // collect the candidates at the first evaluation
+  __syncthreads();
+  double rec0 = 0.0;
+  const int it = vina_bfgs(A, S, g, D, A.max_iters, rec0);
   if (tid == 0) {
     if (A.terms) {
       float* t = A.terms + NT * (size_t)g;
@@ -747,6 +769,244 @@ template <int MT> __global__ __launch_bounds__(V_THREADS) void k_vina(VinaArgs A
     __shared__ SH S;
     vina_pose(A, S);
   }
+}
+
+// ------------------------------------------------------------------------------------------------ Monte-Carlo search
+// Vina's iterated local search around the minimiser above (include/dbfr.h: dbfr_vina_search; docs/vina.md, "Monte-Carlo search").
+// One workgroup per (pose, chain), block = chain * G + pose.  The chain's current pose is the base S.x0 of `rebuild`, so a mutation
+// is a q with one entity set; the best pose lives in xb.  Random numbers are Philox4x32-10 blocks addressed by (seed; stream, chain,
+// slot): nothing is carried from draw to draw, and nothing of a chain depends on another workgroup.
+struct Philox4 { uint32_t w[4]; };
+
+__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return {{c0, c1, c2, c3}};
+}
+
+__host__ __device__ inline float philox_u(uint32_t w) { return (float)(w >> 8) * (1.f / 16777216.f); }   // [0, 1)
+
+struct VinaRng {          // one (pose, chain)
+  uint32_t k0, k1, s0, s1, chain;
+  __host__ __device__ Philox4 slot(uint32_t s) const { return philox4x32_10(s0, s1, chain, s, k0, k1); }
+};
+
+__host__ __device__ inline VinaRng vina_rng(uint64_t seed, int64_t stream, int chain) {
+  return {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)(uint64_t)stream, (uint32_t)((uint64_t)stream >> 32), (uint32_t)chain};
+}
+
+#define V_TWO_PI 6.28318530717958647692f
+#define V_PI 3.14159265358979323846f
+
+// The mutation of Monte-Carlo step `step` (1-based): q[0 .. 6 + n_tor) is zero but for the chosen entity; returns the entity.
+__host__ __device__ inline int vina_mutation(const VinaRng& rng, int step, int n_tor, float amplitude, float r_g, float* q) {
+  const Philox4 r = rng.slot(2u * (uint32_t)step);
+  const int e = (int)(((uint64_t)r.w[0] * (uint64_t)(2 + n_tor)) >> 32);
+  const float u1 = philox_u(r.w[1]), u2 = philox_u(r.w[2]), u3 = philox_u(r.w[3]);
+  for (int k = 0; k < 6 + n_tor; ++k) q[k] = 0.f;
+  if (e >= 2) { q[6 + e - 2] = V_TWO_PI * u1 - V_PI; return e; }
+  const float z = 2.f * u1 - 1.f, phi = V_TWO_PI * u2, rho = cbrtf(u3);
+  const float s = sqrtf(fmaxf(1.f - z * z, 0.f));
+  const float a = e == 0 ? amplitude : amplitude / r_g;
+  q[3 * e + 0] = a * (rho * (s * cosf(phi)));
+  q[3 * e + 1] = a * (rho * (s * sinf(phi)));
+  q[3 * e + 2] = a * (rho * z);
+  return e;
+}
+
+// A random placement's variables but the translation (which needs the centroid after the torsions: k_vina_search): Shoemake's
+// uniform unit quaternion (x, y, z, w) from three uniforms as the rotation vector 2 atan2(|v|, w) v / |v|, and uniform torsions.
+__host__ __device__ inline void vina_random_start(const VinaRng& rng, int n_tor, float* q) {
+  const Philox4 r = rng.slot(1u);
+  const float u1 = philox_u(r.w[1]), u2 = philox_u(r.w[2]), u3 = philox_u(r.w[3]);
+  const float a = sqrtf(1.f - u1), b = sqrtf(u1);
+  const float x = a * sinf(V_TWO_PI * u2), y = a * cosf(V_TWO_PI * u2), z = b * sinf(V_TWO_PI * u3), w = b * cosf(V_TWO_PI * u3);
+  const float nv = sqrtf(x * x + y * y + z * z);
+  const float f = nv > 0.f ? 2.f * atan2f(nv, w) / nv : 0.f;
+  q[0] = q[1] = q[2] = 0.f;
+  q[3] = f * x; q[4] = f * y; q[5] = f * z;
+  for (int k = 0; k < n_tor; ++k) q[6 + k] = V_TWO_PI * philox_u(rng.slot(0x80000000u + (uint32_t)k).w[0]) - V_PI;
+}
+
+struct VinaSearchArgs {
+  int G, chains, n_steps, step_iters, random_start;
+  float temperature, amplitude, autobox_add;
+  uint64_t seed;
+  const int64_t* stream;   // [G]
+  float *best_pos, *cur_pos;   // [chains, NL, 3]
+  int* accepted;           // [chains, G]
+  float* log;              // [chains, G, n_steps, 8] or null
+  size_t NL;
+};
+
+struct VinaSearchShared : VinaShared<V_MAX_TOR> {
+  float xb[3][V_MAX_NL];   // the chain's best pose
+  double eb[6];            // and its terms
+  float lo[3], hi[3];      // the box
+  float rg;                // radius of gyration of the input pose
+  int ent;                 // the step's entity
+};
+static_assert(sizeof(VinaSearchShared) <= (160 * 1024) / 3, "three search workgroups per CU");
+
+__device__ __forceinline__ float v_objective(const double* e) {
+  double inter = 0.0;
+  for (int k = 0; k < 5; ++k) inter += e[k];
+  return (float)(inter + e[5]);
+}
+
+__global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearchArgs Q) {
+  __shared__ VinaSearchShared S;
+  const int tid = threadIdx.x;
+  const int g = blockIdx.x % Q.G, chain = blockIdx.x / Q.G;
+  const size_t blk = blockIdx.x;
+  // this chain's slices of the workspace and of the per-pose outputs: the device functions index them by g
+  A.cand += (size_t)chain * Q.G * A.cap;
+  A.terms += 8 * (size_t)chain * Q.G;
+  A.iters += (size_t)chain * Q.G;
+  VinaDims D;
+  if (!vina_setup(A, S, g, D)) {   // NaN terms, iters = -1, nothing touched
+    refuse_pose<8>(A, g);
+    if (tid == 0) Q.accepted[blk] = 0;
+    return;
+  }
+  const int l0 = D.l0, nl = D.nl, nt = D.nt, n = D.n;
+  const VinaRng rng = vina_rng(Q.seed, Q.stream[g], chain);
+  // the box and the radius of gyration of the input pose
+  if (tid < 3) {
+    float lo = S.x0[tid][0], hi = lo, s = 0.f;
+    for (int i = 0; i < nl; ++i) { const float v = S.x0[tid][i]; lo = fminf(lo, v); hi = fmaxf(hi, v); s += v; }
+    S.lo[tid] = lo - Q.autobox_add; S.hi[tid] = hi + Q.autobox_add; S.c[tid] = s / (float)nl;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.f;
+    for (int i = 0; i < nl; ++i) {
+      const float dx = S.x0[0][i] - S.c[0], dy = S.x0[1][i] - S.c[1], dz = S.x0[2][i] - S.c[2];
+      s += dx * dx + dy * dy + dz * dz;
+    }
+    S.rg = fmaxf(sqrtf(s / (float)nl), 1e-3f);
+    S.flag = 1;   // collect the candidates at the first evaluation
+  }
+  __syncthreads();
+  const int step_iters = Q.step_iters < 0 ? (25 + nl) / 3 : Q.step_iters;
+  // stage -1: a random placement (evaluated, not minimised); 0: the start minimisation; 1 .. n_steps: the Monte-Carlo steps;
+  // n_steps + 1: the final refinement of a best that came from a step.  (One call site of vina_bfgs, as in vina_pose.)
+  int stage = (Q.random_start && chain >= 1) ? -1 : 0;
+  int total = 0, nacc = 0;
+  bool best_from_step = false;
+  float e_cur = 0.f, e_best = 0.f;
+  for (;;) {
+    for (int k = tid; k < VinaSearchShared::kMaxVar; k += V_THREADS) { S.p[k] = 0.f; S.pn[k] = 0.f; }
+    for (int i = tid; i < n * n; i += V_THREADS) S.H[i] = (i / n == i % n) ? 1.f : 0.f;
+    __syncthreads();
+    if (tid == 0) {
+      if (stage == -1) vina_random_start(rng, nt, S.pn);
+      else if (stage >= 1 && stage <= Q.n_steps) S.ent = vina_mutation(rng, stage, nt, Q.amplitude, S.rg, S.pn);
+    }
+    __syncthreads();
+    double rec0 = 0.0;
+    const int it = vina_bfgs(A, S, g, D, stage == -1 ? 0 : (stage >= 1 && stage <= Q.n_steps) ? step_iters : A.max_iters, rec0);
+    total += it;
+    __syncthreads();
+    const float e_c = v_objective(S.e);
+    bool in_box = true;
+    if (stage == -1) {
+      // the rotation was about the centroid S.c of the turned ligand, which is therefore still the centroid: move it to its draw
+      const Philox4 r = rng.slot(0u);
+      float sh[3];
+      for (int c = 0; c < 3; ++c) sh[c] = (S.lo[c] + philox_u(r.w[1 + c]) * (S.hi[c] - S.lo[c])) - S.c[c];
+      __syncthreads();
+      for (int i = tid; i < nl; i += V_THREADS)
+        for (int c = 0; c < 3; ++c) S.x0[c][i] = S.x[c][i] + sh[c];
+    } else if (stage == 0) {
+      for (int i = tid; i < nl; i += V_THREADS)
+        for (int c = 0; c < 3; ++c) S.x0[c][i] = S.xb[c][i] = S.x[c][i];
+      if (tid < 6) S.eb[tid] = S.e[tid];
+      e_cur = e_best = e_c;
+    } else {
+      int out = 0;
+      for (int i = tid; i < nl; i += V_THREADS)
+        for (int c = 0; c < 3; ++c) out |= !(S.x[c][i] >= S.lo[c] && S.x[c][i] <= S.hi[c]);
+      in_box = !__syncthreads_or(out);
+    }
+    if (stage >= 1 && stage <= Q.n_steps) {
+      const float u = philox_u(rng.slot(2u * (uint32_t)stage + 1u).w[0]);
+      // (expf: its error on a threshold below 1 is under 1e-7, and the double-precision exp costs 21 VGPRs and a wave per SIMD)
+      const bool accept = in_box && (e_c < e_cur || u < expf((e_cur - e_c) / Q.temperature));
+      if (accept) {
+        const bool better = e_c < e_best;
+        for (int i = tid; i < nl; i += V_THREADS)
+          for (int c = 0; c < 3; ++c) {
+            S.x0[c][i] = S.x[c][i];
+            if (better) S.xb[c][i] = S.x[c][i];
+          }
+        if (better) {
+          if (tid < 6) S.eb[tid] = S.e[tid];
+          e_best = e_c;
+          best_from_step = true;
+        }
+        e_cur = e_c;
+        ++nacc;
+      }
+      if (Q.log && tid == 0) {
+        float* L = Q.log + 8 * ((size_t)blk * Q.n_steps + (stage - 1));
+        L[0] = (float)S.ent; L[1] = e_c; L[2] = in_box ? 1.f : 0.f; L[3] = u; L[4] = accept ? 1.f : 0.f;
+        L[5] = e_cur; L[6] = e_best; L[7] = (float)it;
+      }
+    } else if (stage > Q.n_steps) {   // the refined best, kept if it is not higher and has not left the box
+      if (in_box && e_c <= e_best) {
+        for (int i = tid; i < nl; i += V_THREADS)
+          for (int c = 0; c < 3; ++c) S.xb[c][i] = S.x[c][i];
+        if (tid < 6) S.eb[tid] = S.e[tid];
+      }
+    }
+    __syncthreads();
+    if (stage > Q.n_steps) break;
+    if (stage == Q.n_steps) {   // the chain's current pose; then the best becomes the base of the refinement
+      if (Q.cur_pos)
+        for (int i = tid; i < nl; i += V_THREADS)
+          for (int c = 0; c < 3; ++c) Q.cur_pos[3 * (Q.NL * chain + l0 + i) + c] = S.x0[c][i];
+      if (!best_from_step) break;
+      __syncthreads();
+      for (int i = tid; i < nl; i += V_THREADS)
+        for (int c = 0; c < 3; ++c) S.x0[c][i] = S.xb[c][i];
+    }
+    ++stage;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float* t = A.terms + 8 * (size_t)g;
+    double inter = 0.0;
+    for (int k = 0; k < 5; ++k) { t[k] = (float)S.eb[k]; inter += S.eb[k]; }
+    t[5] = (float)S.eb[5];
+    t[6] = (float)(inter + S.eb[5]);
+    t[7] = (float)(inter / (1.0 + (double)W_NROT * D.ntl));
+    A.iters[g] = total;
+    Q.accepted[blk] = nacc;
+  }
+  for (int i = tid; i < nl; i += V_THREADS)
+    for (int c = 0; c < 3; ++c) Q.best_pos[3 * (Q.NL * chain + l0 + i) + c] = S.xb[c][i];
+}
+
+extern "C" int dbfr_test_philox4x32(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
+  if (!ctr || !key || !out) { dbfr_set_error("dbfr_test_philox4x32: null argument"); return DBFR_ERR_ARG; }
+  const Philox4 r = philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
+  for (int k = 0; k < 4; ++k) out[k] = r.w[k];
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_vina_mutation(uint64_t seed, int64_t stream, int32_t chain, int32_t step, int32_t n_tor, float amplitude, float r_g,
+                                       int32_t* entity, float* q) {
+  if (!entity || !q || n_tor < 0 || step < 1 || chain < 0 || !(r_g > 0.f)) {
+    dbfr_set_error("dbfr_test_vina_mutation: entity and q [6 + n_tor], n_tor >= 0, step >= 1, chain >= 0 and r_g > 0 required");
+    return DBFR_ERR_ARG;
+  }
+  *entity = vina_mutation(vina_rng(seed, stream, chain), step, n_tor, amplitude, r_g, q);
+  return DBFR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI
@@ -866,19 +1126,8 @@ static int vina_flex_check(const dbfr_vina_flex_in* in, size_t* cap_per_pose) {
 
 struct VinaFlexOut { const float* q_flex; float *rec_out, *q_flex_out, *grad_flex; };
 
-static int vina_launch(const dbfr_vina_in* in, int minimize, const dbfr_vina_opts* opts, const float* q_rigid, const float* q_tor,
-                       float* pos_out, float* terms, float* grad_rigid, float* grad_tor, int32_t* iters, void* ws, size_t ws_bytes,
-                       void* stream, const dbfr_vina_flex_in* flex = nullptr, const VinaFlexOut* fo = nullptr) {
-  size_t cap;
-  int rc = flex ? vina_flex_check(flex, &cap) : vina_check(in, &cap);
-  if (rc) return rc;
-  const size_t need = (size_t)in->batch->G * cap * sizeof(float4);
-  if (!ws || ws_bytes < need) {
-    dbfr_set_error("dbfr_vina: workspace of " + std::to_string(ws_bytes) + " bytes, this batch needs " + std::to_string(need) +
-                   " (dbfr_vina_workspace_bytes)");
-    return DBFR_ERR_ARG;
-  }
-  VinaArgs A;
+// The kernel arguments every launch shares: the batch, the candidate workspace and the minimiser's options.
+static int vina_args(const dbfr_vina_in* in, const dbfr_vina_opts* opts, size_t cap, void* ws, VinaArgs& A) {
   memset(&A, 0, sizeof A);
   const dbfr_batch* B = in->batch;
   A.b = {B->lig_ptr, B->bond_src, B->bond_dst, B->tor_ptr, B->tor_bond, B->atm_ptr, B->lig_pos, B->rec_pos, B->rot_mask, B->rot_mask_off};
@@ -893,6 +1142,24 @@ static int vina_launch(const dbfr_vina_in* in, int minimize, const dbfr_vina_opt
     }
     A.max_iters = opts->max_iters; A.grad_tol = opts->grad_tol; A.margin = opts->margin;
   }
+  return DBFR_OK;
+}
+
+static int vina_launch(const dbfr_vina_in* in, int minimize, const dbfr_vina_opts* opts, const float* q_rigid, const float* q_tor,
+                       float* pos_out, float* terms, float* grad_rigid, float* grad_tor, int32_t* iters, void* ws, size_t ws_bytes,
+                       void* stream, const dbfr_vina_flex_in* flex = nullptr, const VinaFlexOut* fo = nullptr) {
+  size_t cap;
+  int rc = flex ? vina_flex_check(flex, &cap) : vina_check(in, &cap);
+  if (rc) return rc;
+  const size_t need = (size_t)in->batch->G * cap * sizeof(float4);
+  if (!ws || ws_bytes < need) {
+    dbfr_set_error("dbfr_vina: workspace of " + std::to_string(ws_bytes) + " bytes, this batch needs " + std::to_string(need) +
+                   " (dbfr_vina_workspace_bytes)");
+    return DBFR_ERR_ARG;
+  }
+  VinaArgs A;
+  rc = vina_args(in, opts, cap, ws, A);
+  if (rc) return rc;
   A.minimize = minimize;
   A.q_rigid = q_rigid; A.q_tor = in->batch->NTOR > 0 ? q_tor : nullptr;
   A.pos_out = pos_out; A.terms = terms; A.grad_rigid = grad_rigid; A.grad_tor = grad_tor; A.iters = iters;
@@ -930,6 +1197,61 @@ extern "C" int dbfr_vina_score_at(const dbfr_vina_in* in, const float* q_rigid, 
 extern "C" int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* terms,
                                   int32_t* iters, void* workspace, size_t workspace_bytes, void* hip_stream) {
   return vina_launch(in, 1, opts, nullptr, nullptr, lig_pos_out, terms, nullptr, nullptr, iters, workspace, workspace_bytes, hip_stream);
+}
+
+static int vina_search_check(const dbfr_vina_in* in, int64_t chains, size_t* cap) {
+  const int rc = vina_check(in, cap);
+  if (rc) return rc;
+  if (chains < 1) { dbfr_set_error("dbfr_vina_search: chains >= 1 required"); return DBFR_ERR_ARG; }
+  if ((int64_t)in->batch->G * chains > 0x7fffffff) {
+    dbfr_set_error("dbfr_vina_search: " + std::to_string(in->batch->G) + " poses x " + std::to_string(chains) + " chains exceed the grid of 2^31 - 1 workgroups");
+    return DBFR_ERR_ARG;
+  }
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_vina_search_workspace_bytes(const dbfr_vina_in* in, int32_t chains, size_t* bytes) {
+  size_t cap;
+  const int rc = vina_search_check(in, chains, &cap);
+  if (rc) return rc;
+  if (!bytes) { dbfr_set_error("dbfr_vina_search_workspace_bytes: null argument"); return DBFR_ERR_ARG; }
+  *bytes = (size_t)chains * in->batch->G * cap * sizeof(float4);
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_vina_search(const dbfr_vina_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts,
+                                const int64_t* stream, float* best_pos, float* cur_pos, float* terms, int32_t* iters, int32_t* accepted,
+                                float* log, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  dbfr_vina_search_opts so = {8, 64, -1, 1.2f, 2.f, 4.f, 0, 0};
+  if (search_opts) so = *search_opts;
+  size_t cap;
+  int rc = vina_search_check(in, so.chains, &cap);
+  if (rc) return rc;
+  if (so.n_steps < 0 || !(so.temperature > 0.f) || !(so.amplitude >= 0.f) || !(so.autobox_add >= 0.f)) {
+    dbfr_set_error("dbfr_vina_search: n_steps >= 0, temperature > 0, amplitude >= 0 and autobox_add >= 0 required");
+    return DBFR_ERR_ARG;
+  }
+  if (!stream || !best_pos || !terms || !iters || !accepted) {
+    dbfr_set_error("dbfr_vina_search: stream, best_pos, terms, iters and accepted are required");
+    return DBFR_ERR_ARG;
+  }
+  const dbfr_batch* B = in->batch;
+  const size_t need = (size_t)so.chains * B->G * cap * sizeof(float4);
+  if (!workspace || workspace_bytes < need) {
+    dbfr_set_error("dbfr_vina_search: workspace of " + std::to_string(workspace_bytes) + " bytes, this batch needs " + std::to_string(need) +
+                   " (dbfr_vina_search_workspace_bytes)");
+    return DBFR_ERR_ARG;
+  }
+  VinaArgs A;
+  rc = vina_args(in, opts, cap, workspace, A);
+  if (rc) return rc;
+  A.minimize = 1;
+  A.terms = terms; A.iters = iters;
+  const VinaSearchArgs Q = {B->G, so.chains, so.n_steps, so.step_iters, so.random_start, so.temperature, so.amplitude, so.autobox_add,
+                            so.seed, stream, best_pos, cur_pos, accepted, log, (size_t)B->NL};
+  hipLaunchKernelGGL(k_vina_search, dim3((unsigned)(B->G * so.chains)), dim3(V_THREADS), 0, (hipStream_t)hip_stream, A, Q);
+  HIPCHECK(hipGetLastError());
+  return DBFR_OK;
 }
 
 extern "C" int dbfr_vina_flex_workspace_bytes(const dbfr_vina_flex_in* in, size_t* bytes) {

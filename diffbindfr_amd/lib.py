@@ -112,6 +112,11 @@ class VinaOpts(C.Structure):
     _fields_ = [("max_iters", C.c_int32), ("grad_tol", C.c_float), ("margin", C.c_float)]
 
 
+class VinaSearchOpts(C.Structure):
+    _fields_ = [("chains", C.c_int32), ("n_steps", C.c_int32), ("step_iters", C.c_int32), ("temperature", C.c_float),
+                ("amplitude", C.c_float), ("autobox_add", C.c_float), ("random_start", C.c_int32), ("seed", C.c_uint64)]
+
+
 class PoseRmsdIn(C.Structure):
     _fields_ = [("n_group", C.c_int32), ("pose_ptr", C.c_void_p), ("atom_ptr", C.c_void_p), ("perm_ptr", C.c_void_p),
                 ("pos", C.c_void_p), ("perms", C.c_void_p), ("heavy_mask", C.c_void_p), ("max_pose", C.c_int32),
@@ -304,6 +309,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_vina_flex_workspace_bytes", "dbfr_vina_flex_score_at", "dbfr_vina_flex_minimize",
+           "dbfr_vina_search_workspace_bytes", "dbfr_vina_search", "dbfr_test_philox4x32", "dbfr_test_vina_mutation",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
@@ -396,6 +402,12 @@ def load():
     lib.dbfr_vina_flex_workspace_bytes.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(C.c_size_t)]
     lib.dbfr_vina_flex_score_at.argtypes = [C.POINTER(VinaFlexIn), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_vina_flex_minimize.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(VinaOpts), vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    lib.dbfr_vina_search_workspace_bytes.argtypes = [C.POINTER(VinaIn), i32, C.POINTER(C.c_size_t)]
+    lib.dbfr_vina_search.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), C.POINTER(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp, vp,
+                                     C.c_size_t, vp]
+    lib.dbfr_test_philox4x32.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    lib.dbfr_test_vina_mutation.argtypes = [C.c_uint64, C.c_int64, i32, i32, i32, C.c_float, C.c_float, C.POINTER(i32),
+                                            C.POINTER(C.c_float)]
     lib.dbfr_pose_rmsd_matrix.argtypes = [C.POINTER(PoseRmsdIn), vp, vp]
     lib.dbfr_select_modes.argtypes = [C.POINTER(PoseRmsdIn), vp, vp, C.POINTER(ModesOpts), vp, vp, vp, vp]
     lib.dbfr_pose_check.argtypes = [C.POINTER(PoseCheckIn), C.POINTER(PoseCheckOpts), C.POINTER(PoseCheckOut), vp]

@@ -47,6 +47,10 @@ more heavy neighbours or with one that is P or S, otherwise O_DA (a hydroxyl and
 hydrogens: the stance ``receptor_type_table`` takes for HIS); N is N_P with three or more heavy neighbours, else N_DA; S, P and
 halogens as in ``ligand_types``; any other element is DUMMY.  Parity with smina's or Vina's typing of cofactors is not claimed.
 
+Monte-Carlo search (``VinaBatch.search``, ``search_poses``, ``search_entry``, ``error_correct(exhaustiveness=)``): Vina's iterated
+local search around the minimiser, ``chains`` independent chains per pose on a rigid receptor; docs/vina.md states the algorithm
+and its random numbers (Philox4x32-10, addressed by seed, the pose's stream, chain and step).
+
 Flexible side chains (``flex_topology``, ``select_flexible``, ``VinaFlexBatch``, ``refine_entry_flex``, ``error_correct(flex_dist=)``):
 the pocket side chains near the ligand turn about their chi axes in the same minimisation; docs/vina.md states the model.
 """
@@ -58,7 +62,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .lib import DbfrError, VinaFlexIn, VinaIn, VinaOpts
+from .lib import DbfrError, VinaFlexIn, VinaIn, VinaOpts, VinaSearchOpts
 
 XS_NAMES = ["C_H", "C_P", "N_P", "N_D", "N_A", "N_DA", "O_P", "O_D", "O_A", "O_DA", "S_P", "P_P", "F_H", "Cl_H", "Br_H",
             "I_H", "DUMMY", "Met_D"]
@@ -71,6 +75,9 @@ MAX_TORSIONS = 58
 FLEX_TERMS = TERMS + ["rec", "rec_start"]
 FLEX_MAX_SLOTS, FLEX_MAX_VARS, FLEX_MAX_EXCL = 256, 128, 32     # ligand + flexible atoms + axis anchors; 6 + all torsions
 FLEX_COLUMNS = ["ec_n_flex", "ec_flex_residues", "ec_sc_moved", "ec_rec_energy"]
+SEARCH_DEFAULTS = dict(chains=8, n_steps=64, step_iters=-1, temperature=1.2, amplitude=2.0, autobox_add=4.0, random_start=False, seed=0)
+SEARCH_LOG = ["entity", "e_candidate", "in_box", "u", "accepted", "e_current", "e_best", "iters"]     # the log's last axis
+SEARCH_COLUMNS = ["ec_search_gain", "ec_search_rmsd", "ec_search_accepted"]
 
 _HALOGEN = {"F": "F_H", "Cl": "Cl_H", "Br": "Br_H", "I": "I_H"}
 _VALENCE = {"N": 3, "O": 2}
@@ -400,6 +407,53 @@ class VinaBatch:
         return out, terms, iters
 
 
+    def search(self, streams=None, max_iters=100, grad_tol=1e-3, margin=2.0, log=False, current=False, **search_opts):
+        """Monte-Carlo search from every pose (docs/vina.md, "Monte-Carlo search"): ``chains`` chains of ``n_steps`` steps per
+        pose; ``search_opts`` are the keys of ``SEARCH_DEFAULTS``.  ``streams``: int64 [G], the random stream of every pose
+        (default: its index in the batch), so that a pose's result does not depend on its batch mates.  Returns a dict: ``pos``
+        [NL,3] and ``terms`` [G,8] of the best chain per pose (lowest objective, ties to the lowest chain), ``best_chain`` [G],
+        ``chain_pos`` [chains,NL,3], ``chain_terms`` [chains,G,8], ``iters`` and ``accepted`` [chains,G] (BFGS steps, accepted
+        Monte-Carlo steps), ``log`` [chains,G,n_steps,8] (``SEARCH_LOG``; with ``log``) and ``cur_pos`` [chains,NL,3] (each chain's
+        current pose after the last step; with ``current``)."""
+        unknown = set(search_opts) - set(SEARCH_DEFAULTS)
+        if unknown:
+            raise DbfrError(f"unknown search option(s) {sorted(unknown)}: {sorted(SEARCH_DEFAULTS)}")
+        o = {**SEARCH_DEFAULTS, **search_opts}
+        pb, dev = self.pb, self.pb.lig_pos.device
+        G, NL, nc, ns = pb.G, pb.dims["NL"], int(o["chains"]), int(o["n_steps"])
+        if streams is None:
+            streams = torch.arange(G, dtype=torch.int64, device=dev)
+        streams = torch.as_tensor(streams).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        if streams.numel() != G:
+            raise DbfrError(f"{streams.numel()} streams for {G} poses")
+        lib = L.load()
+        nb = C.c_size_t(0)
+        L.check(lib.dbfr_vina_search_workspace_bytes(C.byref(self.c), nc, C.byref(nb)))
+        ws = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
+        best = torch.empty(nc, NL, 3, device=dev)
+        cur = torch.empty(nc, NL, 3, device=dev) if current else None
+        terms = torch.empty(nc, G, 8, device=dev)
+        iters = torch.empty(nc, G, dtype=torch.int32, device=dev)
+        acc = torch.empty(nc, G, dtype=torch.int32, device=dev)
+        lg = torch.empty(nc, G, max(ns, 1), 8, device=dev) if log else None
+        opts = VinaOpts(int(max_iters), float(grad_tol), float(margin))
+        so = VinaSearchOpts(nc, ns, int(o["step_iters"]), float(o["temperature"]), float(o["amplitude"]), float(o["autobox_add"]),
+                            int(bool(o["random_start"])), int(o["seed"]) & 0xFFFFFFFFFFFFFFFF)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        L.check(lib.dbfr_vina_search(C.byref(self.c), C.byref(opts), C.byref(so), streams.data_ptr(), best.data_ptr(), ptr(cur),
+                                     terms.data_ptr(), iters.data_ptr(), acc.data_ptr(), ptr(lg), ws.data_ptr(), ws.numel(), self._stream()))
+        # the best chain per pose: lowest objective (a refused pose's NaN counts as +inf), ties to the lowest chain
+        obj = terms[:, :, 6]
+        obj = torch.where(torch.isnan(obj), torch.full_like(obj, float("inf")), obj)
+        idx = torch.arange(nc, device=dev)[:, None].expand(nc, G)
+        pick = torch.where(obj == obj.min(0).values[None], idx, torch.full_like(idx, nc)).min(0).values.clamp(max=nc - 1)
+        lp = pb.lig_ptr_host.long()
+        graph = torch.repeat_interleave(torch.arange(G), lp[1:] - lp[:-1]).to(dev)
+        ar = torch.arange(G, device=dev)
+        return dict(pos=best[pick[graph], torch.arange(NL, device=dev)], terms=terms[pick, ar], best_chain=pick, chain_pos=best,
+                    chain_terms=terms, iters=iters, accepted=acc, log=None if lg is None else lg[:, :, :ns], cur_pos=cur)
+
+
 def score_poses(pb, lig_types, pairs, ext=None, rec_types=None):
     """Vina terms and generalised gradients of every pose of a sampled PackedBatch (see VinaBatch for the inputs)."""
     return VinaBatch(pb, lig_types, pairs, ext, rec_types).score()
@@ -408,6 +462,11 @@ def score_poses(pb, lig_types, pairs, ext=None, rec_types=None):
 def minimize_poses(pb, lig_types, pairs, ext=None, rec_types=None, **opts):
     """BFGS refinement of every pose of a sampled PackedBatch: (lig_pos [NL,3], terms [G,8], iters [G])."""
     return VinaBatch(pb, lig_types, pairs, ext, rec_types).minimize(**opts)
+
+
+def search_poses(pb, lig_types, pairs, streams=None, ext=None, rec_types=None, **opts):
+    """Monte-Carlo search from every pose of a sampled PackedBatch: the dict of ``VinaBatch.search``."""
+    return VinaBatch(pb, lig_types, pairs, ext, rec_types).search(streams=streams, **opts)
 
 
 class PoseBatch:
@@ -515,6 +574,32 @@ def refine_entry(e, lig_types=None, max_iters=100, grad_tol=1e-3, hetero=None, w
     vb, center, P, N = _entry_batch(e, lig_types, hetero, waters)
     pos, terms, iters = vb.minimize(max_iters=max_iters, grad_tol=grad_tol)
     return (pos.reshape(P, N, 3) + center), terms, iters
+
+
+def search_entry(e, exhaustiveness=8, n_steps=64, seed=0, hetero=None, waters=True, lig_types=None, streams=None, max_iters=100,
+                 grad_tol=1e-3, minimized=False, mode_opts=None, **search_opts):
+    """Monte-Carlo search (``VinaBatch.search``; ``exhaustiveness`` chains of ``n_steps`` steps) from the final frame of every pose
+    of one ``export.ComplexOutput``, against the receptor of ``refine_entry``: classical rigid-receptor docking into each sampled
+    pocket, in the box of the sampled pose.  ``streams``: int64 [P], default the pose numbers.  Returns a dict: ``lig`` [P, N, 3]
+    absolute and ``terms`` [P, 8]: the best chain per pose; ``chain_lig`` [chains, P, N, 3], ``chain_terms`` [chains, P, 8], ``iters``,
+    ``accepted`` [chains, P]: every chain's optimum; ``modes``: the complex's distinct binding modes over all P x chains optima
+    (optimum k = chain * P + pose, ranked by objective; ``modes.rmsd_matrix`` / ``modes.select_modes`` with ``mode_opts``) as a dict
+    ``rank``, ``id`` [chains * P] and ``cluster_size``, ``rmsd`` [chains * P, chains * P].  ``minimized``: also ``min_lig`` /
+    ``min_terms``, the poses of ``refine_entry`` (the start of every chain 0)."""
+    from . import modes
+    vb, center, P, N = _entry_batch(e, lig_types, hetero, waters)
+    r = vb.search(streams=streams, max_iters=max_iters, grad_tol=grad_tol, chains=exhaustiveness, n_steps=n_steps, seed=seed, **search_opts)
+    nc = int(exhaustiveness)
+    chain_lig = r["chain_pos"].reshape(nc, P, N, 3) + center
+    out = dict(lig=r["pos"].reshape(P, N, 3) + center, terms=r["terms"], best_chain=r["best_chain"], chain_lig=chain_lig,
+               chain_terms=r["chain_terms"], iters=r["iters"], accepted=r["accepted"])
+    R = modes.rmsd_matrix([chain_lig.reshape(nc * P, N, 3)], [modes._entry_perms(e)], [e.heavy_mask])
+    rank, mid, size = modes.select_modes(R, [r["chain_terms"][:, :, 6].reshape(-1)], **{**modes.DEFAULTS, **(mode_opts or {})})
+    out["modes"] = dict(rank=rank[0], id=mid[0], cluster_size=size[0], rmsd=R[0])
+    if minimized:
+        pos, terms, _ = vb.minimize(max_iters=max_iters, grad_tol=grad_tol)
+        out["min_lig"], out["min_terms"] = pos.reshape(P, N, 3) + center, terms
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ flexible side chains
@@ -746,7 +831,7 @@ def refined_entry(e, lig, atom14):
 
 
 def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_dist=None, max_flex_res=12, refined=None, hetero=None,
-                  waters=True):
+                  waters=True, exhaustiveness=None, search_steps=64, search_seed=0):
     """The error-correction step of the reference's predict.py (:160-170, smina per pose there) over the ``export.ComplexOutput``
     entries and the frame ``export.complex_modeling`` returned for them (rows in entry order, ``n_pose`` per entry, with a
     ``docked_lig`` column): every pose's final frame is minimised on the device (``refine_entry``), written next to its
@@ -762,7 +847,16 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
 
     ``hetero`` (None = protein atoms only, unchanged): one ``hetero.HeteroRecord`` or None per entry, in the form ``hetero.annotate``
     takes; its atoms are scored (``hetero_types``; waters only with ``waters``) and the frame gains ``ec_het_atoms``, the number of
-    scored hetero atoms of the pose's entry."""
+    scored hetero atoms of the pose's entry.
+
+    ``exhaustiveness`` (None = the minimisation above, unchanged; an int = the reference wrapper's ``smina_min(exhaustiveness=)``): every
+    pose is searched instead (``search_entry``: that many chains of ``search_steps`` Monte-Carlo steps, key ``search_seed``, the
+    pose's stream = its row number in the frame); ``lig_final_ec.sdf`` and ``smina_score`` are then the searched pose's, and the frame
+    gains ``SEARCH_COLUMNS``: ``ec_search_gain`` (the minimised pose's objective - the searched pose's, kcal/mol, >= 0),
+    ``ec_search_rmsd`` (A between the two poses) and ``ec_search_accepted`` (accepted Monte-Carlo steps over the pose's chains).
+    Search with flexible side chains is not built: together with ``flex_dist`` it raises ``DbfrError``."""
+    if exhaustiveness is not None and flex_dist is not None:
+        raise DbfrError("error_correct: exhaustiveness= with flex_dist= (a search with flexible side chains) is not built")
     df = pd_df.copy()
     if hetero is not None and len(hetero) != len(entries):
         raise DbfrError(f"{len(hetero)} hetero records for {len(entries)} entries")
@@ -779,13 +873,22 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
             raise DbfrError("error_correct(flex_dist=): protein_pdb must name the prot_final.pdb / pkt_final.pdb complex_modeling wrote")
     scores, paths, row = [], [], 0
     prot_paths, extra = [], {k: [] for k in FLEX_COLUMNS}
+    found = {k: [] for k in SEARCH_COLUMNS}
     import os
     het_atoms = []
     for k, e in enumerate(entries):
         if e.sdf_template is None:
             raise DbfrError(f"{e.name}: error_correct writes SD files from the entry's sdf_template")
         het = {} if hetero is None else dict(hetero=hetero[k], waters=waters)
-        if flex_dist is None:
+        if exhaustiveness is not None:
+            P = int(e.ligand_traj.shape[0])
+            r = search_entry(e, exhaustiveness=int(exhaustiveness), n_steps=int(search_steps), seed=int(search_seed), max_iters=max_iters,
+                             grad_tol=grad_tol, streams=torch.arange(row, row + P), minimized=True, **het)
+            pos, terms = r["lig"], r["terms"]
+            found["ec_search_gain"].extend((r["min_terms"][:, 6] - terms[:, 6]).cpu().tolist())
+            found["ec_search_rmsd"].extend(((pos - r["min_lig"]) ** 2).sum(-1).mean(-1).sqrt().cpu().tolist())
+            found["ec_search_accepted"].extend(r["accepted"].sum(0).cpu().tolist())
+        elif flex_dist is None:
             pos, terms, _ = refine_entry(e, max_iters=max_iters, grad_tol=grad_tol, **het)
         else:
             from .interactions import residue_tags
@@ -826,6 +929,9 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
     df["docked_lig"] = paths
     if hetero is not None:
         df["ec_het_atoms"] = het_atoms
+    if exhaustiveness is not None:
+        for k in SEARCH_COLUMNS:
+            df[k] = found[k]
     if flex_dist is not None:
         df["protein_pdb"] = prot_paths
         for k in FLEX_COLUMNS:

@@ -49,7 +49,9 @@ extern "C" {
                                    dbfr_holo_metrics, dbfr_hetero_check_in, dbfr_hetero_check_opts, dbfr_hetero_check_out,
                                    dbfr_hetero_check, dbfr_hydrogens_in, dbfr_hydrogens_opts, dbfr_hydrogens_out, dbfr_hydrogens,
                                    dbfr_vina_decompose_in, dbfr_vina_decompose_opts, dbfr_vina_decompose_out, dbfr_vina_decompose; XS type code 17 (Met_D) in dbfr_vina_in;
-                                8: + dbfr_test_time_embed, dbfr_test_mlp, dbfr_test_atom_encoder, dbfr_test_reduce_ln_layer, dbfr_test_center_edges, dbfr_test_trrot, dbfr_test_bond_attr, dbfr_test_tor_final (additions only) */
+                                8: + dbfr_test_time_embed, dbfr_test_mlp, dbfr_test_atom_encoder, dbfr_test_reduce_ln_layer, dbfr_test_center_edges, dbfr_test_trrot, dbfr_test_bond_attr, dbfr_test_tor_final (additions only);
+                                   later additions under the same number: dbfr_vina_search_opts, dbfr_vina_search_workspace_bytes, dbfr_vina_search,
+                                   dbfr_test_philox4x32, dbfr_test_vina_mutation */
 
 typedef enum {
   DBFR_OK = 0,
@@ -508,6 +510,44 @@ int dbfr_vina_score_at(const dbfr_vina_in* in, const float* q_rigid, const float
  * after max_iters steps, or when not even a steepest-descent step lowers the objective any more.  opts NULL = defaults.     */
 int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* terms, int32_t* iters,
                        void* workspace, size_t workspace_bytes, void* hip_stream);
+
+/* ---- Monte-Carlo search (docs/vina.md, "Monte-Carlo search"): Vina's iterated local search around dbfr_vina_minimize, on a rigid
+ * receptor.  One workgroup per (pose, chain).  A chain minimises its start (the input pose; with random_start and chain >= 1 a random
+ * placement in the box), then repeats n_steps times: mutate one entity of the current pose (translation, rotation or one torsion),
+ * minimise the candidate for at most step_iters BFGS steps from H = I, accept it by the Metropolis rule at `temperature` if every atom
+ * lies in the box (the input pose's bounding box grown by autobox_add on every side); the lowest accepted candidate is the best,
+ * and a best that came from a step is minimised once more with opts->max_iters (kept if it is not higher and still in the box).  Random numbers: Philox4x32-10, key = seed, counter =
+ * (stream low, stream high, chain, slot): a (pose, chain) result depends on its inputs, the seed, its stream and its chain only.   */
+typedef struct {
+  int32_t  chains;           /* chains per pose (smina's exhaustiveness), default 8; >= 1                                       */
+  int32_t  n_steps;          /* Monte-Carlo steps per chain, default 64; >= 0 (0 = dbfr_vina_minimize per chain)                */
+  int32_t  step_iters;       /* BFGS steps per candidate; < 0 = (25 + n_atoms) / 3 (Vina's), 0 = evaluate the mutated pose only */
+  float    temperature;      /* kcal/mol, default 1.2; > 0                                                                      */
+  float    amplitude;        /* A: radius of the translation ball; the rotation ball is amplitude / r_g rad; default 2         */
+  float    autobox_add;      /* A added to the input pose's bounding box on every side, default 4                               */
+  int32_t  random_start;     /* != 0: chains >= 1 start from a random placement; chain 0 always starts from the input pose      */
+  uint64_t seed;             /* the Philox key                                                                                  */
+} dbfr_vina_search_opts;
+
+/* Device workspace of dbfr_vina_search: chains x the workspace of dbfr_vina_workspace_bytes.  The checks of that call apply.     */
+int dbfr_vina_search_workspace_bytes(const dbfr_vina_in* in, int32_t chains, size_t* bytes);
+/* opts NULL = the defaults of dbfr_vina_minimize, search_opts NULL = the defaults above.  stream [G] int64 (device): the Philox
+ * stream of every pose.  best_pos [chains, NL, 3]: each chain's best pose; cur_pos [chains, NL, 3] (may be NULL): each chain's
+ * current pose after the last step; terms [chains, G, 8]: the terms of best_pos as dbfr_vina_score gives them; iters [chains, G]:
+ * BFGS steps over all minimisations of the chain; accepted [chains, G]: accepted Monte-Carlo steps; log (may be NULL)
+ * [chains, G, n_steps, 8] floats per step: {entity (0 translation, 1 rotation, 2 + k torsion k), E_c (the candidate's objective),
+ * in_box, the Metropolis u, accepted, E_cur after the step, E_best after the step, BFGS steps of the candidate}.  Energies are
+ * compared as the floats the log holds.  A graph dbfr_vina_minimize refuses gets NaN terms, iters = -1 and accepted = 0 in every
+ * chain and is not touched.  chains < 1, n_steps < 0 or temperature <= 0 (or not a number): DBFR_ERR_ARG.                         */
+int dbfr_vina_search(const dbfr_vina_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts, const int64_t* stream,
+                     float* best_pos, float* cur_pos, float* terms, int32_t* iters, int32_t* accepted, float* log, void* workspace,
+                     size_t workspace_bytes, void* hip_stream);
+/* Host test hooks of the search's random numbers (no device needed).  dbfr_test_philox4x32: one Philox4x32-10 block.
+ * dbfr_test_vina_mutation: the mutation of Monte-Carlo step `step` (1-based) of (seed, stream, chain) for a ligand of n_tor
+ * torsions: *entity and q [6 + n_tor] (translation, rotation vector, torsions; all but the chosen entity's entries 0).          */
+int dbfr_test_philox4x32(const uint32_t* ctr, const uint32_t* key, uint32_t* out);
+int dbfr_test_vina_mutation(uint64_t seed, int64_t stream, int32_t chain, int32_t step, int32_t n_tor, float amplitude, float r_g,
+                            int32_t* entity, float* q);
 
 /* ---- The same refinement with flexible pocket side chains (docs/vina.md, "Flexible side chains"; the same kernel code in a
  * second instantiation).  Receptor atoms of a pose are numbered pocket atoms first (0 .. na_g - 1: rec_pos under atm_ptr), then

@@ -29,6 +29,10 @@
 // (pose, chain).  vina_pose is split for it into vina_setup (the graph into LDS), vina_bfgs (the BFGS loop) and the outputs; the
 // search's LDS struct is the rigid one plus the best pose and the box.  Its random numbers are counter-based (Philox4x32-10), and
 // the generator and the mutation are __host__ __device__ so that the host tests them (dbfr_test_philox4x32, dbfr_test_vina_mutation).
+// k_vina_search is a template over the LDS struct as k_vina is: k_vina_search<V_MAX_TOR> is that rigid search, and
+// k_vina_search<V_FLEX_MAX_TOR> (dbfr_vina_flex_search; docs/vina.md, "Search with flexible side chains") runs the same stages over
+// the flexible minimiser's variables: the base of `rebuild` and the best pose cover all slots, a step may redraw a flexible torsion,
+// and two accumulators per flexible torsion keep the angles that re-basing would forget.
 #include "common.h"
 #include <algorithm>
 
@@ -841,41 +845,73 @@ struct VinaSearchArgs {
   int* accepted;           // [chains, G]
   float* log;              // [chains, G, n_steps, 8] or null
   size_t NL;
+  // flexible instantiation only
+  float *best_rec, *cur_rec;   // [chains, NA, 3] (cur_rec or null)
+  float* q_flex_out;       // [chains, NFT]
+  size_t NA, NFT;
 };
 
-struct VinaSearchShared : VinaShared<V_MAX_TOR> {
+// The search state behind the minimiser's struct.  Flexible: the best pose and the base cover all slots, and two accumulators carry
+// the total flexible torsion angles of the current (qc) and the best (qb) pose through the re-basing.
+template <bool F> struct VinaSearchFlexShared {};
+template <> struct VinaSearchFlexShared<true> {
+  float qc[V_FLEX_MAX_TOR], qb[V_FLEX_MAX_TOR];
+};
+template <int MT> struct VinaSearchShared : VinaShared<MT>, VinaSearchFlexShared<(MT > V_MAX_TOR)> {
   float xb[3][V_MAX_NL];   // the chain's best pose
-  double eb[6];            // and its terms
+  double eb[VinaShared<MT>::kFlex ? 8 : 6];   // and its terms
   float lo[3], hi[3];      // the box
   float rg;                // radius of gyration of the input pose
   int ent;                 // the step's entity
 };
-static_assert(sizeof(VinaSearchShared) <= (160 * 1024) / 3, "three search workgroups per CU");
+static_assert(sizeof(VinaSearchShared<V_MAX_TOR>) <= (160 * 1024) / 3, "three search workgroups per CU");
+static_assert(sizeof(VinaSearchShared<V_FLEX_MAX_TOR>) <= 160 * 1024 - 64, "the flexible search must fit the gfx950 workgroup LDS limit");
 
-__device__ __forceinline__ float v_objective(const double* e) {
+template <bool F> __device__ __forceinline__ float v_objective(const double* e) {
   double inter = 0.0;
   for (int k = 0; k < 5; ++k) inter += e[k];
+  if constexpr (F) return (float)(inter + e[5] + e[6]);
   return (float)(inter + e[5]);
 }
 
-__global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearchArgs Q) {
-  __shared__ VinaSearchShared S;
+__device__ __forceinline__ float v_wrap_pi(float a) {   // into [-pi, pi); a value inside keeps its bits
+  while (a >= V_PI) a -= V_TWO_PI;
+  while (a < -V_PI) a += V_TWO_PI;
+  return a;
+}
+
+// The pocket atoms of slots `x` (S.x0 or S.xb) into out [NA, 3] of this chain: fixed ones copied, flexible ones from their slots.
+template <class SH> __device__ __forceinline__ void search_rec_out(const VinaArgs& A, SH& S, const float (*x)[V_MAX_NL], float* out,
+                                                                 int g, const VinaDims& D) {
+  const size_t a0 = (size_t)A.b.atm_ptr[g];
+  for (int c = threadIdx.x; c < D.na; c += V_THREADS)
+    if (!((S.fm[c >> 5] >> (c & 31)) & 1u))
+      for (int k = 0; k < 3; ++k) out[3 * (a0 + c) + k] = A.b.rec_pos[3 * (a0 + c) + k];
+  for (int r = threadIdx.x; r < D.nf; r += V_THREADS)
+    for (int k = 0; k < 3; ++k) out[3 * (a0 + S.fa[r]) + k] = x[k][D.nl + r];
+}
+
+template <class SH> __device__ __forceinline__ void vina_search_chain(VinaArgs A, const VinaSearchArgs& Q, SH& S) {
+  constexpr bool F = SH::kFlex;
+  constexpr int NT = F ? 10 : 8, NE = F ? 7 : 6;
   const int tid = threadIdx.x;
   const int g = blockIdx.x % Q.G, chain = blockIdx.x / Q.G;
   const size_t blk = blockIdx.x;
   // this chain's slices of the workspace and of the per-pose outputs: the device functions index them by g
   A.cand += (size_t)chain * Q.G * A.cap;
-  A.terms += 8 * (size_t)chain * Q.G;
+  A.terms += NT * (size_t)chain * Q.G;
   A.iters += (size_t)chain * Q.G;
   VinaDims D;
   if (!vina_setup(A, S, g, D)) {   // NaN terms, iters = -1, nothing touched
-    refuse_pose<8>(A, g);
+    refuse_pose<NT>(A, g);
     if (tid == 0) Q.accepted[blk] = 0;
     return;
   }
   const int l0 = D.l0, nl = D.nl, nt = D.nt, n = D.n;
+  const int nb = F ? D.ns : nl;        // the slots of the base and of the best pose
+  const int ntl = D.ntl, nft = nt - ntl;
   const VinaRng rng = vina_rng(Q.seed, Q.stream[g], chain);
-  // the box and the radius of gyration of the input pose
+  // the box and the radius of gyration of the input pose (the ligand's atoms)
   if (tid < 3) {
     float lo = S.x0[tid][0], hi = lo, s = 0.f;
     for (int i = 0; i < nl; ++i) { const float v = S.x0[tid][i]; lo = fminf(lo, v); hi = fmaxf(hi, v); s += v; }
@@ -892,19 +928,20 @@ __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearc
     S.flag = 1;   // collect the candidates at the first evaluation
   }
   __syncthreads();
-  const int step_iters = Q.step_iters < 0 ? (25 + nl) / 3 : Q.step_iters;
+  const int step_iters = Q.step_iters < 0 ? (25 + nl + D.nf) / 3 : Q.step_iters;
   // stage -1: a random placement (evaluated, not minimised); 0: the start minimisation; 1 .. n_steps: the Monte-Carlo steps;
   // n_steps + 1: the final refinement of a best that came from a step.  (One call site of vina_bfgs, as in vina_pose.)
   int stage = (Q.random_start && chain >= 1) ? -1 : 0;
   int total = 0, nacc = 0;
   bool best_from_step = false;
   float e_cur = 0.f, e_best = 0.f;
+  double rec_start = 0.0;
   for (;;) {
-    for (int k = tid; k < VinaSearchShared::kMaxVar; k += V_THREADS) { S.p[k] = 0.f; S.pn[k] = 0.f; }
+    for (int k = tid; k < SH::kMaxVar; k += V_THREADS) { S.p[k] = 0.f; S.pn[k] = 0.f; }
     for (int i = tid; i < n * n; i += V_THREADS) S.H[i] = (i / n == i % n) ? 1.f : 0.f;
     __syncthreads();
     if (tid == 0) {
-      if (stage == -1) vina_random_start(rng, nt, S.pn);
+      if (stage == -1) vina_random_start(rng, ntl, S.pn);   // the ligand only: flexible torsions start as sampled
       else if (stage >= 1 && stage <= Q.n_steps) S.ent = vina_mutation(rng, stage, nt, Q.amplitude, S.rg, S.pn);
     }
     __syncthreads();
@@ -912,7 +949,7 @@ __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearc
     const int it = vina_bfgs(A, S, g, D, stage == -1 ? 0 : (stage >= 1 && stage <= Q.n_steps) ? step_iters : A.max_iters, rec0);
     total += it;
     __syncthreads();
-    const float e_c = v_objective(S.e);
+    const float e_c = v_objective<F>(S.e);
     bool in_box = true;
     if (stage == -1) {
       // the rotation was about the centroid S.c of the turned ligand, which is therefore still the centroid: move it to its draw
@@ -923,9 +960,13 @@ __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearc
       for (int i = tid; i < nl; i += V_THREADS)
         for (int c = 0; c < 3; ++c) S.x0[c][i] = S.x[c][i] + sh[c];
     } else if (stage == 0) {
-      for (int i = tid; i < nl; i += V_THREADS)
+      for (int i = tid; i < nb; i += V_THREADS)
         for (int c = 0; c < 3; ++c) S.x0[c][i] = S.xb[c][i] = S.x[c][i];
-      if (tid < 6) S.eb[tid] = S.e[tid];
+      if (tid < NE) S.eb[tid] = S.e[tid];
+      if constexpr (F) {
+        if (tid < nft) S.qc[tid] = S.qb[tid] = v_wrap_pi(S.p[6 + ntl + tid]);
+        rec_start = rec0;
+      }
       e_cur = e_best = e_c;
     } else {
       int out = 0;
@@ -939,13 +980,19 @@ __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearc
       const bool accept = in_box && (e_c < e_cur || u < expf((e_cur - e_c) / Q.temperature));
       if (accept) {
         const bool better = e_c < e_best;
-        for (int i = tid; i < nl; i += V_THREADS)
+        for (int i = tid; i < nb; i += V_THREADS)
           for (int c = 0; c < 3; ++c) {
             S.x0[c][i] = S.x[c][i];
             if (better) S.xb[c][i] = S.x[c][i];
           }
+        if constexpr (F)
+          if (tid < nft) {
+            const float a = v_wrap_pi(S.qc[tid] + S.p[6 + ntl + tid]);
+            S.qc[tid] = a;
+            if (better) S.qb[tid] = a;
+          }
         if (better) {
-          if (tid < 6) S.eb[tid] = S.e[tid];
+          if (tid < NE) S.eb[tid] = S.e[tid];
           e_best = e_c;
           best_from_step = true;
         }
@@ -959,9 +1006,11 @@ __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearc
       }
     } else if (stage > Q.n_steps) {   // the refined best, kept if it is not higher and has not left the box
       if (in_box && e_c <= e_best) {
-        for (int i = tid; i < nl; i += V_THREADS)
+        for (int i = tid; i < nb; i += V_THREADS)
           for (int c = 0; c < 3; ++c) S.xb[c][i] = S.x[c][i];
-        if (tid < 6) S.eb[tid] = S.e[tid];
+        if (tid < NE) S.eb[tid] = S.e[tid];
+        if constexpr (F)
+          if (tid < nft) S.qb[tid] = v_wrap_pi(S.qb[tid] + S.p[6 + ntl + tid]);
       }
     }
     __syncthreads();
@@ -970,26 +1019,44 @@ __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearc
       if (Q.cur_pos)
         for (int i = tid; i < nl; i += V_THREADS)
           for (int c = 0; c < 3; ++c) Q.cur_pos[3 * (Q.NL * chain + l0 + i) + c] = S.x0[c][i];
+      if constexpr (F)
+        if (Q.cur_rec) search_rec_out(A, S, S.x0, Q.cur_rec + 3 * Q.NA * chain, g, D);
       if (!best_from_step) break;
       __syncthreads();
-      for (int i = tid; i < nl; i += V_THREADS)
+      for (int i = tid; i < nb; i += V_THREADS)
         for (int c = 0; c < 3; ++c) S.x0[c][i] = S.xb[c][i];
     }
     ++stage;
   }
   __syncthreads();
   if (tid == 0) {
-    float* t = A.terms + 8 * (size_t)g;
+    float* t = A.terms + NT * (size_t)g;
     double inter = 0.0;
     for (int k = 0; k < 5; ++k) { t[k] = (float)S.eb[k]; inter += S.eb[k]; }
     t[5] = (float)S.eb[5];
     t[6] = (float)(inter + S.eb[5]);
     t[7] = (float)(inter / (1.0 + (double)W_NROT * D.ntl));
+    if constexpr (F) { t[6] = (float)(inter + S.eb[5] + S.eb[6]); t[8] = (float)S.eb[6]; t[9] = (float)rec_start; }
     A.iters[g] = total;
     Q.accepted[blk] = nacc;
   }
   for (int i = tid; i < nl; i += V_THREADS)
     for (int c = 0; c < 3; ++c) Q.best_pos[3 * (Q.NL * chain + l0 + i) + c] = S.xb[c][i];
+  if constexpr (F) {
+    search_rec_out(A, S, S.xb, Q.best_rec + 3 * Q.NA * chain, g, D);
+    if (tid < nft) Q.q_flex_out[Q.NFT * chain + A.ft_ptr[g] + tid] = S.qb[tid];
+  }
+}
+
+template <int MT> __global__ __launch_bounds__(V_THREADS) void k_vina_search(VinaArgs A, VinaSearchArgs Q) {
+  using SH = VinaSearchShared<MT>;
+  if constexpr (SH::kFlex) {   // dynamic LDS, as k_vina<flex>
+    extern __shared__ __align__(16) unsigned char v_lds[];
+    vina_search_chain(A, Q, *reinterpret_cast<SH*>(v_lds));
+  } else {
+    __shared__ SH S;
+    vina_search_chain(A, Q, S);
+  }
 }
 
 extern "C" int dbfr_test_philox4x32(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
@@ -1199,9 +1266,10 @@ extern "C" int dbfr_vina_minimize(const dbfr_vina_in* in, const dbfr_vina_opts* 
   return vina_launch(in, 1, opts, nullptr, nullptr, lig_pos_out, terms, nullptr, nullptr, iters, workspace, workspace_bytes, hip_stream);
 }
 
-static int vina_search_check(const dbfr_vina_in* in, int64_t chains, size_t* cap) {
-  const int rc = vina_check(in, cap);
+static int vina_search_check(const dbfr_vina_in* in, int64_t chains, size_t* cap, const dbfr_vina_flex_in* flex = nullptr) {
+  const int rc = flex ? vina_flex_check(flex, cap) : vina_check(in, cap);
   if (rc) return rc;
+  if (flex) in = flex->base;
   if (chains < 1) { dbfr_set_error("dbfr_vina_search: chains >= 1 required"); return DBFR_ERR_ARG; }
   if ((int64_t)in->batch->G * chains > 0x7fffffff) {
     dbfr_set_error("dbfr_vina_search: " + std::to_string(in->batch->G) + " poses x " + std::to_string(chains) + " chains exceed the grid of 2^31 - 1 workgroups");
@@ -1219,27 +1287,36 @@ extern "C" int dbfr_vina_search_workspace_bytes(const dbfr_vina_in* in, int32_t 
   return DBFR_OK;
 }
 
-extern "C" int dbfr_vina_search(const dbfr_vina_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts,
-                                const int64_t* stream, float* best_pos, float* cur_pos, float* terms, int32_t* iters, int32_t* accepted,
-                                float* log, void* workspace, size_t workspace_bytes, void* hip_stream) {
+struct VinaSearchFlexOut { float *best_rec, *q_flex_out, *cur_rec; };
+
+// dbfr_vina_search and dbfr_vina_flex_search: the checks in one order, then the rigid or the flexible instantiation.
+static int vina_search_launch(const char* name, const dbfr_vina_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts,
+                              const int64_t* stream, float* best_pos, float* cur_pos, float* terms, int32_t* iters, int32_t* accepted,
+                              float* log, void* workspace, size_t workspace_bytes, void* hip_stream,
+                              const dbfr_vina_flex_in* flex = nullptr, const VinaSearchFlexOut* fo = nullptr) {
+  const std::string who = name;
   dbfr_vina_search_opts so = {8, 64, -1, 1.2f, 2.f, 4.f, 0, 0};
   if (search_opts) so = *search_opts;
   size_t cap;
-  int rc = vina_search_check(in, so.chains, &cap);
+  int rc = vina_search_check(in, so.chains, &cap, flex);
   if (rc) return rc;
   if (so.n_steps < 0 || !(so.temperature > 0.f) || !(so.amplitude >= 0.f) || !(so.autobox_add >= 0.f)) {
-    dbfr_set_error("dbfr_vina_search: n_steps >= 0, temperature > 0, amplitude >= 0 and autobox_add >= 0 required");
+    dbfr_set_error(who + ": n_steps >= 0, temperature > 0, amplitude >= 0 and autobox_add >= 0 required");
     return DBFR_ERR_ARG;
   }
   if (!stream || !best_pos || !terms || !iters || !accepted) {
-    dbfr_set_error("dbfr_vina_search: stream, best_pos, terms, iters and accepted are required");
+    dbfr_set_error(who + ": stream, best_pos, terms, iters and accepted are required");
+    return DBFR_ERR_ARG;
+  }
+  if (flex && (!fo->best_rec || (flex->n_ftor > 0 && !fo->q_flex_out))) {
+    dbfr_set_error(who + ": best_rec and q_flex_out are required");
     return DBFR_ERR_ARG;
   }
   const dbfr_batch* B = in->batch;
   const size_t need = (size_t)so.chains * B->G * cap * sizeof(float4);
   if (!workspace || workspace_bytes < need) {
-    dbfr_set_error("dbfr_vina_search: workspace of " + std::to_string(workspace_bytes) + " bytes, this batch needs " + std::to_string(need) +
-                   " (dbfr_vina_search_workspace_bytes)");
+    dbfr_set_error(who + ": workspace of " + std::to_string(workspace_bytes) + " bytes, this batch needs " + std::to_string(need) +
+                   " (" + who + "_workspace_bytes)");
     return DBFR_ERR_ARG;
   }
   VinaArgs A;
@@ -1247,11 +1324,53 @@ extern "C" int dbfr_vina_search(const dbfr_vina_in* in, const dbfr_vina_opts* op
   if (rc) return rc;
   A.minimize = 1;
   A.terms = terms; A.iters = iters;
-  const VinaSearchArgs Q = {B->G, so.chains, so.n_steps, so.step_iters, so.random_start, so.temperature, so.amplitude, so.autobox_add,
-                            so.seed, stream, best_pos, cur_pos, accepted, log, (size_t)B->NL};
-  hipLaunchKernelGGL(k_vina_search, dim3((unsigned)(B->G * so.chains)), dim3(V_THREADS), 0, (hipStream_t)hip_stream, A, Q);
+  VinaSearchArgs Q = {B->G, so.chains, so.n_steps, so.step_iters, so.random_start, so.temperature, so.amplitude, so.autobox_add,
+                      so.seed, stream, best_pos, cur_pos, accepted, log, (size_t)B->NL, nullptr, nullptr, nullptr, 0, 0};
+  const dim3 grid((unsigned)(B->G * so.chains));
+  if (flex) {
+    A.f_ptr = flex->flex_ptr; A.f_atom = flex->flex_atom; A.ft_ptr = flex->ftor_ptr; A.ft_bc = flex->ftor_bc;
+    A.turn_ptr = flex->turn_ptr; A.turn = flex->turn; A.excl_ptr = flex->excl_ptr; A.excl = flex->excl;
+    Q.best_rec = fo->best_rec; Q.cur_rec = fo->cur_rec; Q.q_flex_out = fo->q_flex_out;
+    Q.NA = (size_t)B->NA; Q.NFT = (size_t)flex->n_ftor;
+    // (the LDS attribute is set on every launch: it is per device, and a process may drive several)
+    const size_t lds = sizeof(VinaSearchShared<V_FLEX_MAX_TOR>);
+    if (dbfr_launch_check(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_vina_search<V_FLEX_MAX_TOR>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+                          "k_vina_search<flex>: hipFuncSetAttribute(MaxDynamicSharedMemorySize)"))
+      return dbfr_take_launch_error();
+    hipLaunchKernelGGL(k_vina_search<V_FLEX_MAX_TOR>, grid, dim3(V_THREADS), lds, (hipStream_t)hip_stream, A, Q);
+  } else {
+    hipLaunchKernelGGL(k_vina_search<V_MAX_TOR>, grid, dim3(V_THREADS), 0, (hipStream_t)hip_stream, A, Q);
+  }
   HIPCHECK(hipGetLastError());
   return DBFR_OK;
+}
+
+extern "C" int dbfr_vina_search(const dbfr_vina_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts,
+                                const int64_t* stream, float* best_pos, float* cur_pos, float* terms, int32_t* iters, int32_t* accepted,
+                                float* log, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return vina_search_launch("dbfr_vina_search", in, opts, search_opts, stream, best_pos, cur_pos, terms, iters, accepted, log, workspace,
+                            workspace_bytes, hip_stream);
+}
+
+extern "C" int dbfr_vina_flex_search_workspace_bytes(const dbfr_vina_flex_in* in, int32_t chains, size_t* bytes) {
+  if (!in || !in->base) { dbfr_set_error("dbfr_vina_flex: null argument"); return DBFR_ERR_ARG; }
+  size_t cap;
+  const int rc = vina_search_check(in->base, chains, &cap, in);
+  if (rc) return rc;
+  if (!bytes) { dbfr_set_error("dbfr_vina_flex_search_workspace_bytes: null argument"); return DBFR_ERR_ARG; }
+  *bytes = (size_t)chains * in->base->batch->G * cap * sizeof(float4);
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_vina_flex_search(const dbfr_vina_flex_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts,
+                                     const int64_t* stream, float* best_pos, float* best_rec, float* q_flex_out, float* cur_pos,
+                                     float* cur_rec, float* terms, int32_t* iters, int32_t* accepted, float* log, void* workspace,
+                                     size_t workspace_bytes, void* hip_stream) {
+  if (!in || !in->base) { dbfr_set_error("dbfr_vina_flex: null argument"); return DBFR_ERR_ARG; }
+  const VinaSearchFlexOut fo = {best_rec, q_flex_out, cur_rec};
+  return vina_search_launch("dbfr_vina_flex_search", in->base, opts, search_opts, stream, best_pos, cur_pos, terms, iters, accepted, log,
+                            workspace, workspace_bytes, hip_stream, in, &fo);
 }
 
 extern "C" int dbfr_vina_flex_workspace_bytes(const dbfr_vina_flex_in* in, size_t* bytes) {

@@ -310,6 +310,7 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
            "dbfr_vina_flex_workspace_bytes", "dbfr_vina_flex_score_at", "dbfr_vina_flex_minimize",
            "dbfr_vina_search_workspace_bytes", "dbfr_vina_search", "dbfr_test_philox4x32", "dbfr_test_vina_mutation",
+           "dbfr_vina_flex_search_workspace_bytes", "dbfr_vina_flex_search",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
@@ -405,6 +406,9 @@ def load():
     lib.dbfr_vina_search_workspace_bytes.argtypes = [C.POINTER(VinaIn), i32, C.POINTER(C.c_size_t)]
     lib.dbfr_vina_search.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), C.POINTER(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp, vp,
                                      C.c_size_t, vp]
+    lib.dbfr_vina_flex_search_workspace_bytes.argtypes = [C.POINTER(VinaFlexIn), i32, C.POINTER(C.c_size_t)]
+    lib.dbfr_vina_flex_search.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(VinaOpts), C.POINTER(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, vp, C.c_size_t, vp]
     lib.dbfr_test_philox4x32.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     lib.dbfr_test_vina_mutation.argtypes = [C.c_uint64, C.c_int64, i32, i32, i32, C.c_float, C.c_float, C.POINTER(i32),
                                             C.POINTER(C.c_float)]

@@ -53,6 +53,10 @@ and its random numbers (Philox4x32-10, addressed by seed, the pose's stream, cha
 
 Flexible side chains (``flex_topology``, ``select_flexible``, ``VinaFlexBatch``, ``refine_entry_flex``, ``error_correct(flex_dist=)``):
 the pocket side chains near the ligand turn about their chi axes in the same minimisation; docs/vina.md states the model.
+
+Search with flexible side chains (``VinaFlexBatch.search``, ``search_entry_flex``, ``error_correct(exhaustiveness=,
+search_flex_dist=)``): the Monte-Carlo search over the flexible minimiser's variables -- a step may also redraw one chi angle, the
+Metropolis energy includes E_rec, the ligand alone is held in the box; docs/vina.md, "Search with flexible side chains".
 """
 import ctypes as C
 import os
@@ -415,17 +419,9 @@ class VinaBatch:
         ``chain_pos`` [chains,NL,3], ``chain_terms`` [chains,G,8], ``iters`` and ``accepted`` [chains,G] (BFGS steps, accepted
         Monte-Carlo steps), ``log`` [chains,G,n_steps,8] (``SEARCH_LOG``; with ``log``) and ``cur_pos`` [chains,NL,3] (each chain's
         current pose after the last step; with ``current``)."""
-        unknown = set(search_opts) - set(SEARCH_DEFAULTS)
-        if unknown:
-            raise DbfrError(f"unknown search option(s) {sorted(unknown)}: {sorted(SEARCH_DEFAULTS)}")
-        o = {**SEARCH_DEFAULTS, **search_opts}
+        _, streams, so = _search_args(self.pb, streams, search_opts)
         pb, dev = self.pb, self.pb.lig_pos.device
-        G, NL, nc, ns = pb.G, pb.dims["NL"], int(o["chains"]), int(o["n_steps"])
-        if streams is None:
-            streams = torch.arange(G, dtype=torch.int64, device=dev)
-        streams = torch.as_tensor(streams).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
-        if streams.numel() != G:
-            raise DbfrError(f"{streams.numel()} streams for {G} poses")
+        G, NL, nc, ns = pb.G, pb.dims["NL"], so.chains, so.n_steps
         lib = L.load()
         nb = C.c_size_t(0)
         L.check(lib.dbfr_vina_search_workspace_bytes(C.byref(self.c), nc, C.byref(nb)))
@@ -437,21 +433,42 @@ class VinaBatch:
         acc = torch.empty(nc, G, dtype=torch.int32, device=dev)
         lg = torch.empty(nc, G, max(ns, 1), 8, device=dev) if log else None
         opts = VinaOpts(int(max_iters), float(grad_tol), float(margin))
-        so = VinaSearchOpts(nc, ns, int(o["step_iters"]), float(o["temperature"]), float(o["amplitude"]), float(o["autobox_add"]),
-                            int(bool(o["random_start"])), int(o["seed"]) & 0xFFFFFFFFFFFFFFFF)
         ptr = lambda t: None if t is None else t.data_ptr()
         L.check(lib.dbfr_vina_search(C.byref(self.c), C.byref(opts), C.byref(so), streams.data_ptr(), best.data_ptr(), ptr(cur),
                                      terms.data_ptr(), iters.data_ptr(), acc.data_ptr(), ptr(lg), ws.data_ptr(), ws.numel(), self._stream()))
-        # the best chain per pose: lowest objective (a refused pose's NaN counts as +inf), ties to the lowest chain
-        obj = terms[:, :, 6]
-        obj = torch.where(torch.isnan(obj), torch.full_like(obj, float("inf")), obj)
-        idx = torch.arange(nc, device=dev)[:, None].expand(nc, G)
-        pick = torch.where(obj == obj.min(0).values[None], idx, torch.full_like(idx, nc)).min(0).values.clamp(max=nc - 1)
+        pick = _best_chain(terms)
         lp = pb.lig_ptr_host.long()
         graph = torch.repeat_interleave(torch.arange(G), lp[1:] - lp[:-1]).to(dev)
         ar = torch.arange(G, device=dev)
         return dict(pos=best[pick[graph], torch.arange(NL, device=dev)], terms=terms[pick, ar], best_chain=pick, chain_pos=best,
                     chain_terms=terms, iters=iters, accepted=acc, log=None if lg is None else lg[:, :, :ns], cur_pos=cur)
+
+
+def _search_args(pb, streams, search_opts):
+    """(options dict, streams int64 [G] on the device, VinaSearchOpts) of a ``search`` call."""
+    unknown = set(search_opts) - set(SEARCH_DEFAULTS)
+    if unknown:
+        raise DbfrError(f"unknown search option(s) {sorted(unknown)}: {sorted(SEARCH_DEFAULTS)}")
+    o = {**SEARCH_DEFAULTS, **search_opts}
+    G, dev = pb.G, pb.lig_pos.device
+    if streams is None:
+        streams = torch.arange(G, dtype=torch.int64, device=dev)
+    streams = torch.as_tensor(streams).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    if streams.numel() != G:
+        raise DbfrError(f"{streams.numel()} streams for {G} poses")
+    so = VinaSearchOpts(int(o["chains"]), int(o["n_steps"]), int(o["step_iters"]), float(o["temperature"]), float(o["amplitude"]),
+                        float(o["autobox_add"]), int(bool(o["random_start"])), int(o["seed"]) & 0xFFFFFFFFFFFFFFFF)
+    return o, streams, so
+
+
+def _best_chain(terms):
+    """The best chain per pose of terms [chains, G, >= 7]: lowest objective (a refused pose's NaN counts as +inf), ties to the lowest
+    chain."""
+    nc, G = terms.shape[0], terms.shape[1]
+    obj = terms[:, :, 6]
+    obj = torch.where(torch.isnan(obj), torch.full_like(obj, float("inf")), obj)
+    idx = torch.arange(nc, device=terms.device)[:, None].expand(nc, G)
+    return torch.where(obj == obj.min(0).values[None], idx, torch.full_like(idx, nc)).min(0).values.clamp(max=nc - 1)
 
 
 def score_poses(pb, lig_types, pairs, ext=None, rec_types=None):
@@ -686,6 +703,43 @@ class VinaFlexBatch:
         return pos, rec, qf[:self.n_ftor], terms, iters
 
 
+    def search(self, streams=None, max_iters=100, grad_tol=1e-3, margin=2.0, log=False, current=False, **search_opts):
+        """``VinaBatch.search`` over the ligand and the flexible side chains together (docs/vina.md, "Search with flexible side
+        chains").  Returns that method's dict with ``terms`` [G,10] / ``chain_terms`` [chains,G,10] (``FLEX_TERMS``) and, added,
+        ``rec`` [NA,3] and ``q_flex`` [n_ftor] of the best chain per pose, ``chain_rec`` [chains,NA,3], ``chain_q_flex``
+        [chains,n_ftor] and ``cur_rec`` [chains,NA,3] (with ``current``)."""
+        vb, pb, dev = self.vb, self.vb.pb, self.vb.pb.lig_pos.device
+        _, streams, so = _search_args(pb, streams, search_opts)
+        G, NL, NA, NF, nc, ns = pb.G, pb.dims["NL"], pb.dims["NA"], self.n_ftor, so.chains, so.n_steps
+        lib = L.load()
+        nb = C.c_size_t(0)
+        L.check(lib.dbfr_vina_flex_search_workspace_bytes(C.byref(self.c), nc, C.byref(nb)))
+        ws = torch.empty(max(int(nb.value), 16), dtype=torch.uint8, device=dev)
+        best, rec = torch.empty(nc, NL, 3, device=dev), torch.empty(nc, NA, 3, device=dev)
+        qf = torch.zeros(nc, max(NF, 1), device=dev)
+        cur = torch.empty(nc, NL, 3, device=dev) if current else None
+        cur_rec = torch.empty(nc, NA, 3, device=dev) if current else None
+        terms = torch.empty(nc, G, 10, device=dev)
+        iters = torch.empty(nc, G, dtype=torch.int32, device=dev)
+        acc = torch.empty(nc, G, dtype=torch.int32, device=dev)
+        lg = torch.empty(nc, G, max(ns, 1), 8, device=dev) if log else None
+        opts = VinaOpts(int(max_iters), float(grad_tol), float(margin))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        L.check(lib.dbfr_vina_flex_search(C.byref(self.c), C.byref(opts), C.byref(so), streams.data_ptr(), best.data_ptr(), rec.data_ptr(),
+                                          qf.data_ptr(), ptr(cur), ptr(cur_rec), terms.data_ptr(), iters.data_ptr(), acc.data_ptr(),
+                                          ptr(lg), ws.data_ptr(), ws.numel(), vb._stream()))
+        qf = qf[:, :NF]
+        pick = _best_chain(terms)
+        count = lambda p: torch.as_tensor(np.diff(np.asarray(p, np.int64)))
+        of = lambda p: torch.repeat_interleave(torch.arange(G), count(p)).to(dev)
+        lig_g, rec_g, tor_g = of(pb.lig_ptr_host), of(pb.t["atm_ptr"].cpu()), of(self.ftor_ptr)
+        ar = torch.arange(G, device=dev)
+        return dict(pos=best[pick[lig_g], torch.arange(NL, device=dev)], terms=terms[pick, ar], best_chain=pick, chain_pos=best,
+                    chain_terms=terms, iters=iters, accepted=acc, log=None if lg is None else lg[:, :, :ns], cur_pos=cur,
+                    rec=rec[pick[rec_g], torch.arange(NA, device=dev)], q_flex=qf[pick[tor_g], torch.arange(NF, device=dev)],
+                    chain_rec=rec, chain_q_flex=qf, cur_rec=cur_rec)
+
+
 def residue_flex_sets(aatype, mask14, topo):
     """The one place that turns residues into flexible sets.  aatype [R] and mask14 bool [R, 14] of the pocket residues, whose
     present atoms are the pocket atoms 0 .. M-1 of ``topo`` (a ``pocketcheck.receptor_topology``) in row-major order.  Returns
@@ -818,6 +872,46 @@ def refine_entry_flex(e, flex_dist=3.5, max_flex_res=12, max_iters=100, grad_tol
                 q_flex=[qf[int(fb.ftor_ptr[p]):int(fb.ftor_ptr[p + 1])] for p in range(P)], trimmed=trimmed)
 
 
+def search_entry_flex(e, flex_dist=3.5, max_flex_res=12, exhaustiveness=8, n_steps=64, seed=0, hetero=None, waters=True, lig_types=None,
+                      streams=None, max_iters=100, grad_tol=1e-3, minimized=False, mode_opts=None, **search_opts):
+    """``search_entry`` with the pocket side chains near the ligand flexible (``VinaFlexBatch.search``; the flexible set of every
+    pose is ``select_flexible`` on its input pose, as in ``refine_entry_flex``): classical flexible-receptor docking into each
+    sampled pocket.  Returns the keys of ``refine_entry_flex`` for the best chain per pose (``lig`` [P, N, 3] absolute, ``atom14``
+    [P, R, 14, 3] pocket-centred, ``terms`` [P, 10], ``flex_rows``, ``q_flex``, ``trimmed``) with ``best_chain`` [P]; every chain's
+    optimum as ``chain_lig`` [chains, P, N, 3], ``chain_atom14`` [chains, P, R, 14, 3], ``chain_terms`` [chains, P, 10], ``iters``,
+    ``accepted`` [chains, P]; and ``modes`` over all P x chains ligand optima as ``search_entry`` gives them.  ``minimized``: also
+    ``minimized``, the ``refine_entry_flex`` result of the same flexible sets (the start of every chain 0)."""
+    from . import modes
+    vb, center, P, N = _entry_batch(e, lig_types, hetero, waters)
+    topo = flex_topology(e)
+    a14 = e.protein_traj[:, -1]
+    rows, trimmed = select_flexible(e, e.ligand_traj[:, -1], a14, flex_dist, max_flex_res, topo)
+    rows = [np.sort(r) for r in rows]
+    fb = VinaFlexBatch(vb, _flex_sets(topo, rows))
+    nc = int(exhaustiveness)
+    r = fb.search(streams=streams, max_iters=max_iters, grad_tol=grad_tol, chains=nc, n_steps=n_steps, seed=seed, **search_opts)
+    m14 = torch.as_tensor(topo["mask14"], device=a14.device)
+    out14, chain14 = a14.to(torch.float32).clone(), a14.to(torch.float32)[None].repeat(nc, 1, 1, 1, 1)
+    out14[:, m14] = r["rec"].reshape(P, -1, 3)
+    chain14[:, :, m14] = r["chain_rec"].reshape(nc, P, -1, 3)
+    qf = r["q_flex"].cpu()
+    chain_lig = r["chain_pos"].reshape(nc, P, N, 3) + center
+    out = dict(lig=r["pos"].reshape(P, N, 3) + center, atom14=out14, terms=r["terms"], flex_rows=rows,
+               q_flex=[qf[int(fb.ftor_ptr[p]):int(fb.ftor_ptr[p + 1])] for p in range(P)], trimmed=trimmed, best_chain=r["best_chain"],
+               chain_lig=chain_lig, chain_atom14=chain14, chain_terms=r["chain_terms"], iters=r["iters"], accepted=r["accepted"])
+    R = modes.rmsd_matrix([chain_lig.reshape(nc * P, N, 3)], [modes._entry_perms(e)], [e.heavy_mask])
+    rank, mid, size = modes.select_modes(R, [r["chain_terms"][:, :, 6].reshape(-1)], **{**modes.DEFAULTS, **(mode_opts or {})})
+    out["modes"] = dict(rank=rank[0], id=mid[0], cluster_size=size[0], rmsd=R[0])
+    if minimized:
+        pos, rec, mq, terms, iters = fb.minimize(max_iters=max_iters, grad_tol=grad_tol)
+        min14 = a14.to(torch.float32).clone()
+        min14[:, m14] = rec.reshape(P, -1, 3)
+        mq = mq.cpu()
+        out["minimized"] = dict(lig=pos.reshape(P, N, 3) + center, atom14=min14, terms=terms, iters=iters, flex_rows=rows,
+                                q_flex=[mq[int(fb.ftor_ptr[p]):int(fb.ftor_ptr[p + 1])] for p in range(P)], trimmed=trimmed)
+    return out
+
+
 def refined_entry(e, lig, atom14):
     """A copy of the entry whose trajectories hold one frame, the refined one: lig [P, N, 3] absolute and atom14 [P, R, 14, 3]
     pocket-centred, as ``refine_entry_flex`` (or ``refine_entry``, with ``e.protein_traj[:, -1]``) returns them.  ``posecheck``,
@@ -831,7 +925,7 @@ def refined_entry(e, lig, atom14):
 
 
 def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_dist=None, max_flex_res=12, refined=None, hetero=None,
-                  waters=True, exhaustiveness=None, search_steps=64, search_seed=0):
+                  waters=True, exhaustiveness=None, search_steps=64, search_seed=0, search_flex_dist=None):
     """The error-correction step of the reference's predict.py (:160-170, smina per pose there) over the ``export.ComplexOutput``
     entries and the frame ``export.complex_modeling`` returned for them (rows in entry order, ``n_pose`` per entry, with a
     ``docked_lig`` column): every pose's final frame is minimised on the device (``refine_entry``), written next to its
@@ -854,9 +948,20 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
     pose's stream = its row number in the frame); ``lig_final_ec.sdf`` and ``smina_score`` are then the searched pose's, and the frame
     gains ``SEARCH_COLUMNS``: ``ec_search_gain`` (the minimised pose's objective - the searched pose's, kcal/mol, >= 0),
     ``ec_search_rmsd`` (A between the two poses) and ``ec_search_accepted`` (accepted Monte-Carlo steps over the pose's chains).
-    Search with flexible side chains is not built: together with ``flex_dist`` it raises ``DbfrError``."""
+    The search with flexible side chains is asked for with ``search_flex_dist``; together with ``flex_dist`` (the flexible
+    minimisation) ``exhaustiveness`` is not built as a combination and raises ``DbfrError``.
+
+    ``search_flex_dist`` (A; None = the rigid search above, unchanged; needs ``exhaustiveness``): the side chains within it of the input
+    pose move in the search too (``search_entry_flex``, at most ``max_flex_res`` residues).  ``lig_final_ec.sdf`` and ``smina_score``
+    are the searched pose's, the receptor files, ``protein_pdb`` and ``FLEX_COLUMNS`` are written as with ``flex_dist`` (for the
+    searched pocket), ``SEARCH_COLUMNS`` as with ``exhaustiveness``, with ``ec_search_gain`` = the flexible minimiser's objective -
+    the searched pose's; ``refined`` receives the searched poses."""
     if exhaustiveness is not None and flex_dist is not None:
-        raise DbfrError("error_correct: exhaustiveness= with flex_dist= (a search with flexible side chains) is not built")
+        raise DbfrError("error_correct: exhaustiveness= with flex_dist= (a search with flexible side chains) is not built under these "
+                        "keywords: pass exhaustiveness= with search_flex_dist= for the search with flexible side chains")
+    if search_flex_dist is not None and exhaustiveness is None:
+        raise DbfrError("error_correct: search_flex_dist= needs exhaustiveness= (it is the flexible set of the search)")
+    flex_out = flex_dist if search_flex_dist is None else search_flex_dist       # the receptor files and FLEX_COLUMNS are written
     df = pd_df.copy()
     if hetero is not None and len(hetero) != len(entries):
         raise DbfrError(f"{len(hetero)} hetero records for {len(entries)} entries")
@@ -865,7 +970,7 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
     n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
     if n_rows != len(df):
         raise DbfrError(f"{len(df)} frame rows for {n_rows} poses of the entries")
-    if flex_dist is not None:
+    if flex_out is not None:
         if "protein_pdb" not in df.columns:
             raise DbfrError("error_correct(flex_dist=) needs the frame's protein_pdb column")
         import os
@@ -882,18 +987,25 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
         het = {} if hetero is None else dict(hetero=hetero[k], waters=waters)
         if exhaustiveness is not None:
             P = int(e.ligand_traj.shape[0])
-            r = search_entry(e, exhaustiveness=int(exhaustiveness), n_steps=int(search_steps), seed=int(search_seed), max_iters=max_iters,
-                             grad_tol=grad_tol, streams=torch.arange(row, row + P), minimized=True, **het)
+            so = dict(exhaustiveness=int(exhaustiveness), n_steps=int(search_steps), seed=int(search_seed), max_iters=max_iters,
+                      grad_tol=grad_tol, streams=torch.arange(row, row + P), minimized=True, **het)
+            if search_flex_dist is None:
+                r = search_entry(e, **so)
+                min_lig, min_terms = r["min_lig"], r["min_terms"]
+            else:
+                r = search_entry_flex(e, flex_dist=search_flex_dist, max_flex_res=max_flex_res, **so)
+                min_lig, min_terms = r["minimized"]["lig"], r["minimized"]["terms"]
             pos, terms = r["lig"], r["terms"]
-            found["ec_search_gain"].extend((r["min_terms"][:, 6] - terms[:, 6]).cpu().tolist())
-            found["ec_search_rmsd"].extend(((pos - r["min_lig"]) ** 2).sum(-1).mean(-1).sqrt().cpu().tolist())
+            found["ec_search_gain"].extend((min_terms[:, 6] - terms[:, 6]).cpu().tolist())
+            found["ec_search_rmsd"].extend(((pos - min_lig) ** 2).sum(-1).mean(-1).sqrt().cpu().tolist())
             found["ec_search_accepted"].extend(r["accepted"].sum(0).cpu().tolist())
         elif flex_dist is None:
             pos, terms, _ = refine_entry(e, max_iters=max_iters, grad_tol=grad_tol, **het)
         else:
-            from .interactions import residue_tags
             r = refine_entry_flex(e, flex_dist=flex_dist, max_flex_res=max_flex_res, max_iters=max_iters, grad_tol=grad_tol, **het)
             pos, terms = r["lig"], r["terms"]
+        if flex_out is not None:
+            from .interactions import residue_tags
             P = pos.shape[0]
             center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3))
             final = r["atom14"].cpu() + center
@@ -929,11 +1041,11 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
     df["docked_lig"] = paths
     if hetero is not None:
         df["ec_het_atoms"] = het_atoms
-    if exhaustiveness is not None:
-        for k in SEARCH_COLUMNS:
-            df[k] = found[k]
-    if flex_dist is not None:
+    if flex_out is not None:
         df["protein_pdb"] = prot_paths
         for k in FLEX_COLUMNS:
             df[k] = extra[k]
+    if exhaustiveness is not None:
+        for k in SEARCH_COLUMNS:
+            df[k] = found[k]
     return df

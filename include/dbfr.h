@@ -51,7 +51,8 @@ extern "C" {
                                    dbfr_vina_decompose_in, dbfr_vina_decompose_opts, dbfr_vina_decompose_out, dbfr_vina_decompose; XS type code 17 (Met_D) in dbfr_vina_in;
                                 8: + dbfr_test_time_embed, dbfr_test_mlp, dbfr_test_atom_encoder, dbfr_test_reduce_ln_layer, dbfr_test_center_edges, dbfr_test_trrot, dbfr_test_bond_attr, dbfr_test_tor_final (additions only);
                                    later additions under the same number: dbfr_vina_search_opts, dbfr_vina_search_workspace_bytes, dbfr_vina_search,
-                                   dbfr_test_philox4x32, dbfr_test_vina_mutation */
+                                   dbfr_test_philox4x32, dbfr_test_vina_mutation,
+                                   dbfr_vina_flex_search_workspace_bytes, dbfr_vina_flex_search */
 
 typedef enum {
   DBFR_OK = 0,
@@ -595,6 +596,29 @@ int dbfr_vina_flex_score_at(const dbfr_vina_flex_in* in, const float* q_rigid, c
 int dbfr_vina_flex_minimize(const dbfr_vina_flex_in* in, const dbfr_vina_opts* opts, float* lig_pos_out, float* rec_pos_out,
                             float* q_flex_out, float* terms, int32_t* iters, void* workspace, size_t workspace_bytes,
                             void* hip_stream);
+
+/* ---- The Monte-Carlo search with flexible pocket side chains (docs/vina.md, "Search with flexible side chains"): the rule of
+ * dbfr_vina_search over the variables of dbfr_vina_flex_minimize, in a second instantiation of the same kernel.  A step draws its
+ * entity among 2 + ligand torsions + flexible torsions (dbfr_test_vina_mutation with n_tor = their sum): entity 2 + ntl + k sets
+ * flexible torsion k of the graph to a uniform angle in [-pi, pi).  The Metropolis energy is the flexible objective
+ * E_inter + E_intra + E_rec; the box test reads the ligand's atoms only; step_iters < 0 = (25 + ligand atoms + flexible atoms) / 3;
+ * with random_start the chains >= 1 re-place the ligand only (the draws of dbfr_vina_search) and keep the input side chains.
+ * With no flexible atom in any graph the results equal dbfr_vina_search's bit for bit.                                          */
+/* Device workspace of dbfr_vina_flex_search: chains x the workspace of dbfr_vina_flex_workspace_bytes; every check of the flexible
+ * calls runs.                                                                                                                */
+int dbfr_vina_flex_search_workspace_bytes(const dbfr_vina_flex_in* in, int32_t chains, size_t* bytes);
+/* opts, search_opts, stream, iters, accepted and log [chains, G, n_steps, 8] as in dbfr_vina_search.  best_pos [chains, NL, 3] and
+ * best_rec [chains, NA, 3]: each chain's best ligand pose and its pocket atoms (fixed atoms copied bit for bit); q_flex_out
+ * [chains, n_ftor]: the best pose's flexible torsion angles against the input, in [-pi, pi) (required when n_ftor > 0); cur_pos /
+ * cur_rec (either may be NULL): each chain's current pose after the last step; terms [chains, G, 10] as dbfr_vina_flex_score_at
+ * gives them for the best pose, terms[9] = E_rec at the first evaluation of the chain's start minimisation.  The refusals of
+ * dbfr_vina_search and of dbfr_vina_flex_minimize both apply before any launch (DBFR_ERR_ARG), the validation of the lists through
+ * `host` included.  A graph dbfr_vina_flex_minimize refuses gets NaN terms, iters = -1 and accepted = 0 in every chain and is not
+ * touched.                                                                                                                   */
+int dbfr_vina_flex_search(const dbfr_vina_flex_in* in, const dbfr_vina_opts* opts, const dbfr_vina_search_opts* search_opts,
+                          const int64_t* stream, float* best_pos, float* best_rec, float* q_flex_out, float* cur_pos, float* cur_rec,
+                          float* terms, int32_t* iters, int32_t* accepted, float* log, void* workspace, size_t workspace_bytes,
+                          void* hip_stream);
 
 /* ---- Distinct binding modes of sampled poses (csrc/modes.hip; docs/modes.md).  A batch of G groups (one group = the poses
  * of one ligand in one pocket frame), group g holding P_g poses of N_g atoms and n_perm_g automorphisms (identity included):

@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdbfr.so")
-SOURCES = ["api.cpp", "so3_host.cpp", "conv.hip", "conv2.hip", "conv2h.hip", "convz.hip", "graph.hip", "heads.hip", "export.hip", "mdn.hip", "probe.hip", "vina.hip", "modes.hip", "posecheck.hip", "xtc.hip", "sites.hip", "interactions.hip", "pocketcheck.hip", "sasa.hip", "apoholo.hip", "hetero.hip", "hydrogens.hip", "decompose.hip"]
+SOURCES = ["api.cpp", "pack.cpp", "so3_host.cpp", "conv.hip", "conv2.hip", "conv2h.hip", "convz.hip", "graph.hip", "heads.hip", "export.hip", "mdn.hip", "probe.hip", "vina.hip", "modes.hip", "posecheck.hip", "xtc.hip", "sites.hip", "interactions.hip", "pocketcheck.hip", "sasa.hip", "apoholo.hip", "hetero.hip", "hydrogens.hip", "decompose.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 if os.environ.get("DBFR_BUILD_DEV") == "1":      # developer build: the timing-only kernel variants behind DBFR_CONV*_ABL / _VAR (wrong results)
     FLAGS.append("-DDBFR_DEV_VARIANTS")
@@ -114,7 +114,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "frames.h"), os.path.join(CSRC, "residue_tables.inc"), os.path.join(HERE, "..", "include", "dbfr.h")]
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "pack.h"), os.path.join(CSRC, "frames.h"), os.path.join(CSRC, "residue_tables.inc"), os.path.join(HERE, "..", "include", "dbfr.h")]
     objs, jobs = [], []
     bid = source_hash(dev="-DDBFR_DEV_VARIANTS" in FLAGS)
     stamp = os.path.join(CSRC, ".build_id")

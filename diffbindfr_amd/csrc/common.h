@@ -85,7 +85,7 @@ struct ConvW2 {
   const float* b2q;   // [n_tiles*16]
   const void* W1h;    // [9] x 9280 B: lin.0 (W1p's tiles, bias rows) in the W2h tile format with the one factor 2^k1, for k_conv2h's hidden layer
   int k1;
-  int f16_depth;      // largest row depth LEFT in the fp16 packing (api.cpp pack_f16_tiles): above F16_ROW_DEPTH_OK the conv is served by the fp32-instruction kernel k_conv2
+  int f16_depth;      // largest row depth LEFT in the fp16 packing (pack.cpp pack_f16_tiles): above F16_ROW_DEPTH_OK the conv is served by the fp32-instruction kernel k_conv2
   int f16_depth_run;  // ... before the per-row factors: above F16_ROW_DEPTH_OK the rows of W2h / W1h carry their own powers of two (W2rinv / W1rinv)
   const float* W2rinv;   // [n_tiles][16] 2^-d(row) of the rows of W2h packed with per-row factors, or null (every factor 1): k_conv2h<.., ROWF> takes them off the accumulator rows
   const float* W1rinv;   // [144] the same for W1h's rows (hidden units), or null

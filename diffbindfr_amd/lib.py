@@ -302,7 +302,7 @@ class SitesOut(C.Structure):
 # every symbol include/dbfr.h declares (tests check that the library exports all of them)
 SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
            "dbfr_sample_range", "dbfr_capacity_report",
-           "dbfr_init_poses", "dbfr_extract_templates", "dbfr_status_sync", "dbfr_abi_version", "dbfr_build_id", "dbfr_last_error", "dbfr_wigner3j", "dbfr_conv_paths", "dbfr_test_pack_f16_tiles", "dbfr_test_pack_f16_rows", "dbfr_test_chunk_table", "dbfr_test_pack_f16_depth", "dbfr_probe_mfma_f16",
+           "dbfr_init_poses", "dbfr_extract_templates", "dbfr_status_sync", "dbfr_abi_version", "dbfr_build_id", "dbfr_last_error", "dbfr_wigner3j", "dbfr_conv_paths", "dbfr_test_pack_f16_tiles", "dbfr_test_pack_f16_rows", "dbfr_test_chunk_table", "dbfr_test_pack_f16_depth", "dbfr_test_pack_conv", "dbfr_probe_mfma_f16",
            "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2", "dbfr_test_sde_step",
            "dbfr_test_time_embed", "dbfr_test_mlp", "dbfr_test_atom_encoder", "dbfr_test_reduce_ln_layer", "dbfr_test_center_edges", "dbfr_test_trrot", "dbfr_test_bond_attr", "dbfr_test_tor_final",
            "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
@@ -359,6 +359,7 @@ def load():
     lib.dbfr_test_pack_f16_tiles.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
     lib.dbfr_test_pack_f16_depth.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     lib.dbfr_test_pack_f16_rows.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp, C.POINTER(i32)]
+    lib.dbfr_test_pack_conv.argtypes = [i32, vp, i32, vp, vp, i32, C.c_char_p, C.c_size_t, C.POINTER(i32)]
     lib.dbfr_test_chunk_table.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
     lib.dbfr_probe_mfma_f16.argtypes = [C.c_double, C.POINTER(C.c_double), vp]
     lib.dbfr_profile_enable.argtypes = [vp, i32]

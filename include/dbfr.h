@@ -52,7 +52,8 @@ extern "C" {
                                 8: + dbfr_test_time_embed, dbfr_test_mlp, dbfr_test_atom_encoder, dbfr_test_reduce_ln_layer, dbfr_test_center_edges, dbfr_test_trrot, dbfr_test_bond_attr, dbfr_test_tor_final (additions only);
                                    later additions under the same number: dbfr_vina_search_opts, dbfr_vina_search_workspace_bytes, dbfr_vina_search,
                                    dbfr_test_philox4x32, dbfr_test_vina_mutation,
-                                   dbfr_vina_flex_search_workspace_bytes, dbfr_vina_flex_search */
+                                   dbfr_vina_flex_search_workspace_bytes, dbfr_vina_flex_search,
+                                   dbfr_test_pack_conv */
 
 typedef enum {
   DBFR_OK = 0,
@@ -1515,6 +1516,15 @@ int dbfr_test_pack_f16_rows(const float* frag, const float* bias, int32_t n_tile
  * |value| is 2^(15 - d) after the run's factor -- and the limit up to which two fp16 pieces hold a row to 22 significant bits (17): a conv
  * with a deeper row in one of its runs is what dbfr_model_fallback_convs reports.                                                     */
 int dbfr_test_pack_f16_depth(const float* frag, const float* bias, int32_t n_tiles, int32_t* depth_out, int32_t* depth_ok_out);
+/* Test hook (host code, no GPU): every weight layout model creation builds for ONE conv of `kind` (as dbfr_conv_paths), as digests.  tensors7 = its
+ * fc.lin.0 weight and bias, fc.lin.3 weight and bias, batch_norm.mean_shift, affine_weight, affine_bias; numel7 receives their element counts
+ * (tensors7 = NULL: nothing else happens, the call returns 0).  rowscale as DBFR_F16_ROWSCALE (0, 1, 2).  The packers run as at model creation:
+ * k_conv's layout; for the K = 144 kinds then k_conv2 / k_conv2h's, the same of the vector-output rows alone (kinds 0..3), k_convz's.  Returns the
+ * number n of arrays model creation would upload; digests[2i], digests[2i + 1] = byte count and FNV-1a 64 of array i in upload order, digests[2n] =
+ * FNV-1a 64 over the non-pointer members of ConvW (with its LNDesc), ConvW2 (both) and ConvZ in declaration order; names (may be NULL) = the arrays'
+ * names, ';'-separated; *flags (may be NULL) = per-row factors present: 1 W2rinv, 2 W1rinv, 4 and 8 the same of the vector-output packing.          */
+int dbfr_test_pack_conv(int32_t kind, const float* const* tensors7, int32_t rowscale, int64_t* numel7, uint64_t* digests, int32_t digests_cap,
+                        char* names, size_t names_cap, int32_t* flags);
 /* Profiling hooks: time (ms) spent in the dominant fused conv kernel and the
  * number of launches + edges since the last reset, measured with hip events on
  * the launch stream when profiling is enabled.  conv_flops = algorithmic FLOP

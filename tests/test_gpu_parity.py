@@ -659,7 +659,7 @@ def _run_conv_hook(fn, h, layer, fam, c, E, dev):
 @pytest.mark.gpu
 def test_split_f16_vanishing_weights_next_to_an_ordinary_bias(setup, dev):
     """A conv whose lin.3 weights are 1e-30 of their usual size while its bias is not: the run factors of the W2h tiles stop where the
-    bias rows would leave fp32's range under the per-edge factor (api.cpp pack_f16_tiles), so the messages stay finite and equal the
+    bias rows would leave fp32's range under the per-edge factor (pack.cpp pack_f16_tiles), so the messages stay finite and equal the
     fp32 instruction's (which are the bias-only messages to fp32 accuracy)."""
     mcfg, p, _ = setup
     p2 = {k: v.clone() for k, v in p.items()}

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, HoloMetricsIn, HoloMetricsOpts, HoloMetricsOut, HoloSiteIn
 from .tables import residue_tables
 
@@ -489,9 +489,7 @@ def annotate(entries, pd_df, holos, **opts):
     ``holo_plddt_pli``, ``holo_lddt_pli`` (against the pose's own ligand, best automorphism; NaN when the atom counts differ),
     ``holo_chi1_rate`` / ``holo_chi12_rate`` (the share of matched residues whose chi1, or chi1 and chi2, are within
     ``export.CHI_UPPER_BOUND`` of the holo's) and ``holo_sc_rmsd_input`` / ``holo_plddt_pli_input`` (the input structure)."""
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if sum(n_pose) != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
+    n_pose = en.check_rows(entries, pd_df)
     if len(holos) != len(entries):
         raise DbfrError(f"{len(holos)} holo structures for {len(entries)} entries")
     pairs, groups, which = [], [], []

@@ -28,7 +28,7 @@ import os
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, VinaDecomposeIn, VinaDecomposeOpts, VinaDecomposeOut
 
 TERMS = ["gauss1", "gauss2", "repulsion", "hydrophobic", "hbond"]
@@ -144,21 +144,16 @@ def entry_group(e, hetero=None, waters=True, lig_types=None):
     residues of ``hetero`` (a ``hetero.HeteroRecord`` or None) after them."""
     from . import vina
     rec, rec_type, ext_pos, ext_type, n_prot = vina._entry_arrays(e, vina.receptor_type_table(), hetero, waters)
-    topo = e.topology
-    m14 = np.asarray(e.atom14_mask) > 0.5
-    prow = np.asarray(topo.pocket_rows, np.int64)
-    other = np.ones(topo.aatype.shape[0], bool)
-    other[prow] = False
-    srow = np.flatnonzero(other)[np.nonzero(topo.atom37_mask[other] > 0.5)[0]]
-    n_res = int(topo.aatype.shape[0])
+    r = en.receptor(e)
+    n_res = r.n_res
     hcol, htags = hetero_columns(hetero)
     if lig_types is None:
         if e.sdf_template is None:
             raise DbfrError(f"{e.name}: ligand types need the entry's sdf_template (or lig_types)")
         lig_types = vina.ligand_types(e.sdf_template.format(np.asarray(e.ligand_pos)))
     group = dict(lig_type=np.asarray(lig_types, np.int8), pocket=rec, pocket_type=rec_type,
-                 pocket_col=np.repeat(prow[:, None], 14, 1)[m14].astype(np.int32), static=ext_pos, static_type=ext_type,
-                 static_col=np.concatenate([srow.astype(np.int32), n_res + hcol]).astype(np.int32), n_col=n_res + len(htags))
+                 pocket_col=r.pocket_atoms[0].astype(np.int32), static=ext_pos, static_type=ext_type,
+                 static_col=np.concatenate([r.static_atoms[0].astype(np.int32), n_res + hcol]).astype(np.int32), n_col=n_res + len(htags))
     return group, htags, n_res
 
 
@@ -167,33 +162,17 @@ def decompose_entries(entries, hetero=None, poses=None, reference=None, waters=T
     ``atom`` [n_pose, N, 5] and ``totals`` [n_pose, 6] in kcal/mol (float64, from the integer outputs; NaN for an unusable frame),
     with ``tags`` (one per column) and ``n_res``; list per entry of the reference frame's ``col`` [n_col, 5] or None).
     ``hetero`` / ``poses`` / ``reference`` / ``opts``: see ``annotate``."""
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
     if hetero is not None and len(hetero) != len(entries):
         raise DbfrError(f"{len(hetero)} hetero records for {len(entries)} entries")
-    by_input = isinstance(reference, str)
-    if reference is not None and ((by_input and reference != "input") or (not by_input and len(reference) != len(entries))):
-        raise DbfrError("reference: 'input' or one [N, 3] pose per entry")
-    extra = int(reference is not None)
+    frames, n_pose, extra = en.ligand_frames(entries, poses, reference, heavy=False)
     groups, meta = [], []
-    rtags = fb.residue_tag_cache(entries)
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
-        n_atoms = int(e.ligand_traj.shape[2])
-        x = e.ligand_traj[:, -1] if poses is None else torch.as_tensor(poses[k], dtype=torch.float32, device=dev) - center
-        if tuple(x.shape) != (n_pose[k], n_atoms, 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {n_atoms} atoms")
+    rtags = en.residue_tag_cache(entries)
+    for k, (e, x) in enumerate(zip(entries, frames)):
+        n_atoms = int(x.shape[1])
         record = getattr(e, "hetero", None) if hetero is None else hetero[k]
         group, htags, n_res = entry_group(e, record, waters)
         if extra:
-            ref = e.ligand_pos if by_input else reference[k]
-            ref = torch.as_tensor(np.asarray(ref, np.float32).reshape(1, n_atoms, 3), device=dev) - center
-            x = torch.cat([x.to(torch.float32), ref])
-            m14 = np.asarray(e.atom14_mask) > 0.5
-            ref_pocket = torch.as_tensor(np.asarray(e.atom14_position, np.float32)[m14][None], device=dev)
-            group["pocket"] = torch.cat([group["pocket"].to(torch.float32), ref_pocket])
+            group["pocket"] = en.receptor(e).pocket_frames(True)
         if group["lig_type"].size != n_atoms:       # the ligand of the refinement (vina._entry_batch): every atom of the trajectory
             raise DbfrError(f"{e.name}: {group['lig_type'].size} ligand types for {n_atoms} ligand atoms")
         groups.append(dict(lig=x, **group))
@@ -202,7 +181,7 @@ def decompose_entries(entries, hetero=None, poses=None, reference=None, waters=T
         return [], []
     r = decompose(groups, **opts)
     tot = _kcal(r["totals_fixed"].cpu().numpy())
-    first, _ = fb.frame_rows(n_pose, extra)
+    first, _ = en.frame_rows(n_pose, extra)
     out, refs = [], []
     for k, (tags, n_res) in enumerate(meta):
         col, atom = _kcal(r["col_fixed"][k].cpu().numpy()), _kcal(r["atom_fixed"][k].cpu().numpy())
@@ -260,9 +239,7 @@ def annotate(entries, pd_df, hetero=None, poses=None, reference=None, top=8, wat
     ``ligand_pos``) or per entry [N, 3] absolute positions of a reference pose; it is evaluated as one extra frame of the same
     launch against the input pocket ``atom14_position`` and adds ``vd_hotspots_ref`` and ``vd_hotspot_recovery`` (the share of the
     reference's hotspot columns that are hotspots of the pose; NaN when the reference has none).  ``opts``: ``cutoff``."""
-    n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
-    if n_rows != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {n_rows} poses of the entries")
+    en.check_rows(entries, pd_df)
     res, refs = decompose_entries(entries, hetero, poses, reference, waters, **opts)
     df = pd_df.copy()
     rows = {k: [] for k in COLUMNS + (REFERENCE_COLUMNS if reference is not None else [])}
@@ -296,9 +273,7 @@ def write_atom_items(entries, pd_df, atom_terms, poses=None, threads=0):
     per entry [P, N_heavy, 5]).  Returns the paths, in row order."""
     if "docked_lig" not in pd_df.columns:
         raise DbfrError("write_atom_contributions needs the frame complex_modeling wrote (a docked_lig column)")
-    n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
-    if n_rows != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {n_rows} poses of the entries")
+    en.check_rows(entries, pd_df)
     paths, row = [], 0
     for k, e in enumerate(entries):
         if e.sdf_template is None:

@@ -1,7 +1,8 @@
 """The staging the per-pose analysis modules share (posecheck, interactions, pocketcheck, sasa, apoholo; csrc/frames.h is the
 device side): a batch is a list of groups, a group holds F frames (one pose of one complex each) of N atoms, the frames of all
 groups are laid out one after the other and every per-group array is CSR-indexed.  Only what the modules do identically lives
-here; what a module checks of its own inputs, and the wording of its refusals, stays with the module."""
+here; what a module checks of its own inputs, and the wording of its refusals, stays with the module.  What the modules read off
+``export.ComplexOutput`` entries before they stage a batch (receptor, ligand frames, frame rows) is entries.py."""
 import ctypes as C
 
 import numpy as np
@@ -78,20 +79,3 @@ def launcher(fn, In, head, order, tail, t, dev, opts, cout, host=None, once=True
 
     return launch
 
-
-def frame_rows(n_pose, extra):
-    """Entries of n_pose[k] poses plus ``extra`` (0 or 1) reference or baseline frames each, laid out entry by entry:
-    (first frame of every entry [K + 1], the frames of the poses alone in order, int64)."""
-    first = np.concatenate([[0], np.cumsum([p + extra for p in n_pose])])
-    keep = np.concatenate([np.arange(first[k], first[k] + n_pose[k]) for k in range(len(n_pose))]).astype(np.int64)
-    return first, keep
-
-
-def residue_tag_cache(entries):
-    """``interactions.residue_tags`` of every entry's topology, made once per topology: a list per entry."""
-    from .interactions import residue_tags
-    made = {}
-    for e in entries:
-        if id(e.topology) not in made:
-            made[id(e.topology)] = residue_tags(e.topology)
-    return [made[id(e.topology)] for e in entries]

@@ -34,7 +34,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, HeteroCheckIn, HeteroCheckOpts, HeteroCheckOut
 
 ORGANIC, INORGANIC, WATER = 0, 1, 2
@@ -291,41 +291,20 @@ def check(groups, cand_cap=0, **opts):
 # ------------------------------------------------------------------------------------------------ over export entries
 def _entry_groups(entries, hetero, poses, reference):
     from .posecheck import entry_chemistry
-    from .sasa import entry_receptor
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
+    from .sasa import receptor_arrays
     if hetero is not None and len(hetero) != len(entries):
         raise DbfrError(f"{len(hetero)} hetero records for {len(entries)} entries")
-    by_input = isinstance(reference, str)
-    if reference is not None and ((by_input and reference != "input") or (not by_input and len(reference) != len(entries))):
-        raise DbfrError("reference: 'input' or one [N, 3] pose per entry")
-    extra = int(reference is not None)
+    frames, n_pose, extra = en.ligand_frames(entries, poses, reference)
     groups, records, columns = [], [], []
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        center_np = np.asarray(e.pocket_center_pos, np.float32).reshape(3)
-        center = torch.as_tensor(center_np, device=dev)
-        n_atoms = int(e.ligand_traj.shape[2])
-        if poses is None:
-            x = e.ligand_traj[:, -1]
-        else:
-            x = torch.as_tensor(poses[k], dtype=torch.float32, device=dev) - center
-        if tuple(x.shape) != (n_pose[k], n_atoms, 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {n_atoms} atoms")
-        rec, arrays, m14 = entry_receptor(e)
-        if extra:
-            ref = e.ligand_pos if by_input else reference[k]
-            ref = torch.as_tensor(np.asarray(ref, np.float32).reshape(1, n_atoms, 3), device=dev) - center
-            x = torch.cat([x.to(torch.float32), ref])
-            rec = torch.cat([rec.to(torch.float32), torch.as_tensor(np.asarray(e.atom14_position, np.float32)[m14][None], device=dev)])
-        if e.heavy_mask is not None:
-            x = x[:, torch.as_tensor(np.asarray(e.heavy_mask).reshape(-1) != 0, device=dev)]
+    for k, (e, x) in enumerate(zip(entries, frames)):
+        r = en.receptor(e)
+        arrays = receptor_arrays(r)
         record = (e.hetero if hetero is None else hetero[k]) or HeteroRecord()
         rad, cov, flags = ligand_tables(entry_chemistry(e)["symbols"])
-        groups.append(dict(lig=x, lig_rad=rad, lig_cov=cov, lig_flags=flags, pocket=rec, pocket_polar=arrays["pocket_polar"],
-                           pocket_col=arrays["pocket_col"], static=arrays["static"], static_polar=arrays["static_polar"],
-                           static_col=arrays["static_col"], n_res=arrays["n_res"], **record_arrays(record, center_np)))
+        center = np.asarray(e.pocket_center_pos, np.float32).reshape(3)
+        groups.append(dict(lig=x, lig_rad=rad, lig_cov=cov, lig_flags=flags, pocket=r.pocket_frames(extra),
+                           **{q: arrays[q] for q in ("pocket_polar", "pocket_col", "static", "static_polar", "static_col", "n_res")},
+                           **record_arrays(record, center)))
         records.append(record)
         columns.append(np.concatenate([arrays["pocket_col"], arrays["static_col"]]))
     return groups, records, columns, n_pose, extra
@@ -355,8 +334,7 @@ def annotate(entries, pd_df, hetero=None, poses=None, reference=None, **opts):
     ``het_water_bridges_ref`` and ``het_bridge_recovery`` (the share of the reference's bridging waters that also bridge in the
     pose; NaN when the reference has none).  ``opts``: the thresholds of ``check``."""
     groups, records, columns, n_pose, extra = _entry_groups(entries, hetero, poses, reference)
-    if sum(n_pose) != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
+    en.check_rows(entries, pd_df)
     df = pd_df.copy()
     K = int(_opts(**opts).max_event)
     if groups and sum(n_pose) + extra * len(entries) > 0:
@@ -365,7 +343,7 @@ def annotate(entries, pd_df, hetero=None, poses=None, reference=None, **opts):
         r = {k: np.zeros((0, 3), np.float32 if k in _FLOAT_OUTPUTS else np.int32) for k in CLASS_OUTPUTS}
         r.update({k: np.zeros(0, np.int32) for k in FRAME_OUTPUTS + ["n_event"]})
         r["event_i"], r["event_f"] = np.zeros((0, K, 6), np.int32), np.zeros((0, K, 3), np.float32)
-    first, keep = fb.frame_rows(n_pose, extra)
+    first, keep = en.frame_rows(n_pose, extra)
     passed = r["passed"][keep].astype(np.int64)
     for bit, name in enumerate(CHECKS):
         df[name] = (passed >> bit & 1).astype(bool)
@@ -377,7 +355,7 @@ def annotate(entries, pd_df, hetero=None, poses=None, reference=None, **opts):
         df[f"het_min_ratio_{cname}"] = ratio[:, c]
     for c, cname in enumerate(CLASS_NAMES):
         df[f"het_volume_overlap_{cname}"] = share[:, c]
-    rtags = fb.residue_tag_cache(entries)
+    rtags = en.residue_tag_cache(entries)
     worst, displaced, bridges, metals, truncated, bridges_ref, recovery = [], [], [], [], [], [], []
 
     def bridge_names(k, ev, htag):

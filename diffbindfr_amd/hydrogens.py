@@ -32,7 +32,7 @@ import os
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, HydrogensIn, HydrogensOpts, HydrogensOut
 from .vina import XS, ligand_types, parse_molblock
 
@@ -426,29 +426,18 @@ def entry_record(e, record=None):
     return record
 
 
+def _hydrogens(e, r, his):
+    x0 = np.concatenate([np.asarray(e.atom14_position, np.float64)[r.m14], r.static.astype(np.float64)])
+    rh = receptor_hydrogens(r.aa, r.pocket_atoms, r.static_atoms, x0, chain_index=e.topology.chain_index, his=his)
+    rh["n_res"] = r.n_res
+    return rh
+
+
 def entry_receptor(e, his="both"):
     """(pocket [P, M, 3] device tensor of the final frames, static [S, 3], ``receptor_hydrogens`` over the topology's residue
     rows, pocket atom mask [R_p, 14]) of one ``export.ComplexOutput``."""
-    from .interactions import receptor_feature_tables
-    from .vina import _entry_receptor
-    T = receptor_feature_tables()
-    rec, _, ext_pos, _ = _entry_receptor(e, T["types"])
-    topo = e.topology
-    m14 = np.asarray(e.atom14_mask) > 0.5
-    paa = np.asarray(e.aatype, np.int64)
-    prow = np.asarray(topo.pocket_rows, np.int64)
-    aa = np.asarray(topo.aatype, np.int64).copy()
-    aa[prow] = paa
-    a37 = T["atom14_to_atom37"][paa]
-    other = np.ones(aa.shape[0], bool)
-    other[prow] = False
-    am = topo.atom37_mask[other] > 0.5
-    srow = np.flatnonzero(other)[np.nonzero(am)[0]]
-    x0 = np.concatenate([np.asarray(e.atom14_position, np.float64)[m14], ext_pos.astype(np.float64)])
-    rh = receptor_hydrogens(aa, (np.repeat(prow[:, None], 14, 1)[m14], a37[m14]), (srow, np.nonzero(am)[1]), x0,
-                            chain_index=topo.chain_index, his=his)
-    rh["n_res"] = int(aa.shape[0])
-    return rec, ext_pos, rh, m14
+    r = en.receptor(e)
+    return r.pocket, r.static, _hydrogens(e, r, his), r.m14
 
 
 def place_entries(entries, poses=None, records=None, reference=None, his="both", **opts):
@@ -457,41 +446,23 @@ def place_entries(entries, poses=None, records=None, reference=None, his="both",
     [P, NH_l, 3] and ``rec_h`` [P, NH_r, 3] (absolute positions), ``lig_k``, ``rec_k``, ``res_bits`` [P, n_res], ``counts`` [P, 3],
     ``n_bond`` [P], ``bond_i``, ``bond_f``, ``ligand`` (``ligand_hydrogens``), ``receptor`` (``receptor_hydrogens``), ``m14`` and --
     with a reference -- ``ref``: the same outputs of the reference frame."""
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
     if records is not None and len(records) != len(entries):
         raise DbfrError(f"{len(records)} records for {len(entries)} entries")
-    by_input = isinstance(reference, str)
-    if reference is not None and ((by_input and reference != "input") or (not by_input and len(reference) != len(entries))):
-        raise DbfrError("reference: 'input' or one [N, 3] pose per entry")
-    extra = int(reference is not None)
+    frames, n_pose, extra = en.ligand_frames(entries, poses, reference)
     groups, made = [], []
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
-        n_atoms = int(e.ligand_traj.shape[2])
-        x = e.ligand_traj[:, -1] if poses is None else torch.as_tensor(poses[k], dtype=torch.float32, device=dev) - center
-        if tuple(x.shape) != (n_pose[k], n_atoms, 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {n_atoms} atoms")
-        rec, ext_pos, rh, m14 = entry_receptor(e, his)
-        if extra:
-            ref = e.ligand_pos if by_input else reference[k]
-            ref = torch.as_tensor(np.asarray(ref, np.float32).reshape(1, n_atoms, 3), device=dev) - center
-            x = torch.cat([x.to(torch.float32), ref])
-            rec = torch.cat([rec.to(torch.float32), torch.as_tensor(np.asarray(e.atom14_position, np.float32)[m14][None], device=dev)])
-        if e.heavy_mask is not None:
-            x = x[:, torch.as_tensor(np.asarray(e.heavy_mask).reshape(-1) != 0, device=dev)]
+    for k, (e, x) in enumerate(zip(entries, frames)):
+        r = en.receptor(e)
+        rh = _hydrogens(e, r, his)
         lh = ligand_hydrogens(entry_record(e, None if records is None else records[k]))
         if lh["n_heavy"] != x.shape[1]:
             raise DbfrError(f"{e.name}: the record has {lh['n_heavy']} heavy atoms, the poses {x.shape[1]}")
-        groups.append(dict(lig=x, lig_acc=lh["acc"], lig_nbr=lh["nbr"], lig_h=lh, pocket=rec, pocket_meta=rh["pocket_meta"], static=ext_pos,
-                           static_meta=rh["static_meta"], rec_h=rh, n_res=rh["n_res"]))
-        made.append((lh, rh, m14))
+        groups.append(dict(lig=x, lig_acc=lh["acc"], lig_nbr=lh["nbr"], lig_h=lh, pocket=r.pocket_frames(extra),
+                           pocket_meta=rh["pocket_meta"], static=r.static, static_meta=rh["static_meta"], rec_h=rh, n_res=rh["n_res"]))
+        made.append((lh, rh, r.m14))
     if not groups:
         return []
     out = place(groups, **opts)
-    first, _ = fb.frame_rows(n_pose, extra)
+    first, _ = en.frame_rows(n_pose, extra)
     frame = {k: out[k].cpu().numpy() for k in ("counts", "n_bond", "bond_i", "bond_f")}
     res = []
     for k, e in enumerate(entries):
@@ -535,9 +506,7 @@ def annotate(entries, pd_df, poses=None, reference=None, records=None, **opts):
     ``atom14_position`` and adds ``hb_recovery`` (the share of the reference's (side, D, A) bonds the pose has too; NaN when the
     reference has none).  ``records``: per entry the SD record with hydrogens (default: ``ligand_record``).  ``opts``: the
     thresholds of ``place`` and ``his``."""
-    n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
-    if n_rows != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {n_rows} poses of the entries")
+    en.check_rows(entries, pd_df)
     res = place_entries(entries, poses, records, reference, **opts)
     df = pd_df.copy()
     cnt = np.concatenate([r["counts"] for r in res]).astype(np.int64) if res else np.zeros((0, 3), np.int64)
@@ -545,7 +514,7 @@ def annotate(entries, pd_df, poses=None, reference=None, records=None, **opts):
         df[name] = cnt[:, q]
     names, has_h, recovery = [], [], []
     key = lambda bi, nb: {(s, D, A) for s, D, _, A in _bond_rows(bi, nb).tolist()}
-    for e, r, tags in zip(entries, res, fb.residue_tag_cache(entries)):
+    for e, r, tags in zip(entries, res, en.residue_tag_cache(entries)):
         ref = key(r["ref"]["bond_i"], r["ref"]["n_bond"]) if reference is not None else None
         for f in range(r["counts"].shape[0]):
             names.append(bond_names(r["bond_i"][f], r["n_bond"][f], r["ligand"], r["receptor"], tags))

@@ -61,7 +61,7 @@ There is no CPU path: CPU tensors raise ``DbfrError``.  Limits: 256 ligand atoms
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, InteractionsIn, InteractionsOpts, InteractionsOut
 from .vina import _tables, ligand_types, parse_molblock, receptor_type_table
 
@@ -464,65 +464,33 @@ def entry_features(e):
     return ligand_features(e.sdf_template.format(np.asarray(e.ligand_pos, np.float64).reshape(-1, 3)))
 
 
+def _features(r):
+    feat = receptor_features(r.aa, r.pocket_atoms, r.static_atoms)
+    feat["n_res"] = r.n_res
+    return feat
+
+
 def entry_receptor(e):
     """(pocket [P, M, 3] device tensor of the final frames, static [S, 3], ``receptor_features`` over the topology's residue
-    rows, pocket atom mask [R_p, 14]) of one ``export.ComplexOutput``: the receptor ``vina._entry_receptor`` assembles."""
-    from .vina import _entry_receptor
-    T = receptor_feature_tables()
-    rec, _, ext_pos, _ = _entry_receptor(e, T["types"])
-    topo = e.topology
-    m14 = np.asarray(e.atom14_mask) > 0.5
-    paa = np.asarray(e.aatype, np.int64)
-    prow = np.asarray(topo.pocket_rows, np.int64)
-    aa = np.asarray(topo.aatype, np.int64).copy()
-    aa[prow] = paa
-    a37 = T["atom14_to_atom37"][paa]                                                  # [R_p, 14]
-    other = np.ones(aa.shape[0], bool)
-    other[prow] = False
-    am = topo.atom37_mask[other] > 0.5
-    srow = np.flatnonzero(other)[np.nonzero(am)[0]]
-    feat = receptor_features(aa, (np.repeat(prow[:, None], 14, 1)[m14], a37[m14]), (srow, np.nonzero(am)[1]))
-    feat["n_res"] = int(aa.shape[0])
-    return rec, ext_pos, feat, m14
+    rows, pocket atom mask [R_p, 14]) of one ``export.ComplexOutput``: the receptor ``entries.receptor`` assembles."""
+    r = en.receptor(e)
+    return r.pocket, r.static, _features(r), r.m14
 
 
 def fingerprint_entries(entries, poses=None, reference=None, **opts):
     """One launch over ``export.ComplexOutput`` entries: (list per entry of the [n_pose, n_res] int16 words on the host -- one
     column per topology residue --, int64 [sum n_pose, 10] counts, list per entry of the reference pose's words [n_res] or None).
     ``poses`` / ``reference`` / ``opts``: see ``annotate``."""
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
-    by_input = isinstance(reference, str)
-    if reference is not None and ((by_input and reference != "input") or (not by_input and len(reference) != len(entries))):
-        raise DbfrError("reference: 'input' or one [N, 3] pose per entry")
-    extra = int(reference is not None)
+    frames, n_pose, extra = en.ligand_frames(entries, poses, reference)
     groups = []
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
-        n_atoms = int(e.ligand_traj.shape[2])
-        if poses is None:
-            x = e.ligand_traj[:, -1]
-        else:
-            x = torch.as_tensor(poses[k], dtype=torch.float32, device=dev) - center
-        if tuple(x.shape) != (n_pose[k], n_atoms, 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {n_atoms} atoms")
-        rec, ext_pos, feat, m14 = entry_receptor(e)
-        if extra:
-            ref = e.ligand_pos if by_input else reference[k]
-            ref = torch.as_tensor(np.asarray(ref, np.float32).reshape(1, n_atoms, 3), device=dev) - center
-            x = torch.cat([x.to(torch.float32), ref])
-            ref_pocket = torch.as_tensor(np.asarray(e.atom14_position, np.float32)[m14][None], device=dev)
-            rec = torch.cat([rec.to(torch.float32), ref_pocket])
-        if e.heavy_mask is not None:
-            x = x[:, torch.as_tensor(np.asarray(e.heavy_mask).reshape(-1) != 0, device=dev)]
-        groups.append(dict(lig=x, feat=entry_features(e), pocket=rec, static=ext_pos, **feat))
+    for e, x in zip(entries, frames):
+        r = en.receptor(e)
+        groups.append(dict(lig=x, feat=entry_features(e), pocket=r.pocket_frames(extra), static=r.static, **_features(r)))
     if not groups:
         return [], np.zeros((0, len(KINDS)), np.int64), []
     bits, counts = fingerprint(groups, **opts)
     words = [b.cpu().numpy() for b in bits]
-    cnt = counts.cpu().numpy().astype(np.int64)[fb.frame_rows(n_pose, extra)[1]]
+    cnt = counts.cpu().numpy().astype(np.int64)[en.frame_rows(n_pose, extra)[1]]
     return [w[:p] for w, p in zip(words, n_pose)], cnt, [w[p] if extra else None for w, p in zip(words, n_pose)]
 
 
@@ -537,15 +505,13 @@ def annotate(entries, pd_df, poses=None, reference=None, **opts):
     positions of a reference pose; it is evaluated as one extra frame of the same launch against the input pocket
     ``atom14_position`` and adds the columns ``ifp_tanimoto`` and ``ifp_recovery`` (|pose n ref| / |ref|; NaN when the
     reference sets no bit).  ``opts``: the thresholds of ``fingerprint``.  ``fingerprint_entries`` returns the words themselves."""
-    n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
-    if n_rows != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {n_rows} poses of the entries")
+    en.check_rows(entries, pd_df)
     words, cnt, refs = fingerprint_entries(entries, poses, reference, **opts)
     df = pd_df.copy()
     for q, kind in enumerate(KINDS):
         df[f"ifp_n_{kind.lower()}"] = cnt[:, q]
     contacts = []
-    for e, w, tags in zip(entries, words, fb.residue_tag_cache(entries)):
+    for e, w, tags in zip(entries, words, en.residue_tag_cache(entries)):
         contacts += contact_names(w, e.topology, tags)
     df["ifp_contacts"] = contacts
     if reference is not None:

@@ -25,7 +25,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import lib as L
+from . import entries as en, lib as L
 from .lib import DbfrError, ModesOpts, PoseRmsdIn
 
 MAX_POSES = 4096
@@ -167,24 +167,10 @@ def _entry_perms(e):
 def _modes(entries, pd_df, score, poses, lower_is_better, opts):
     if score not in pd_df.columns:
         raise DbfrError(f"the frame has no {score!r} column")
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if sum(n_pose) != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
+    n_pose = en.check_rows(entries, pd_df)
+    pos, _, _ = en.ligand_frames(entries, poses, heavy=False, centred=False)
     if lower_is_better is None:
         lower_is_better = score != "mdn_score"
-    pos = []
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        if poses is None:
-            center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
-            x = e.ligand_traj[:, -1] + center
-        else:
-            x = torch.as_tensor(poses[k], dtype=torch.float32, device=dev)
-        if tuple(x.shape) != (n_pose[k], int(e.ligand_traj.shape[2]), 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {int(e.ligand_traj.shape[2])} atoms")
-        pos.append(x)
     R = rmsd_matrix(pos, [_entry_perms(e) for e in entries], [e.heavy_mask for e in entries])
     s = np.asarray(pd_df[score], np.float64)
     off = np.concatenate([[0], np.cumsum(n_pose)])

@@ -42,7 +42,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, PocketCheckIn, PocketCheckOpts, PocketCheckOut
 
 DEFAULTS = dict(clash_ratio=0.75, bond_tol=0.3, max_clashes=0)
@@ -262,35 +262,13 @@ def check(groups, cand_cap=0, **opts):
 
 
 # ------------------------------------------------------------------------------------------------ over export entries
-def _entry_atoms(e):
-    """(topology restypes with the pocket rows' own, (row, slot) of the pocket atoms, (row, slot) of the static atoms, pocket atom
-    mask [R_p, 14]) of one ``export.ComplexOutput``, in the atom order of ``vina._entry_receptor``."""
-    from .interactions import receptor_feature_tables
-    T = receptor_feature_tables()
-    topo = e.topology
-    m14 = np.asarray(e.atom14_mask) > 0.5
-    paa = np.asarray(e.aatype, np.int64)
-    prow = np.asarray(topo.pocket_rows, np.int64)
-    aa = np.asarray(topo.aatype, np.int64).copy()
-    aa[prow] = paa
-    a37 = T["atom14_to_atom37"][paa]
-    other = np.ones(aa.shape[0], bool)
-    other[prow] = False
-    am = topo.atom37_mask[other] > 0.5
-    srow = np.flatnonzero(other)[np.nonzero(am)[0]]
-    return aa, (np.repeat(prow[:, None], 14, 1)[m14], a37[m14]), (srow, np.nonzero(am)[1]), m14
-
-
 def entry_topology(e):
     """(``receptor_topology`` of one ``export.ComplexOutput`` from its input structure -- ``atom14_position`` for the pocket, the
     topology's atom37 positions for the rest, both pocket-centred --, static [S, 3] float32, pocket atom mask [R_p, 14])."""
-    aa, patoms, satoms, m14 = _entry_atoms(e)
-    center = np.asarray(e.pocket_center_pos, np.float32).reshape(3)
-    static = (e.topology.atom37_pos[satoms[0], satoms[1]] - center).astype(np.float32)
-    pocket0 = np.asarray(e.atom14_position, np.float32)[m14]
-    topo = receptor_topology(aa, patoms, satoms, np.concatenate([pocket0, static]))
-    topo["n_res"] = int(aa.shape[0])
-    return topo, static, m14
+    r = en.receptor(e)
+    topo = receptor_topology(r.aa, r.pocket_atoms, r.static_atoms, np.concatenate([r.pocket0, r.static]))
+    topo["n_res"] = r.n_res
+    return topo, r.static, r.m14
 
 
 def check_entries(entries, frames=None, baseline=False, **opts):
@@ -327,7 +305,7 @@ def check_entries(entries, frames=None, baseline=False, **opts):
     r = check(groups, **opts)
     rows = [x.cpu().numpy() for x in r.pop("res_clash")]
     host = {k: v.cpu().numpy() for k, v in r.items()}
-    first, keep = fb.frame_rows(n_frame, extra)
+    first, keep = en.frame_rows(n_frame, extra)
     out = {k: v[keep] for k, v in host.items()}
     out["res_clash"] = [w[:n] for w, n in zip(rows, n_frame)]
     base = [dict({k: v[first[k2] + n_frame[k2]] for k, v in host.items()}, res_clash=rows[k2][n_frame[k2]]) if extra else None
@@ -352,8 +330,7 @@ def annotate(entries, pd_df, baseline=True, frames=None, **opts):
     clashes of the entry's input structure) and ``pk_new_clash_residues`` (the residues that clash in the pose and not in the
     input).  ``frames`` / ``opts``: see ``check_entries`` / ``check``."""
     n_pose = [int(e.protein_traj.shape[0]) if frames is None else int(len(frames[k])) for k, e in enumerate(entries)]
-    if sum(n_pose) != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
+    en.check_rows(entries, pd_df, n_pose)
     r, topos, base = check_entries(entries, frames, baseline, **opts)
     df = pd_df.copy()
     passed = r["passed"].astype(np.int64)
@@ -367,7 +344,7 @@ def annotate(entries, pd_df, baseline=True, frames=None, **opts):
     df["pk_min_ratio"] = r["min_ratio"].astype(np.float64)
     worst, clashing, fresh, n_input = [], [], [], []
     i = 0
-    for e, tags, topo, rows, b in zip(entries, fb.residue_tag_cache(entries), topos, r["res_clash"], base):
+    for e, tags, topo, rows, b in zip(entries, en.residue_tag_cache(entries), topos, r["res_clash"], base):
         atoms = atom_tags(e, topo, tags)
         for f in range(rows.shape[0]):
             a, c = (int(v) for v in r["worst_pair"][i])

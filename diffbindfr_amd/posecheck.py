@@ -41,7 +41,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, PoseCheckIn, PoseCheckOpts, PoseCheckOut
 
 RADII = {"H": 1.20, "C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "P": 1.80, "S": 1.80, "Cl": 1.75, "Br": 1.85, "I": 1.98}
@@ -293,28 +293,14 @@ def annotate(entries, pd_df, poses=None, **opts):
 
     ``poses``: per entry [P, N, 3] absolute positions to check (e.g. ``vina.refine_entry``'s) against the same pocket;
     default: every pose's final frame.  ``opts``: the thresholds of ``check``."""
-    from .vina import _entry_receptor
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if sum(n_pose) != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
+    n_pose = en.check_rows(entries, pd_df)
+    frames, _, _ = en.ligand_frames(entries, poses)
     rad_table = receptor_radius_table()
     groups = []
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
-        n_atoms = int(e.ligand_traj.shape[2])
-        if poses is None:
-            x = e.ligand_traj[:, -1]
-        else:
-            x = torch.as_tensor(poses[k], dtype=torch.float32, device=dev) - center
-        if tuple(x.shape) != (n_pose[k], n_atoms, 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {n_atoms} atoms")
-        if e.heavy_mask is not None:
-            x = x[:, torch.as_tensor(np.asarray(e.heavy_mask).reshape(-1) != 0, device=dev)]
-        rec, rec_rad, ext_pos, ext_rad = _entry_receptor(e, rad_table)
-        groups.append(dict(lig=x, chem=entry_chemistry(e), pocket=rec, pocket_rad=rec_rad, static=ext_pos, static_rad=ext_rad))
+    for e, x in zip(entries, frames):
+        r = en.receptor(e)
+        rec_rad, ext_rad = r.lookup(rad_table)
+        groups.append(dict(lig=x, chem=entry_chemistry(e), pocket=r.pocket, pocket_rad=rec_rad, static=r.static, static_rad=ext_rad))
     df = pd_df.copy()
     if not groups or sum(n_pose) == 0:
         r = {k: np.zeros(0, np.int32 if k in _INT_OUTPUTS else np.float32) for k in OUTPUTS}

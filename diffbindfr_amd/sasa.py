@@ -32,7 +32,7 @@ static atoms are not limited.
 import numpy as np
 import torch
 
-from . import frames as fb, lib as L
+from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, SasaIn, SasaOpts, SasaOut
 
 DEFAULTS = dict(probe=1.4)
@@ -161,28 +161,25 @@ def burial(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
 
 
 # ------------------------------------------------------------------------------------------------ over export entries
+def receptor_arrays(r):
+    """The per-atom arrays of ``burial`` for an ``entries.Receptor``: see ``entry_receptor``."""
+    from .posecheck import RADII
+    from .vina import _tables
+    T = _tables()
+    elem = np.tile(np.asarray(T["atom37_to_element"], np.int64)[None], (len(T["restype_names3"]), 1))      # 0 C, 1 N, 2 O, 3 S
+    pel, sel = r.lookup(elem)
+    by_elem = np.array([RADII["C"], RADII["N"], RADII["O"], RADII["S"]], np.float32)
+    pol = lambda el: ((el == 1) | (el == 2)).astype(np.uint8)
+    return dict(static=r.static, pocket_rad=by_elem[pel], pocket_col=r.pocket_atoms[0].astype(np.int32), pocket_polar=pol(pel),
+                static_rad=by_elem[sel], static_col=r.static_atoms[0].astype(np.int32), static_polar=pol(sel), n_res=r.n_res)
+
+
 def entry_receptor(e):
     """(pocket [P, M, 3] device tensor of the final frames, dict of the receptor's per-atom arrays for ``burial`` -- ``static``,
     ``*_rad`` (``posecheck.RADII`` by the atom37 slot's element), ``*_col`` (the topology's residue row), ``*_polar``, ``n_res`` --,
-    pocket atom mask [R_p, 14]) of one ``export.ComplexOutput``: the receptor ``vina._entry_receptor`` assembles."""
-    from .posecheck import RADII
-    from .vina import _entry_receptor, _tables
-    T = _tables()
-    elem = np.tile(np.asarray(T["atom37_to_element"], np.int64)[None], (len(T["restype_names3"]), 1))      # 0 C, 1 N, 2 O, 3 S
-    rec, pel, ext_pos, sel = _entry_receptor(e, elem)
-    by_elem = np.array([RADII["C"], RADII["N"], RADII["O"], RADII["S"]], np.float32)
-    topo = e.topology
-    m14 = np.asarray(e.atom14_mask) > 0.5
-    prow = np.asarray(topo.pocket_rows, np.int64)
-    other = np.ones(topo.aatype.shape[0], bool)
-    other[prow] = False
-    am = topo.atom37_mask[other] > 0.5
-    srow = np.flatnonzero(other)[np.nonzero(am)[0]]
-    pol = lambda el: ((el == 1) | (el == 2)).astype(np.uint8)
-    arrays = dict(static=ext_pos, pocket_rad=by_elem[pel], pocket_col=np.repeat(prow[:, None], 14, 1)[m14].astype(np.int32),
-                  pocket_polar=pol(pel), static_rad=by_elem[sel], static_col=srow.astype(np.int32), static_polar=pol(sel),
-                  n_res=int(topo.aatype.shape[0]))
-    return rec, arrays, m14
+    pocket atom mask [R_p, 14]) of one ``export.ComplexOutput``: the receptor ``entries.receptor`` assembles."""
+    r = en.receptor(e)
+    return r.pocket, receptor_arrays(r), r.m14
 
 
 def burial_entries(entries, poses=None, reference=None, **opts):
@@ -191,40 +188,18 @@ def burial_entries(entries, poses=None, reference=None, **opts):
     column per topology residue --, list per entry of the reference frame's outputs (a dict with ``totals`` [6] and
     ``res_buried`` [n_res]) or None).  ``poses`` / ``reference`` / ``opts``: see ``annotate``."""
     from .posecheck import entry_chemistry
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if poses is not None and len(poses) != len(entries):
-        raise DbfrError(f"{len(poses)} pose sets for {len(entries)} entries")
-    by_input = isinstance(reference, str)
-    if reference is not None and ((by_input and reference != "input") or (not by_input and len(reference) != len(entries))):
-        raise DbfrError("reference: 'input' or one [N, 3] pose per entry")
-    extra = int(reference is not None)
+    frames, n_pose, extra = en.ligand_frames(entries, poses, reference)
     groups = []
-    for k, e in enumerate(entries):
-        dev = e.ligand_traj.device
-        center = torch.as_tensor(np.asarray(e.pocket_center_pos, np.float32).reshape(3), device=dev)
-        n_atoms = int(e.ligand_traj.shape[2])
-        if poses is None:
-            x = e.ligand_traj[:, -1]
-        else:
-            x = torch.as_tensor(poses[k], dtype=torch.float32, device=dev) - center
-        if tuple(x.shape) != (n_pose[k], n_atoms, 3):
-            raise DbfrError(f"{e.name}: poses of shape {tuple(x.shape)} for {n_pose[k]} poses of {n_atoms} atoms")
-        rec, arrays, m14 = entry_receptor(e)
-        if extra:
-            ref = e.ligand_pos if by_input else reference[k]
-            ref = torch.as_tensor(np.asarray(ref, np.float32).reshape(1, n_atoms, 3), device=dev) - center
-            x = torch.cat([x.to(torch.float32), ref])
-            rec = torch.cat([rec.to(torch.float32), torch.as_tensor(np.asarray(e.atom14_position, np.float32)[m14][None], device=dev)])
-        if e.heavy_mask is not None:
-            x = x[:, torch.as_tensor(np.asarray(e.heavy_mask).reshape(-1) != 0, device=dev)]
+    for e, x in zip(entries, frames):
+        r = en.receptor(e)
         chem = entry_chemistry(e)
         groups.append(dict(lig=x, lig_rad=chem["radii"], lig_polar=np.array([s in POLAR for s in chem["symbols"]], np.uint8),
-                           pocket=rec, **arrays))
+                           pocket=r.pocket_frames(extra), **receptor_arrays(r)))
     if not groups:
         return dict(totals=np.zeros((0, 6), np.int64), lig_free=[], lig_bound=[], res_buried=[]), []
     r = burial(groups, **opts)
     tot = r["totals"].cpu().numpy()
-    first, keep = fb.frame_rows(n_pose, extra)
+    first, keep = en.frame_rows(n_pose, extra)
     rows = [x.cpu().numpy() for x in r["res_buried"]]
     out = dict(totals=tot[keep], res_buried=[w[:p] for w, p in zip(rows, n_pose)])
     for key in ("lig_free", "lig_bound"):
@@ -254,9 +229,7 @@ def annotate(entries, pd_df, poses=None, reference=None, interface_area=1.0, **o
     positions of a reference pose; it is evaluated as one extra frame of the same launch against the input pocket
     ``atom14_position`` and adds ``sasa_buried_frac_ref`` and ``sasa_interface_recovery`` (the share of the reference's interface
     residues that are also in the pose's interface; NaN when the reference has none).  ``opts``: ``probe``, ``n_points``."""
-    n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
-    if n_rows != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {n_rows} poses of the entries")
+    en.check_rows(entries, pd_df)
     r, refs = burial_entries(entries, poses, reference, **opts)
     df = pd_df.copy()
     tot = r["totals"].astype(np.float64).reshape(-1, 6)
@@ -272,7 +245,7 @@ def annotate(entries, pd_df, poses=None, reference=None, interface_area=1.0, **o
     df["sasa_buried_rec_polar"] = area(tot[:, 5])
     limit = float(interface_area) * UNIT
     n_int, names, frac_ref, recovery, i = [], [], [], [], 0
-    for tags, rows, ref in zip(fb.residue_tag_cache(entries), r["res_buried"], refs if refs else [None] * len(entries)):
+    for tags, rows, ref in zip(en.residue_tag_cache(entries), r["res_buried"], refs if refs else [None] * len(entries)):
         ref_hit = np.flatnonzero(ref["res_buried"] >= limit) if ref is not None else None
         for f in range(rows.shape[0]):
             hit = np.flatnonzero(rows[f] >= limit)

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import lib as L
+from . import entries as en, lib as L
 from .lib import DbfrError, XtcIn, XtcOpts
 from .ligand import PdbLigandTemplate
 
@@ -175,9 +175,7 @@ def encode_xtc(lig, pos14, center, maps, files, dt=1.0, precision=1000.0, first_
 def _entry_dirs(entries, pd_df):
     if "docked_lig" not in pd_df.columns:
         raise DbfrError("write_trajectories needs the frame complex_modeling wrote (a docked_lig column)")
-    n_pose = [int(e.ligand_traj.shape[0]) for e in entries]
-    if sum(n_pose) != len(pd_df):
-        raise DbfrError(f"{len(pd_df)} frame rows for {sum(n_pose)} poses of the entries")
+    n_pose = en.check_rows(entries, pd_df)
     off = np.concatenate([[0], np.cumsum(n_pose)]).astype(int)
     return [[os.path.dirname(str(p)) for p in pd_df["docked_lig"].iloc[off[k]:off[k + 1]]] for k in range(len(entries))]
 

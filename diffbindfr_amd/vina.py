@@ -65,7 +65,7 @@ from collections import deque
 import numpy as np
 import torch
 
-from . import lib as L
+from . import entries as en, lib as L
 from .lib import DbfrError, VinaFlexIn, VinaIn, VinaOpts, VinaSearchOpts
 
 XS_NAMES = ["C_H", "C_P", "N_P", "N_D", "N_A", "N_DA", "O_P", "O_D", "O_A", "O_DA", "S_P", "P_P", "F_H", "Cl_H", "Br_H",
@@ -531,22 +531,10 @@ class PoseBatch:
 
 def _entry_receptor(e, rec_table):
     """Per-pose pocket atoms of the final frame (pocket-centred, atom14 order) with their types, and the non-pocket protein
-    atoms of the topology shifted into the pocket-centred frame with theirs."""
-    T = _tables()
-    center = np.asarray(e.pocket_center_pos, np.float32).reshape(3)
-    m14 = np.asarray(e.atom14_mask) > 0.5
-    aa = np.asarray(e.aatype, np.int64)
-    a37 = T["atom14_to_atom37"][aa]                                      # [R, 14]
-    rec_type = rec_table[np.repeat(aa[:, None], 14, 1)[m14], a37[m14]]
-    rec = e.protein_traj[:, -1][:, torch.as_tensor(m14, device=e.protein_traj.device)]      # [P, M, 3]
-    topo = e.topology
-    other = np.ones(topo.aatype.shape[0], bool)
-    other[np.asarray(topo.pocket_rows)] = False
-    am = topo.atom37_mask[other] > 0.5
-    oaa = topo.aatype[other].astype(np.int64)
-    ext_pos = (topo.atom37_pos[other][am] - center).astype(np.float32)
-    ext_type = rec_table[np.repeat(oaa[:, None], 37, 1)[am], np.nonzero(am)[1]]
-    return rec, rec_type, ext_pos, ext_type
+    atoms of the topology shifted into the pocket-centred frame with theirs (``entries.receptor``)."""
+    r = en.receptor(e)
+    rec_type, ext_type = r.lookup(rec_table)
+    return r.pocket, rec_type, r.static, ext_type
 
 
 def _entry_arrays(e, rec_table, hetero=None, waters=True):
@@ -967,9 +955,7 @@ def error_correct(entries, pd_df, max_iters=100, grad_tol=1e-3, threads=0, flex_
         raise DbfrError(f"{len(hetero)} hetero records for {len(entries)} entries")
     if "docked_lig" not in df.columns:
         raise DbfrError("error_correct needs the frame complex_modeling wrote (a docked_lig column)")
-    n_rows = sum(int(e.ligand_traj.shape[0]) for e in entries)
-    if n_rows != len(df):
-        raise DbfrError(f"{len(df)} frame rows for {n_rows} poses of the entries")
+    en.check_rows(entries, df)
     if flex_out is not None:
         if "protein_pdb" not in df.columns:
             raise DbfrError("error_correct(flex_dist=) needs the frame's protein_pdb column")

@@ -20,5 +20,6 @@ from . import apoholo  # noqa: F401
 from . import hetero  # noqa: F401
 from . import hydrogens  # noqa: F401
 from . import decompose  # noqa: F401
+from . import cavity  # noqa: F401
 
 register_into_druglib()

@@ -196,6 +196,22 @@ class SasaOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("lig_free", "lig_bound", "res_buried", "totals")]
 
 
+class CavityIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "pocket_ptr", "pocket_pos_off",
+                                          "pocket_pos", "pocket_rad", "pocket_col", "pocket_polar", "static_ptr", "static_pos",
+                                          "static_rad", "static_col", "static_polar", "res_ptr", "res_off", "grid_lo", "ref_frame")] + \
+               [(n, C.c_int32) for n in ("max_lig", "max_pocket", "max_res")] + [("host", C.c_void_p)]
+
+
+class CavityOpts(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("spacing", "probe", "ray_length", "lining_cutoff")] + [("min_buried", C.c_int32)]
+
+
+class CavityOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("totals", "lining", "masks", "burial", "workspace")] + [("workspace_bytes", C.c_size_t)]
+
+
 class HoloSiteIn(C.Structure):
     _fields_ = [("n_pair", C.c_int32)] + [(n, C.c_void_p) for n in ("atom_ptr", "atom_pos", "atom_res", "lig_ptr", "lig_pos", "res_ptr")] + \
                [("n_res", C.c_int32), ("max_atoms", C.c_int32), ("cutoff", C.c_float)]
@@ -314,7 +330,8 @@ SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log",
            "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
            "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
            "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
-           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check", "dbfr_hydrogens", "dbfr_vina_decompose"]
+           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check", "dbfr_hydrogens", "dbfr_vina_decompose",
+           "dbfr_pose_cavity_workspace_bytes", "dbfr_pose_cavity"]
 
 _lib = None
 
@@ -435,6 +452,8 @@ def load():
     lib.dbfr_hetero_check.argtypes = [C.POINTER(HeteroCheckIn), C.POINTER(HeteroCheckOpts), C.POINTER(HeteroCheckOut), vp]
     lib.dbfr_hydrogens.argtypes = [C.POINTER(HydrogensIn), C.POINTER(HydrogensOpts), C.POINTER(HydrogensOut), vp]
     lib.dbfr_vina_decompose.argtypes = [C.POINTER(VinaDecomposeIn), C.POINTER(VinaDecomposeOpts), C.POINTER(VinaDecomposeOut), vp]
+    lib.dbfr_pose_cavity_workspace_bytes.argtypes = [C.POINTER(CavityIn), C.POINTER(C.c_size_t)]
+    lib.dbfr_pose_cavity.argtypes = [C.POINTER(CavityIn), C.POINTER(CavityOpts), C.POINTER(CavityOut), vp]
     if lib.dbfr_abi_version() != 8:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib

@@ -53,7 +53,8 @@ extern "C" {
                                    later additions under the same number: dbfr_vina_search_opts, dbfr_vina_search_workspace_bytes, dbfr_vina_search,
                                    dbfr_test_philox4x32, dbfr_test_vina_mutation,
                                    dbfr_vina_flex_search_workspace_bytes, dbfr_vina_flex_search,
-                                   dbfr_test_pack_conv */
+                                   dbfr_test_pack_conv,
+                                   dbfr_cavity_in, dbfr_cavity_opts, dbfr_cavity_out, dbfr_pose_cavity_workspace_bytes, dbfr_pose_cavity */
 
 typedef enum {
   DBFR_OK = 0,
@@ -965,6 +966,80 @@ typedef struct {                 /* device arrays; any may be NULL              
 
 /* One launch for the whole batch.  opts NULL = defaults.                                                                    */
 int dbfr_sasa(const dbfr_sasa_in* in, const dbfr_sasa_opts* opts, const dbfr_sasa_out* out, void* hip_stream);
+
+/* ---- Cavity volume and ligand fill of each pose's pocket (csrc/cavity.hip; docs/cavity.md): the LIGSITE-style definition of
+ * docs/sites.md evaluated per frame.  Groups, frames, ligand (L) and receptor (R) atoms as in dbfr_sasa_in.  Per group a lattice
+ * of 32^3 points q = spacing * (grid_lo + (i, j, k)) (float32), shared by the group's frames.
+ *   P          points with |q - x_a|^2 < fp32((r_a + probe)^2) for a receptor atom a; q - x_a is formed first, per component, and
+ *              the squares are summed (dx^2 + dy^2) + dz^2 (float32, every operation rounded)
+ *   b(q)       the lines (3 axes, 4 body diagonals) that reach a P point within T_e = floor(ray_length / (spacing |e|)) steps in
+ *              both senses; 0 at P points; a point outside the box is solvent
+ *   cavity     solvent points with b >= min_buried
+ *   covered    points with |q - x_l|^2 < fp32(r_l^2) for a ligand atom l
+ *   C          the union of the 6-connected components of cavity points that hold a covered point
+ *   mouth      points of C with a 6-neighbour that is solvent and no cavity point (a neighbour outside the box counts)
+ *   lining     receptor atoms with |q - x_a|^2 <= fp32(lining_cutoff^2) for a q in C (bit 0 of the residue's byte), and for a q in
+ *              C that is not covered (bit 1: the free room)
+ *   totals     [frame, 12] = covered points, those in P, those that are cavity points (filled; all in C), those that are solvent
+ *              and no cavity point, |C|, mouth points, sum b over C, sum b over the filled points, lining atoms, lining atoms
+ *              flagged polar, ligand atoms whose own nearest lattice index rint(x / spacing) (float32) lies outside the box,
+ *              |C and C of frame ref_frame[g]| (-1 without a reference frame)
+ * Every result is an integer OR, count or sum: a frame's outputs are bitwise the same alone, in any batch and in any group
+ * order.  A frame with a non-finite or out-of-range (|x| > 1e4) coordinate (or a radius outside (0, 4]) gets -1 in every total,
+ * an all-zero lining row, zero masks and a zero burial grid.  Limits: N_g <= 256, M_g <= 8192, n_res_g <= 16384 (max_* above
+ * them: DBFR_ERR_ARG); grid_lo in [-4096, 4064].  Static atoms are not limited.                                              */
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]: one workgroup per frame                                                   */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; totals and masks are indexed by frame                 */
+  const int32_t* lig_ptr;        /* [G+1] first atom of every group in lig_rad (N_g atoms per frame, may be 0)              */
+  const int64_t* lig_pos_off;    /* [G] frame k of g at rows lig_pos_off[g] + k N_g of lig_pos                              */
+  const float*   lig_pos;        /* [rows, 3]                                                                               */
+  const float*   lig_rad;        /* [lig_ptr[G]] radii in (0, 4]                                                            */
+  const int32_t* pocket_ptr;     /* [G+1] first pocket atom of every group in pocket_rad / _col / _polar (may be 0 atoms)   */
+  const int64_t* pocket_pos_off; /* [G] frame k of g at rows pocket_pos_off[g] + k M_g of pocket_pos                        */
+  const float*   pocket_pos;     /* [rows, 3]                                                                               */
+  const float*   pocket_rad;
+  const int32_t* pocket_col;     /* residue column, 0 .. n_res_g - 1                                                        */
+  const uint8_t* pocket_polar;
+  const int32_t* static_ptr;     /* [G+1] static atoms of every group in static_pos / _rad / _col / _polar, or NULL = none  */
+  const float*   static_pos;     /* [static_ptr[G], 3] in the frame of lig_pos                                              */
+  const float*   static_rad;
+  const int32_t* static_col;
+  const uint8_t* static_polar;
+  const int32_t* res_ptr;        /* [G+1]: n_res_g = res_ptr[g+1] - res_ptr[g]                                               */
+  const int64_t* res_off;        /* [G] frame k of g writes lining[res_off[g] + k n_res_g ...]                              */
+  const int32_t* grid_lo;        /* [G, 3] lattice index of the box's first point (x y z), each in [-4096, 4064]            */
+  const int32_t* ref_frame;      /* [G] the launch's frame whose C every frame of the group is compared with (a frame of the
+                                    same group), -1 = none; NULL = no group has one                                         */
+  int32_t        max_lig;        /* host-known maxima over the groups (<= 256, 8192, 16384)                                 */
+  int32_t        max_pocket;
+  int32_t        max_res;
+  const void*    host;           /* NULL, or a dbfr_cavity_in whose pointers are HOST copies of the same arrays (the position
+                                    and polar arrays are not read): every count, residue column, radius, lattice corner and
+                                    reference frame is then validated before the launch (DBFR_ERR_ARG)                      */
+} dbfr_cavity_in;
+
+typedef struct {
+  float   spacing;               /* A, [0.75, 2], default 1.0                                                               */
+  float   probe;                 /* A, [0, 4], default 1.2                                                                  */
+  float   ray_length;            /* A, [spacing, 31 spacing], default 8.0                                                   */
+  float   lining_cutoff;         /* A, [0, 6], default 4.0                                                                  */
+  int32_t min_buried;            /* [1, 7], default 6                                                                       */
+} dbfr_cavity_opts;
+
+typedef struct {                 /* device arrays; totals, lining, masks and burial may be NULL                             */
+  int32_t*  totals;              /* [n_frame, 12]                                                                           */
+  uint8_t*  lining;              /* [sum_g F_g n_res_g]                                                                     */
+  uint32_t* masks;               /* [n_frame, 2, 32 (k), 32 (j)]: C, and C AND covered; bit i of a word = x index i         */
+  uint8_t*  burial;              /* [n_frame, 32 (k), 32 (j), 32 (i)] b(q), 4-byte aligned                                  */
+  void*     workspace;           /* dbfr_pose_cavity_workspace_bytes device bytes, read and written when ref_frame is given */
+  size_t    workspace_bytes;
+} dbfr_cavity_out;
+
+int dbfr_pose_cavity_workspace_bytes(const dbfr_cavity_in* in, size_t* bytes);
+/* k_pose_cavity, one workgroup per frame, then (with ref_frame) k_cavity_common on the same stream.  opts NULL = defaults.   */
+int dbfr_pose_cavity(const dbfr_cavity_in* in, const dbfr_cavity_opts* opts, const dbfr_cavity_out* out, void* hip_stream);
 
 /* ---- Holo-pocket recovery of apo / AF2 docking (csrc/apoholo.hip; docs/apoholo.md): what the reference's pair_spatial_metrics
  * (DiffBindFR/utils/apo_holo.py) measures between a holo crystal structure and the docked apo structure, for every pose.

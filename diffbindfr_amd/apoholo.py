@@ -382,8 +382,7 @@ def evaluate_launcher(pairs, groups, **opts):
                altchi=z(2 * n_row, torch.float32), dchi=z(4 * n_row, torch.float32), plddt_num=z(n_row, torch.int32),
                lddt_num=z(n_frame, torch.int32))
     order = [f for f, _ in HoloMetricsIn._fields_][2:25]
-    mx = lambda a: int(max(a)) if len(a) else 0
-    tail = (mx(S), mx(R), max(mx(N), mx(H)))
+    tail = (fb.top(S), fb.top(R), max(fb.top(N), fb.top(H)))
     cout = HoloMetricsOut(*[out[k].data_ptr() for k, _ in HoloMetricsOut._fields_])
     # (once=False: dbfr_holo_metrics takes its site count from the host copies at every launch)
     launch = fb.launcher(lib.dbfr_holo_metrics, HoloMetricsIn, (G, n_frame), order, tail, t, dev, o, cout, host, once=False)

@@ -62,11 +62,10 @@ def grid_lo(spacing=DEFAULTS["spacing"], center=None):
     return (np.asarray(DEFAULT_LO, np.int64) + np.rint(c / float(np.float32(spacing))).astype(np.int64)).astype(np.int32)
 
 
-class _Null:
-    """An absent device array."""
-    @staticmethod
-    def data_ptr():
-        return None
+_POLAR = "one radius, residue column and polar flag"
+_ATOMS = dict(lig=("one radius", [fb.Col("lig_rad", np.float32)]),
+              pocket=(_POLAR, [fb.Col("pocket_rad", np.float32), fb.Col("pocket_col", np.int32), fb.Col("pocket_polar", np.uint8)]),
+              static=(_POLAR, [fb.Col("static_rad", np.float32), fb.Col("static_col", np.int32), fb.Col("static_polar", np.uint8)]))
 
 
 def pockets_launcher(groups, masks=False, burial=False, **opts):
@@ -74,37 +73,12 @@ def pockets_launcher(groups, masks=False, burial=False, **opts):
     recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
     lib = L.load()
     o = _opts(**opts)
-    if not groups:
-        raise DbfrError("no groups to evaluate")
-    dev = fb.device_of(groups[0].get("lig"), "the cavities are computed on the GPU only (no CPU path): the poses are on ")
-    G = len(groups)
-    F, N, M, S, NR = (np.zeros(G, np.int64) for _ in range(5))
-    lig, pocket = [], []
-    names = (("lig_rad", np.float32), ("pocket_rad", np.float32), ("pocket_col", np.int32), ("pocket_polar", np.uint8),
-             ("static_rad", np.float32), ("static_col", np.int32), ("static_polar", np.uint8))
-    cols = {k: [] for k, _ in names}
-    cols["static"] = []
+    st = fb.stage(groups, "the cavities are computed on the GPU only (no CPU path): the poses are on ",
+                  fb.Block(MAX_LIG), fb.Block(MAX_POCKET), _ATOMS,
+                  count=fb.Count("n_res", "res_ptr", MAX_RES, "residue columns", "res_off"))
+    G, F, dev, n_frame = st.G, st.F, st.dev, st.n_frame
     los, refs = np.zeros((G, 3), np.int64), np.full(G, -1, np.int64)
     for g, gr in enumerate(groups):
-        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
-        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3]")
-        if N[g] > MAX_LIG:
-            raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
-        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
-        if M[g] > MAX_POCKET:
-            raise DbfrError(f"group {g}: {M[g]} pocket atoms, at most {MAX_POCKET}")
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        S[g] = st.shape[0]
-        a = {k: np.asarray(gr.get(k, np.zeros(0)), dt).reshape(-1) for k, dt in names}
-        if a["lig_rad"].size != N[g]:
-            raise DbfrError(f"group {g}: one radius per ligand atom ({N[g]})")
-        if a["pocket_rad"].size != M[g] or a["pocket_col"].size != M[g] or a["pocket_polar"].size != M[g]:
-            raise DbfrError(f"group {g}: one radius, residue column and polar flag per pocket atom ({M[g]})")
-        if a["static_rad"].size != S[g] or a["static_col"].size != S[g] or a["static_polar"].size != S[g]:
-            raise DbfrError(f"group {g}: one radius, residue column and polar flag per static atom ({S[g]})")
-        NR[g] = int(gr.get("n_res", 0))
-        if not 0 <= NR[g] <= MAX_RES:
-            raise DbfrError(f"group {g}: {NR[g]} residue columns, at most {MAX_RES}")
         los[g] = np.asarray(gr.get("grid_lo", DEFAULT_LO), np.int64).reshape(3)
         if los[g].min() < LO_MIN or los[g].max() > LO_MAX:
             raise DbfrError(f"group {g}: grid_lo {los[g].tolist()} outside [{LO_MIN}, {LO_MAX}]")
@@ -112,47 +86,25 @@ def pockets_launcher(groups, masks=False, burial=False, **opts):
             if not 0 <= int(gr["ref_frame"]) < F[g]:
                 raise DbfrError(f"group {g}: ref_frame {int(gr['ref_frame'])} is no frame of the group ({F[g]} frames)")
             refs[g] = int(F[:g].sum()) + int(gr["ref_frame"])
-        lig.append(x), pocket.append(p)
-        for k in a:
-            cols[k].append(a[k])
-        cols["static"].append(st)
-    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
-    cat = fb.cat
-    host = dict(frame_ptr=fb.ptr(F), lig_ptr=fb.ptr(N), lig_pos_off=lig_off, lig_rad=cat(cols["lig_rad"], np.float32, 1),
-                pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off, pocket_rad=cat(cols["pocket_rad"], np.float32, 1),
-                pocket_col=cat(cols["pocket_col"], np.int32, 1), pocket_polar=cat(cols["pocket_polar"], np.uint8, 1),
-                static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3), static_rad=cat(cols["static_rad"], np.float32, 1),
-                static_col=cat(cols["static_col"], np.int32, 1), static_polar=cat(cols["static_polar"], np.uint8, 1),
-                res_ptr=fb.ptr(NR), res_off=fb.ptr(F * NR, np.int64)[:-1].copy(), grid_lo=los.astype(np.int32).reshape(-1))
     with_ref = bool((refs >= 0).any())
-    if with_ref:
-        host["ref_frame"] = refs.astype(np.int32)
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
-    if not with_ref:
-        t["ref_frame"] = _Null
-    n_frame, n_row = int(F.sum()), int((F * NR).sum())
+    st.add(grid_lo=los.astype(np.int32).reshape(-1), ref_frame=refs.astype(np.int32) if with_ref else None)
     out = dict(totals=torch.zeros(n_frame + 1, len(TOTALS), dtype=torch.int32, device=dev),
-               lining=torch.zeros(n_row + 1, dtype=torch.uint8, device=dev))
+               lining=torch.zeros(int(st.offsets("n_res")[-1]) + 1, dtype=torch.uint8, device=dev))
     if masks:
         out["masks"] = torch.zeros(n_frame, 2, N_GRID, N_GRID, dtype=torch.int32, device=dev)
     if burial:
         out["burial"] = torch.zeros(n_frame, N_GRID, N_GRID, N_GRID, dtype=torch.uint8, device=dev)
-    order = [f for f, _ in CavityIn._fields_][2:22]
-    mx = lambda a: int(max(a)) if len(a) else 0
-    tail = (mx(N), mx(M), mx(NR))
+    tail = (fb.top(st.n["lig"]), fb.top(st.n["pocket"]), fb.top(st.n["n_res"]))
     ws = torch.zeros(n_frame * N_GRID * N_GRID + 1 if with_ref else 1, dtype=torch.int32, device=dev)
     cout = CavityOut(out["totals"].data_ptr(), out["lining"].data_ptr(), out["masks"].data_ptr() if masks else None,
                      out["burial"].data_ptr() if burial else None, ws.data_ptr(), 4 * (ws.numel() - 1))
-    launch = fb.launcher(lib.dbfr_pose_cavity, CavityIn, (G, n_frame), order, tail, t, dev, o, cout, host)
+    launch = fb.launcher(lib.dbfr_pose_cavity, CavityIn, (G, n_frame), st.order(CavityIn), tail, st.t, dev, o, cout, st.host)
     staged = (out, ws)
 
     def run(_keep=staged):
         launch()
 
-    roff = fb.ptr(F * NR, np.int64)
-    res = dict(totals=out["totals"][:n_frame],
-               lining=[out["lining"][roff[g]:roff[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)],
+    res = dict(totals=out["totals"][:n_frame], lining=st.views(out["lining"], "n_res"),
                grid_lo=los.astype(np.int32), spacing=float(np.float32(o.spacing)))
     if masks:
         res["masks"] = out["masks"]

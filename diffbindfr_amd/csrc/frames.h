@@ -1,8 +1,9 @@
-// The frame-batch layer of the per-pose analysis kernels (posecheck, interactions, pocketcheck, sasa, apoholo): one workgroup of 256
-// threads per frame (one pose of one complex), the frame's group found in frame_ptr, CSR-indexed atoms, the receptor = the frame's
-// pocket atoms then the group's static atoms, a bounding box in LDS to reject receptor atoms against, survivors compacted in index
-// order by ballot prefixes, and the host-side refusals that go with them.  Only what the kernels do identically lives here; every
-// float expression of a definition, every filter width and every list policy stays in the kernel's own file.
+// The frame-batch layer of the per-pose analysis kernels (posecheck, interactions, pocketcheck, sasa, apoholo, hetero, hydrogens,
+// decompose, cavity): one workgroup of 256 threads per frame (one pose of one complex), the frame's group found in frame_ptr,
+// CSR-indexed atoms, the receptor = the frame's pocket atoms then the group's static atoms, a bounding box in LDS to reject
+// receptor atoms against, survivors compacted in index order by ballot prefixes, and the host-side refusals that go with them.
+// Only what the kernels do identically lives here; every float expression of a definition, every filter width and every list
+// policy stays in the kernel's own file.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -50,65 +50,28 @@ def _opts(**opts):
 
 
 # ------------------------------------------------------------------------------------------------ device call
+_ATOMS = dict(lig=("one XS type", [fb.Col("lig_type", np.int8)]),
+              pocket=("one XS type and column", [fb.Col("pocket_type", np.int8), fb.Col("pocket_col", np.int32)]),
+              static=("one XS type and column", [fb.Col("static_type", np.int8), fb.Col("static_col", np.int32)]))
+
+
 def decompose_launcher(groups, **opts):
     """The launch of ``decompose`` prepared once: (launch() -> None, dict of outputs as ``decompose`` returns them).  Every
     launch() recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
     o = _opts(**opts)
     lib = L.load()
-    if not groups:
-        raise DbfrError("no groups to decompose")
-    dev = fb.device_of(groups[0].get("lig"), "the energy decomposition runs on the GPU only (no CPU path): the poses are on ")
-    G = len(groups)
-    F, N, M, S, NC = (np.zeros(G, np.int64) for _ in range(5))
-    lig, pocket = [], []
-    spec = (("lig_type", np.int8), ("pocket_type", np.int8), ("pocket_col", np.int32), ("static_type", np.int8), ("static_col", np.int32))
-    cols = {k: [] for k, _ in spec}
-    cols["static"] = []
-    for g, gr in enumerate(groups):
-        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
-        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3] with at least one atom", min_atoms=1)
-        if N[g] > MAX_LIG:
-            raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
-        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        S[g] = st.shape[0]
-        a = {k: np.asarray(gr.get(k, np.zeros(0)), dt).reshape(-1) for k, dt in spec}
-        if a["lig_type"].size != N[g]:
-            raise DbfrError(f"group {g}: one XS type per ligand atom ({N[g]})")
-        if a["pocket_type"].size != M[g] or a["pocket_col"].size != M[g]:
-            raise DbfrError(f"group {g}: one XS type and column per pocket atom ({M[g]})")
-        if a["static_type"].size != S[g] or a["static_col"].size != S[g]:
-            raise DbfrError(f"group {g}: one XS type and column per static atom ({S[g]})")
-        NC[g] = int(gr.get("n_col", 0))
-        if not 0 <= NC[g] <= MAX_COL:
-            raise DbfrError(f"group {g}: {NC[g]} columns, at most {MAX_COL}")
-        lig.append(x), pocket.append(p)
-        for k in a:
-            cols[k].append(a[k])
-        cols["static"].append(st)
-    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
-    cat = fb.cat
-    coff = fb.ptr(F * NC, np.int64)
-    host = dict(frame_ptr=fb.ptr(F), lig_ptr=fb.ptr(N), lig_pos_off=lig_off, pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off,
-                static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3), col_ptr=fb.ptr(NC), col_off=coff[:-1].copy())
-    for k, dt in spec:
-        host[k] = cat(cols[k], dt, 1)
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
-    n_frame, n_lrow, n_crow = int(F.sum()), int((F * N).sum()), int(coff[-1])
-    shapes = dict(col=(n_crow + 1, 5), atom=(n_lrow + 1, 5), totals=(n_frame + 1, 6))
+    st = fb.stage(groups, "the energy decomposition runs on the GPU only (no CPU path): the poses are on ",
+                  fb.Block(MAX_LIG, 1), fb.Block(), _ATOMS,
+                  count=fb.Count("n_col", "col_ptr", MAX_COL, "columns", "col_off"))
+    dev, n_frame = st.dev, st.n_frame
+    shapes = dict(col=(int(st.offsets("n_col")[-1]) + 1, 5), atom=(int(st.offsets("lig")[-1]) + 1, 5), totals=(n_frame + 1, 6))
     out = {f"{k}_terms" if k != "totals" else k: torch.empty(s, dtype=torch.float32, device=dev) for k, s in shapes.items()}
     out.update({f"{k}_fixed": torch.empty(s, dtype=torch.int64, device=dev) for k, s in shapes.items()})
-    order = [f for f, _ in VinaDecomposeIn._fields_][2:18]
-    mx = lambda a: int(max(a)) if len(a) else 0
     cout = VinaDecomposeOut(*[out[k].data_ptr() for k, _ in VinaDecomposeOut._fields_])
-    launch = fb.launcher(lib.dbfr_vina_decompose, VinaDecomposeIn, (G, n_frame), order, (mx(N), mx(NC)), t, dev, o, cout, host)
-    loff = fb.ptr(F * N, np.int64)
-    res = {}
-    for k in ("col_terms", "col_fixed"):
-        res[k] = [out[k][coff[g]:coff[g + 1]].view(int(F[g]), int(NC[g]), 5) for g in range(G)]
-    for k in ("atom_terms", "atom_fixed"):
-        res[k] = [out[k][loff[g]:loff[g + 1]].view(int(F[g]), int(N[g]), 5) for g in range(G)]
+    launch = fb.launcher(lib.dbfr_vina_decompose, VinaDecomposeIn, (st.G, n_frame), st.order(VinaDecomposeIn),
+                         (fb.top(st.n["lig"]), fb.top(st.n["n_col"])), st.t, dev, o, cout, st.host)
+    res = {k: st.views(out[k], "n_col", 5) for k in ("col_terms", "col_fixed")}
+    res.update({k: st.views(out[k], "lig", 5) for k in ("atom_terms", "atom_fixed")})
     res["totals"], res["totals_fixed"] = out["totals"][:n_frame], out["totals_fixed"][:n_frame]
     return launch, res
 

@@ -1,6 +1,6 @@
-"""What every per-pose analysis module reads off ``export.ComplexOutput`` entries before it stages a launch (frames.py), stated
-once: the receptor of an entry and its atom numbering, the ligand frames of the ``poses`` / ``reference`` contract of the
-``annotate`` functions, the frame-rows check, and the row bookkeeping of entries laid out one after the other.  Host code: numpy
+"""What the per-pose analysis modules (posecheck, interactions, pocketcheck, sasa, hetero, hydrogens, decompose, cavity, apoholo)
+read off ``export.ComplexOutput`` entries before they stage a launch (``frames.stage``), stated once: the receptor of an entry and
+its atom numbering, the ligand frames of the ``poses`` / ``reference`` contract of the ``annotate`` functions, the frame-rows check, and the row bookkeeping of entries laid out one after the other.  Host code: numpy
 and torch indexing only.  Receptor atom b is numbered identically in every module: the pocket atoms in atom14 order under
 ``atom14_mask`` (0 .. M-1), then the atoms of the topology rows outside ``pocket_rows`` in atom37 order under ``atom37_mask``."""
 from dataclasses import dataclass

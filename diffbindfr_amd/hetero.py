@@ -204,68 +204,30 @@ def _opts(**opts):
                            float(o["grid"]), f3(*scale), f3(*vmax), int(K))
 
 
+_ATOMS = dict(lig=("one vdW radius, covalent radius and flag byte",
+                   [fb.Col("lig_rad", np.float32), fb.Col("lig_cov", np.float32), fb.Col("lig_flags", np.uint8)]),
+              het=("one vdW radius, covalent radius, class and metal flag",
+                   [fb.Col("het_rad", np.float32), fb.Col("het_cov", np.float32), fb.Col("het_class", np.uint8), fb.Col("het_metal", np.uint8)]),
+              pocket=("one polar flag and residue column", [fb.Col("pocket_polar", np.uint8), fb.Col("pocket_col", np.int32)]),
+              static=("one polar flag and residue column", [fb.Col("static_polar", np.uint8), fb.Col("static_col", np.int32)]))
+
+
 def check_launcher(groups, cand_cap=0, **opts):
     """The launch of ``check`` prepared once: (launch() -> None, dict of output tensors as ``check`` returns them).  Every
     launch() recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
     o = _opts(**opts)
     lib = L.load()
-    if not groups:
-        raise DbfrError("no groups to check")
-    dev = fb.device_of(groups[0].get("lig"), "the hetero-atom checks run on the GPU only (no CPU path): the poses are on ")
-    G, K = len(groups), int(o.max_event)
-    F, N, H, M, S, NR = (np.zeros(G, np.int64) for _ in range(6))
-    lig, pocket = [], []
-    spec = (("lig_rad", np.float32), ("lig_cov", np.float32), ("lig_flags", np.uint8), ("het_rad", np.float32), ("het_cov", np.float32),
-            ("het_class", np.uint8), ("het_metal", np.uint8), ("pocket_polar", np.uint8), ("pocket_col", np.int32),
-            ("static_polar", np.uint8), ("static_col", np.int32))
-    cols = {k: [] for k, _ in spec}
-    cols["het"], cols["static"] = [], []
-    for g, gr in enumerate(groups):
-        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
-        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3] with at least one atom", min_atoms=1)
-        if N[g] > MAX_LIG:
-            raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
-        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
-        if M[g] > MAX_POCKET:
-            raise DbfrError(f"group {g}: {M[g]} pocket atoms, at most {MAX_POCKET}")
-        het = np.asarray(gr.get("het", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        H[g], S[g] = het.shape[0], st.shape[0]
-        a = {k: np.asarray(gr.get(k, np.zeros(0)), dt).reshape(-1) for k, dt in spec}
-        if any(a[k].size != N[g] for k in ("lig_rad", "lig_cov", "lig_flags")):
-            raise DbfrError(f"group {g}: one vdW radius, covalent radius and flag byte per ligand atom ({N[g]})")
-        if any(a[k].size != H[g] for k in ("het_rad", "het_cov", "het_class", "het_metal")):
-            raise DbfrError(f"group {g}: one vdW radius, covalent radius, class and metal flag per hetero atom ({H[g]})")
-        if a["pocket_polar"].size != M[g] or a["pocket_col"].size != M[g]:
-            raise DbfrError(f"group {g}: one polar flag and residue column per pocket atom ({M[g]})")
-        if a["static_polar"].size != S[g] or a["static_col"].size != S[g]:
-            raise DbfrError(f"group {g}: one polar flag and residue column per static atom ({S[g]})")
-        NR[g] = int(gr.get("n_res", 0))
-        if not 0 <= NR[g] <= MAX_RES:
-            raise DbfrError(f"group {g}: {NR[g]} residue columns, at most {MAX_RES}")
-        lig.append(x), pocket.append(p)
-        for k in a:
-            cols[k].append(a[k])
-        cols["het"].append(het), cols["static"].append(st)
-    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
-    cat = fb.cat
-    host = dict(frame_ptr=fb.ptr(F), lig_ptr=fb.ptr(N), lig_pos_off=lig_off, het_ptr=fb.ptr(H), het_pos=cat(cols["het"], np.float32, 3),
-                pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off, static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3),
-                res_ptr=fb.ptr(NR))
-    for k, dt in spec:
-        host[k] = cat(cols[k], dt, 1)
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
-    n_frame = int(F.sum())
+    st = fb.stage(groups, "the hetero-atom checks run on the GPU only (no CPU path): the poses are on ",
+                  fb.Block(MAX_LIG, 1), fb.Block(MAX_POCKET), _ATOMS,
+                  count=fb.Count("n_res", "res_ptr", MAX_RES, "residue columns"), fixed=("het", "static"))
+    dev, n_frame, K = st.dev, st.n_frame, int(o.max_event)
     new = lambda shape, k: torch.empty(shape, dtype=torch.float32 if k in _FLOAT_OUTPUTS else torch.int32, device=dev)
     out = {k: new((n_frame + 1, 3), k) for k in CLASS_OUTPUTS}
     out.update({k: new((n_frame + 1,), k) for k in FRAME_OUTPUTS + ["n_event"]})
     out["event_i"], out["event_f"] = new((n_frame + 1, K, 6), "event_i"), new((n_frame + 1, K, 3), "event_f")
-    order = [f for f, _ in HeteroCheckIn._fields_][2:25]
-    mx = lambda a: int(max(a)) if len(a) else 0
-    tail = (mx(N), mx(M), mx(NR), int(cand_cap))
+    tail = (fb.top(st.n["lig"]), fb.top(st.n["pocket"]), fb.top(st.n["n_res"]), int(cand_cap))
     cout = HeteroCheckOut(*[out[k].data_ptr() for k, _ in HeteroCheckOut._fields_])
-    launch = fb.launcher(lib.dbfr_hetero_check, HeteroCheckIn, (G, n_frame), order, tail, t, dev, o, cout, host)
+    launch = fb.launcher(lib.dbfr_hetero_check, HeteroCheckIn, (st.G, n_frame), st.order(HeteroCheckIn), tail, st.t, dev, o, cout, st.host)
     return launch, {k: v[:n_frame] for k, v in out.items()}
 
 

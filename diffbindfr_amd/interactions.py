@@ -307,75 +307,42 @@ def _opts(**opts):
     return InteractionsOpts(*[float(o[k]) for k in DEFAULTS])
 
 
+_ATOMS = dict(lig=("one type and neighbour row", [fb.Col("lig_type", np.int8), fb.Col("lig_nbr", np.int32, 3)]),
+              pocket=("one atom record", [fb.Col("pocket_meta", np.int32, 4)]), static=("one atom record", [fb.Col("static_meta", np.int32, 4)]))
+_RECORDS = (fb.Records("lgrp_ptr", [fb.Col("lgrp", np.int32, 8)], MAX_LGRP, "ligand rings and charge centres"),
+            fb.Records("rgrp_ptr", [fb.Col("rgrp", np.int32, 8)]))
+
+
 def fingerprint_launcher(groups, **opts):
     """The launch of ``fingerprint`` prepared once: (launch() -> None, list of per-group [F_g, n_res_g] int16 tensors, [sum F, 10]
     int32 counts).  Every launch() recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
     lib = L.load()
     o = _opts(**opts)
-    if not groups:
-        raise DbfrError("no groups to fingerprint")
-    dev = fb.device_of(groups[0]["lig"], "the interaction fingerprints run on the GPU only (no CPU path): the poses are on ")
-    G = len(groups)
-    lig, pocket, ltype, lnbr, lgrp, pmeta, stat, smeta, rgrp = ([] for _ in range(9))
-    F, N, M, S, NR = (np.zeros(G, np.int64) for _ in range(5))
-    for g, gr in enumerate(groups):
-        ft = gr["feat"]
-        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
-        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N >= 1, 3]", min_atoms=1)
-        if N[g] > MAX_LIG:
-            raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
-        lt = np.asarray(ft["types"], np.int8).reshape(-1)
-        ln = np.asarray(ft["nbr"], np.int32).reshape(-1, 3)
-        lg = np.asarray(ft["groups"], np.int32).reshape(-1, 8)
-        if lt.size != N[g] or ln.shape[0] != N[g]:
-            raise DbfrError(f"group {g}: {lt.size} ligand types and {ln.shape[0]} neighbour rows for {N[g]} atoms")
-        if lg.shape[0] > MAX_LGRP:
-            raise DbfrError(f"group {g}: {lg.shape[0]} ligand rings and charge centres, at most {MAX_LGRP}")
-        if (ln.size and (ln.min() < -1 or ln.max() >= N[g])) or (lg.size and (lg[:, 1:7].min() < -1 or lg[:, 1:7].max() >= N[g])):
-            raise DbfrError(f"group {g}: a ligand neighbour or group atom index lies outside its {N[g]} atoms")
+    feat = [gr["feat"] for gr in groups]
+    st = fb.stage([dict(gr, lig_type=ft["types"], lig_nbr=ft["nbr"], lgrp=ft["groups"], rgrp=gr.get("rec_groups")) for gr, ft in zip(groups, feat)],
+                  "the interaction fingerprints run on the GPU only (no CPU path): the poses are on ",
+                  fb.Block(MAX_LIG, 1), fb.Block(), _ATOMS, _RECORDS, fb.Count("n_res", "res_ptr", MAX_RES, "residues", "bits_off"))
+    n = st.n
+    for g, a in enumerate(st.rows):
+        N, NR, MR = n["lig"][g], n["n_res"][g], int(n["pocket"][g] + n["static"][g])
+        ln, lg, rg = a["lig_nbr"], a["lgrp"], a["rgrp"]
+        if (ln.size and (ln.min() < -1 or ln.max() >= N)) or (lg.size and (lg[:, 1:7].min() < -1 or lg[:, 1:7].max() >= N)):
+            raise DbfrError(f"group {g}: a ligand neighbour or group atom index lies outside its {N} atoms")
         if lg.size and ((lg[:, 0] < 0).any() or (lg[:, 0] > 2).any() or (lg[:, 1] < 0).any()):
             raise DbfrError(f"group {g}: a ligand group needs a kind in 0..2 and at least one atom")
-        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
-        pm = np.asarray(gr.get("pocket_meta", np.zeros((0, 4))), np.int32).reshape(-1, 4)
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        sm = np.asarray(gr.get("static_meta", np.zeros((0, 4))), np.int32).reshape(-1, 4)
-        rg = np.asarray(gr.get("rec_groups", np.zeros((0, 8))), np.int32).reshape(-1, 8)
-        if pm.shape[0] != M[g] or sm.shape[0] != st.shape[0]:
-            raise DbfrError(f"group {g}: {pm.shape[0]} / {sm.shape[0]} receptor atom records for {M[g]} pocket and {st.shape[0]} "
-                            "static atoms")
-        S[g] = st.shape[0]
-        NR[g] = int(gr.get("n_res", 0))
-        if not 0 <= NR[g] <= MAX_RES:
-            raise DbfrError(f"group {g}: {NR[g]} residues, at most {MAX_RES}")
-        MR = int(M[g] + S[g])
-        for name, a in (("receptor atom", np.concatenate([pm, sm])), ("receptor group", rg)):
-            if a.size and ((a[:, 0] < 0).any() or (a[:, 0] >> 8).max() >= NR[g] or a[:, 1:7 if a.shape[1] == 8 else 4].min() < -1 or
-                           a[:, 1:7 if a.shape[1] == 8 else 4].max() >= MR):
-                raise DbfrError(f"group {g}: a {name} names a residue outside its {NR[g]} or an atom outside its {MR}")
+        for name, x in (("receptor atom", np.concatenate([a["pocket_meta"], a["static_meta"]])), ("receptor group", rg)):
+            if x.size and ((x[:, 0] < 0).any() or (x[:, 0] >> 8).max() >= NR or x[:, 1:7 if x.shape[1] == 8 else 4].min() < -1 or
+                           x[:, 1:7 if x.shape[1] == 8 else 4].max() >= MR):
+                raise DbfrError(f"group {g}: a {name} names a residue outside its {NR} or an atom outside its {MR}")
         if rg.size and ((rg[:, 0] & 255) > 2).any():
             raise DbfrError(f"group {g}: a receptor group needs a kind in 0..2")
-        lig.append(x), pocket.append(p)
-        ltype.append(lt), lnbr.append(ln), lgrp.append(lg), pmeta.append(pm), stat.append(st), smeta.append(sm), rgrp.append(rg)
-    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
-    ptr, cat = fb.ptr, fb.cat
-    host = dict(frame_ptr=ptr(F), lig_ptr=ptr(N), lig_pos_off=lig_off, lig_type=cat(ltype, np.int8, 1), lig_nbr=cat(lnbr, np.int32, 3),
-                lgrp_ptr=ptr([len(a) for a in lgrp]), lgrp=cat(lgrp, np.int32, 8), pocket_ptr=ptr(M), pocket_pos_off=pocket_off,
-                pocket_meta=cat(pmeta, np.int32, 4), static_ptr=ptr(S), static_pos=cat(stat, np.float32, 3),
-                static_meta=cat(smeta, np.int32, 4), rgrp_ptr=ptr([len(a) for a in rgrp]), rgrp=cat(rgrp, np.int32, 8), res_ptr=ptr(NR),
-                bits_off=ptr(F * NR, np.int64)[:-1].copy())
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
-    n_frame, n_bits = int(F.sum()), int((F * NR).sum())
-    bits = torch.zeros(n_bits + 1, dtype=torch.int16, device=dev)
+    dev, n_frame = st.dev, st.n_frame
+    bits = torch.zeros(int(st.offsets("n_res")[-1]) + 1, dtype=torch.int16, device=dev)
     counts = torch.zeros(n_frame + 1, 10, dtype=torch.int32, device=dev)
-    mx = lambda a: int(max(a)) if len(a) else 0
-    order = ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_type", "lig_nbr", "lgrp_ptr", "lgrp", "pocket_ptr", "pocket_pos_off",
-             "pocket_pos", "pocket_meta", "static_ptr", "static_pos", "static_meta", "rgrp_ptr", "rgrp", "res_ptr", "bits_off")
     cout = InteractionsOut(bits.data_ptr(), counts.data_ptr())
-    launch = fb.launcher(lib.dbfr_interactions, InteractionsIn, (G, n_frame), order, (mx(N), mx([len(a) for a in lgrp]), mx(NR)), t, dev, o, cout)
-    off = ptr(F * NR, np.int64)
-    rows = [bits[off[g]:off[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)]
-    return launch, rows, counts[:n_frame]
+    launch = fb.launcher(lib.dbfr_interactions, InteractionsIn, (st.G, n_frame), st.order(InteractionsIn),
+                         (fb.top(n["lig"]), fb.top(n["lgrp"]), fb.top(n["n_res"])), st.t, dev, o, cout)
+    return launch, st.views(bits, "n_res"), counts[:n_frame]
 
 
 def fingerprint(groups, **opts):

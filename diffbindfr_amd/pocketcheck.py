@@ -170,79 +170,40 @@ def _opts(**opts):
     return PocketCheckOpts(float(o["clash_ratio"]), float(o["bond_tol"]), int(o["max_clashes"]))
 
 
+_ATOMS = dict(pocket=("one radius, residue column and movable rank",
+                      [fb.Col("pocket_rad", np.float32), fb.Col("pocket_col", np.int32), fb.Col("pocket_rank", np.int32)]),
+              static=("one radius and residue column", [fb.Col("static_rad", np.float32), fb.Col("static_col", np.int32)]))
+_RECORDS = (fb.Records("mov_ptr", [fb.Col("mov_atom", np.int32)]), fb.Records(None, [fb.Col("excl", np.int32)]),
+            fb.Records("closure_ptr", [fb.Col("closure_ab", np.int32, 2), fb.Col("closure_len", np.float32)]))
+_OUTPUTS = ("n_clash", "min_ratio", "worst_pair", "res_clash", "n_broken", "max_bond_dev", "passed")
+
+
 def check_launcher(groups, cand_cap=0, **opts):
     """The launch of ``check`` prepared once: (launch() -> None, dict of outputs as ``check`` returns them).  Every launch()
     recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
     lib = L.load()
     o = _opts(**opts)
-    if not groups:
-        raise DbfrError("no groups to check")
-    dev = fb.device_of(groups[0].get("pocket"), "the pocket checks run on the GPU only (no CPU path): the pocket atoms are on ")
-    G = len(groups)
-    F, M, S, NMOV, NC, NR = (np.zeros(G, np.int64) for _ in range(6))
-    pocket, cols = [], {k: [] for k in ("pocket_rad", "pocket_col", "pocket_rank", "static", "static_rad", "static_col", "mov_atom", "excl",
-                            "closure", "closure_len")}
-    excl_len = []
-    for g, gr in enumerate(groups):
-        fb.on_device(g, dev, "pocket atoms must be a device tensor", gr["pocket"])
-        p, F[g], M[g] = fb.pose_rows(gr["pocket"], g, dev, "pocket atoms must be [F, M, 3]")
-        if M[g] > MAX_POCKET:
-            raise DbfrError(f"group {g}: {M[g]} pocket atoms, at most {MAX_POCKET}")
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        S[g] = st.shape[0]
-        a = {k: np.asarray(gr.get(k, np.zeros(0)), dt).reshape(-1) for k, dt in
-             (("pocket_rad", np.float32), ("pocket_col", np.int32), ("pocket_rank", np.int32), ("static_rad", np.float32),
-              ("static_col", np.int32), ("mov_atom", np.int32), ("excl", np.int32), ("closure_len", np.float32))}
+    st = fb.stage([dict(gr, closure_ab=gr.get("closure")) for gr in groups],
+                  "the pocket checks run on the GPU only (no CPU path): the pocket atoms are on ", None, fb.Block(MAX_POCKET), _ATOMS, _RECORDS,
+                  fb.Count("n_res", "res_ptr", MAX_RES, "residue columns", "res_off"))
+    n, excl_len = st.n, []
+    for g, gr in enumerate(groups):                  # the exclusion lists: one CSR pointer over the movable atoms of all groups
         ep = np.asarray(gr.get("excl_ptr", np.zeros(1)), np.int64).reshape(-1)
-        cl = np.asarray(gr.get("closure", np.zeros((0, 2))), np.int32).reshape(-1, 2)
-        if a["pocket_rad"].size != M[g] or a["pocket_col"].size != M[g] or a["pocket_rank"].size != M[g]:
-            raise DbfrError(f"group {g}: one radius, residue column and movable rank per pocket atom ({M[g]})")
-        if a["static_rad"].size != S[g] or a["static_col"].size != S[g]:
-            raise DbfrError(f"group {g}: one radius and residue column per static atom ({S[g]})")
-        NMOV[g], NC[g], NR[g] = a["mov_atom"].size, cl.shape[0], int(gr.get("n_res", 0))
-        if ep.size != NMOV[g] + 1 or ep[0] != 0 or ep[-1] != a["excl"].size or (np.diff(ep) < 0).any():
-            raise DbfrError(f"group {g}: excl_ptr must be the CSR row pointer of {NMOV[g]} movable atoms into excl")
-        if a["closure_len"].size != NC[g]:
-            raise DbfrError(f"group {g}: one input length per closure bond")
-        if not 0 <= NR[g] <= MAX_RES:
-            raise DbfrError(f"group {g}: {NR[g]} residue columns, at most {MAX_RES}")
-        pocket.append(p)
+        if ep.size != n["mov_atom"][g] + 1 or ep[0] != 0 or ep[-1] != n["excl"][g] or (np.diff(ep) < 0).any():
+            raise DbfrError(f"group {g}: excl_ptr must be the CSR row pointer of {n['mov_atom'][g]} movable atoms into excl")
         excl_len.append(np.diff(ep))
-        for k in a:
-            cols[k].append(a[k])
-        cols["static"].append(st)
-        cols["closure"].append(cl)
-    pocket_pos, pocket_off = fb.pose_block(pocket, F, M, dev)
-    cat = fb.cat
-    all_len = np.concatenate(excl_len) if excl_len else np.zeros(0, np.int64)
-    host = dict(frame_ptr=fb.ptr(F), pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off,
-                pocket_rad=cat(cols["pocket_rad"], np.float32, 1), pocket_col=cat(cols["pocket_col"], np.int32, 1),
-                pocket_rank=cat(cols["pocket_rank"], np.int32, 1), static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3),
-                static_rad=cat(cols["static_rad"], np.float32, 1), static_col=cat(cols["static_col"], np.int32, 1),
-                mov_ptr=fb.ptr(NMOV), mov_atom=cat(cols["mov_atom"], np.int32, 1), excl_ptr=np.append(fb.ptr(all_len), 0).astype(np.int32),
-                excl=cat(cols["excl"], np.int32, 1), closure_ptr=fb.ptr(NC), closure_ab=cat(cols["closure"], np.int32, 2),
-                closure_len=cat(cols["closure_len"], np.float32, 1), res_ptr=fb.ptr(NR), res_off=fb.ptr(F * NR, np.int64)[:-1].copy())
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["pocket_pos"] = pocket_pos
-    n_frame, n_row = int(F.sum()), int((F * NR).sum())
-    out = dict(n_clash=torch.zeros(n_frame + 1, 3, dtype=torch.int32, device=dev),
-               min_ratio=torch.zeros(n_frame + 1, dtype=torch.float32, device=dev),
-               worst_pair=torch.zeros(n_frame + 1, 2, dtype=torch.int32, device=dev),
-               res_clash=torch.zeros(n_row + 1, dtype=torch.uint8, device=dev),
-               n_broken=torch.zeros(n_frame + 1, dtype=torch.int32, device=dev),
-               max_bond_dev=torch.zeros(n_frame + 1, dtype=torch.float32, device=dev),
-               passed=torch.zeros(n_frame + 1, dtype=torch.int32, device=dev))
-    order = ("frame_ptr", "pocket_ptr", "pocket_pos_off", "pocket_pos", "pocket_rad", "pocket_col", "pocket_rank", "static_ptr",
-             "static_pos", "static_rad", "static_col", "mov_ptr", "mov_atom", "excl_ptr", "excl", "closure_ptr", "closure_ab",
-             "closure_len", "res_ptr", "res_off")
-    mx = lambda a: int(max(a)) if len(a) else 0
-    maxima = (mx(M), mx(all_len), mx(NR), int(cand_cap))
-    cout = PocketCheckOut(*[out[k].data_ptr() for k in ("n_clash", "min_ratio", "worst_pair", "res_clash", "n_broken", "max_bond_dev",
-                                                       "passed")])
-    launch = fb.launcher(lib.dbfr_pocket_check, PocketCheckIn, (G, n_frame), order, maxima, t, dev, o, cout, host)
-    off = fb.ptr(F * NR, np.int64)
+    all_len = np.concatenate(excl_len)
+    st.add(excl_ptr=np.append(fb.ptr(all_len), 0).astype(np.int32))
+    dev, n_frame = st.dev, st.n_frame
+    new = lambda dtype, *shape: torch.zeros(*shape, dtype=dtype, device=dev)
+    out = dict(n_clash=new(torch.int32, n_frame + 1, 3), min_ratio=new(torch.float32, n_frame + 1), worst_pair=new(torch.int32, n_frame + 1, 2),
+               res_clash=new(torch.uint8, int(st.offsets("n_res")[-1]) + 1), n_broken=new(torch.int32, n_frame + 1),
+               max_bond_dev=new(torch.float32, n_frame + 1), passed=new(torch.int32, n_frame + 1))
+    maxima = (fb.top(n["pocket"]), fb.top(all_len), fb.top(n["n_res"]), int(cand_cap))
+    cout = PocketCheckOut(*[out[k].data_ptr() for k in _OUTPUTS])
+    launch = fb.launcher(lib.dbfr_pocket_check, PocketCheckIn, (st.G, n_frame), st.order(PocketCheckIn), maxima, st.t, dev, o, cout, st.host)
     res = {k: v[:n_frame] for k, v in out.items() if k != "res_clash"}
-    res["res_clash"] = [out["res_clash"][off[g]:off[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)]
+    res["res_clash"] = st.views(out["res_clash"], "n_res")
     return launch, res
 
 

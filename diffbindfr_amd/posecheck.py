@@ -196,65 +196,34 @@ def _opts(**opts):
     return PoseCheckOpts(*[float(o[k]) for k in DEFAULTS])
 
 
+_ATOMS = {side: ("one radius", [fb.Col(side + "_rad", np.float32)]) for side in ("lig", "pocket", "static")}
+_RECORDS = (fb.Records("pair_ptr", [fb.Col("pair_ij", np.int32, 2)]), fb.Records("flat_ptr", [fb.Col("flat_atoms", np.int32, FLAT_WIDTH)]),
+            fb.Records("stereo_ptr", [fb.Col("stereo_atoms", np.int32, 4), fb.Col("stereo_sign", np.int8)]))
+
+
 def check_launcher(groups, cand_cap=0, **opts):
     """The launch of ``check`` prepared once: (launch() -> None, dict of per-frame output tensors).  Every launch() recomputes
     the outputs from the staged inputs on the current stream (benchmarks)."""
     lib = L.load()
     o = _opts(**opts)
-    if not groups:
-        raise DbfrError("no groups to check")
-    dev = fb.device_of(groups[0]["lig"], "the pose checks run on the GPU only (no CPU path): the poses are on ")
-    G = len(groups)
-    lig, pocket, lrad, prad, stat, srad, pairs, flat, stereo, sign = [], [], [], [], [], [], [], [], [], []
-    F, N, M, S = (np.zeros(G, np.int64) for _ in range(4))
-    for g, gr in enumerate(groups):
-        ch = gr["chem"]
-        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
-        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3]")
-        if len(ch["radii"]) != N[g]:
-            raise DbfrError(f"group {g}: {len(ch['radii'])} ligand radii for {N[g]} atoms")
-        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
-        pr = np.asarray(gr.get("pocket_rad", np.zeros(0)), np.float32).reshape(-1)
-        if pr.size != M[g]:
-            raise DbfrError(f"group {g}: {pr.size} pocket radii for {M[g]} pocket atoms")
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        sr = np.asarray(gr.get("static_rad", np.zeros(0)), np.float32).reshape(-1)
-        if sr.size != st.shape[0]:
-            raise DbfrError(f"group {g}: {sr.size} static radii for {st.shape[0]} static atoms")
-        S[g] = st.shape[0]
-        pq = np.asarray(ch["pairs"], np.int32).reshape(-1, 2)
-        fl = np.asarray(ch["flat"], np.int32).reshape(-1, FLAT_WIDTH)
-        sq = np.asarray(ch["stereo"], np.int32).reshape(-1, 4)
-        sg = np.asarray(ch["stereo_sign"], np.int8).reshape(-1)
-        for name, a, lo in (("pair", pq, 0), ("flatness", fl, -1), ("stereo", sq, 0)):
-            if a.size and (a.min() < lo or a.max() >= N[g]):
-                raise DbfrError(f"group {g}: a {name} atom index lies outside its {N[g]} atoms")
+    chem = [gr["chem"] for gr in groups]
+    st = fb.stage([dict(gr, lig_rad=ch["radii"], pair_ij=ch["pairs"], flat_atoms=ch["flat"], stereo_atoms=ch["stereo"],
+                        stereo_sign=ch["stereo_sign"]) for gr, ch in zip(groups, chem)],
+                  "the pose checks run on the GPU only (no CPU path): the poses are on ", fb.Block(), fb.Block(), _ATOMS, _RECORDS)
+    for g, a in enumerate(st.rows):
+        N, fl = st.n["lig"][g], a["flat_atoms"]
+        for name, x, lo in (("pair", a["pair_ij"], 0), ("flatness", fl, -1), ("stereo", a["stereo_atoms"], 0)):
+            if x.size and (x.min() < lo or x.max() >= N):
+                raise DbfrError(f"group {g}: a {name} atom index lies outside its {N} atoms")
         if ((fl >= 0).sum(1) < 4).any() or (fl[:, :2] < 0).any():
             raise DbfrError(f"group {g}: a flatness bond needs its two atoms and at least 4 atoms in all")
-        if sg.size != sq.shape[0] or not np.isin(sg, (-1, 1)).all():
+        if not np.isin(a["stereo_sign"], (-1, 1)).all():
             raise DbfrError(f"group {g}: one input sign (+1 / -1) per stereo bond")
-        lig.append(x), pocket.append(p)
-        lrad.append(np.asarray(ch["radii"], np.float32))
-        prad.append(pr), stat.append(st), srad.append(sr)
-        pairs.append(pq), flat.append(fl), stereo.append(sq), sign.append(sg)
-    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
-    ptr, cat = fb.ptr, fb.cat
-    host = dict(frame_ptr=ptr(F), lig_ptr=ptr(N), lig_pos_off=lig_off, lig_rad=cat(lrad, np.float32, 1), pocket_ptr=ptr(M),
-                pocket_pos_off=pocket_off, pocket_rad=cat(prad, np.float32, 1), static_ptr=ptr(S), static_pos=cat(stat, np.float32, 3),
-                static_rad=cat(srad, np.float32, 1), pair_ptr=ptr([len(p) for p in pairs]), pair_ij=cat(pairs, np.int32, 2),
-                flat_ptr=ptr([len(p) for p in flat]), flat_atoms=cat(flat, np.int32, FLAT_WIDTH),
-                stereo_ptr=ptr([len(p) for p in stereo]), stereo_atoms=cat(stereo, np.int32, 4), stereo_sign=cat(sign, np.int8, 1))
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
-    n_frame = int(F.sum())
+    dev, n_frame, n = st.dev, st.n_frame, st.n
     out = {k: torch.empty(n_frame + 1, dtype=torch.int32 if k in _INT_OUTPUTS else torch.float32, device=dev) for k in OUTPUTS}
-    mx = lambda a: int(max(a)) if len(a) else 0
-    order = ("frame_ptr", "lig_ptr", "lig_pos_off", "lig_pos", "lig_rad", "pocket_ptr", "pocket_pos_off", "pocket_pos", "pocket_rad",
-             "static_ptr", "static_pos", "static_rad", "pair_ptr", "pair_ij", "flat_ptr", "flat_atoms", "stereo_ptr", "stereo_atoms",
-             "stereo_sign")
-    maxima = (mx(N), mx([len(p) for p in pairs]), mx([len(p) for p in flat]), mx([len(p) for p in stereo]), int(cand_cap))
+    maxima = (fb.top(n["lig"]), fb.top(n["pair_ij"]), fb.top(n["flat_atoms"]), fb.top(n["stereo_atoms"]), int(cand_cap))
     cout = PoseCheckOut(*[out[k].data_ptr() for k in OUTPUTS])
-    launch = fb.launcher(lib.dbfr_pose_check, PoseCheckIn, (G, n_frame), order, maxima, t, dev, o, cout)
+    launch = fb.launcher(lib.dbfr_pose_check, PoseCheckIn, (st.G, n_frame), st.order(PoseCheckIn), maxima, st.t, dev, o, cout)
     return launch, {k: v[:n_frame] for k, v in out.items()}
 
 

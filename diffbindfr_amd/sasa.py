@@ -71,76 +71,35 @@ def _opts(**opts):
     return SasaOpts(float(o["probe"]))
 
 
+_POLAR = "one radius, residue column and polar flag"
+_ATOMS = dict(lig=("one radius and polar flag", [fb.Col("lig_rad", np.float32), fb.Col("lig_polar", np.uint8)]),
+              pocket=(_POLAR, [fb.Col("pocket_rad", np.float32), fb.Col("pocket_col", np.int32), fb.Col("pocket_polar", np.uint8)]),
+              static=(_POLAR, [fb.Col("static_rad", np.float32), fb.Col("static_col", np.int32), fb.Col("static_polar", np.uint8)]))
+
+
 def burial_launcher(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
     """The launch of ``burial`` prepared once: (launch() -> None, dict of outputs as ``burial`` returns them).  Every launch()
     recomputes the outputs from the staged inputs on the current stream (benchmarks)."""
     lib = L.load()
     o = _opts(**opts)
-    if not groups:
-        raise DbfrError("no groups to evaluate")
-    dev = fb.device_of(groups[0].get("lig"), "the surface areas are computed on the GPU only (no CPU path): the poses are on ")
     pts = sphere_points(n_points) if points is None else np.ascontiguousarray(points, np.float32).reshape(-1, 3)
     n_points = int(pts.shape[0])
-    G = len(groups)
-    F, N, M, S, NR = (np.zeros(G, np.int64) for _ in range(5))
-    lig, pocket = [], []
-    cols = {k: [] for k in ("lig_rad", "lig_polar", "pocket_rad", "pocket_col", "pocket_polar", "static", "static_rad", "static_col",
-                            "static_polar")}
-    for g, gr in enumerate(groups):
-        fb.on_device(g, dev, "poses and pocket atoms must be device tensors", gr["lig"], gr.get("pocket"))
-        x, F[g], N[g] = fb.pose_rows(gr["lig"], g, dev, "ligand poses must be [F, N, 3]")
-        if N[g] > MAX_LIG:
-            raise DbfrError(f"group {g}: {N[g]} ligand atoms, at most {MAX_LIG}")
-        p, _, M[g] = fb.pose_rows(gr.get("pocket"), g, dev, "pocket atoms must be [F, M, 3] with the frames of the poses", F[g])
-        if M[g] > MAX_POCKET:
-            raise DbfrError(f"group {g}: {M[g]} pocket atoms, at most {MAX_POCKET}")
-        st = np.asarray(gr.get("static", np.zeros((0, 3))), np.float32).reshape(-1, 3)
-        S[g] = st.shape[0]
-        a = {k: np.asarray(gr.get(k, np.zeros(0)), dt).reshape(-1) for k, dt in
-             (("lig_rad", np.float32), ("lig_polar", np.uint8), ("pocket_rad", np.float32), ("pocket_col", np.int32),
-              ("pocket_polar", np.uint8), ("static_rad", np.float32), ("static_col", np.int32), ("static_polar", np.uint8))}
-        if a["lig_rad"].size != N[g] or a["lig_polar"].size != N[g]:
-            raise DbfrError(f"group {g}: one radius and polar flag per ligand atom ({N[g]})")
-        if a["pocket_rad"].size != M[g] or a["pocket_col"].size != M[g] or a["pocket_polar"].size != M[g]:
-            raise DbfrError(f"group {g}: one radius, residue column and polar flag per pocket atom ({M[g]})")
-        if a["static_rad"].size != S[g] or a["static_col"].size != S[g] or a["static_polar"].size != S[g]:
-            raise DbfrError(f"group {g}: one radius, residue column and polar flag per static atom ({S[g]})")
-        NR[g] = int(gr.get("n_res", 0))
-        if not 0 <= NR[g] <= MAX_RES:
-            raise DbfrError(f"group {g}: {NR[g]} residue columns, at most {MAX_RES}")
-        lig.append(x), pocket.append(p)
-        for k in a:
-            cols[k].append(a[k])
-        cols["static"].append(st)
-    (lig_pos, lig_off), (pocket_pos, pocket_off) = fb.pose_block(lig, F, N, dev), fb.pose_block(pocket, F, M, dev)
-    cat = fb.cat
-    host = dict(frame_ptr=fb.ptr(F), lig_ptr=fb.ptr(N), lig_pos_off=lig_off, lig_rad=cat(cols["lig_rad"], np.float32, 1),
-                lig_polar=cat(cols["lig_polar"], np.uint8, 1), pocket_ptr=fb.ptr(M), pocket_pos_off=pocket_off,
-                pocket_rad=cat(cols["pocket_rad"], np.float32, 1), pocket_col=cat(cols["pocket_col"], np.int32, 1),
-                pocket_polar=cat(cols["pocket_polar"], np.uint8, 1), static_ptr=fb.ptr(S), static_pos=cat(cols["static"], np.float32, 3),
-                static_rad=cat(cols["static_rad"], np.float32, 1), static_col=cat(cols["static_col"], np.int32, 1),
-                static_polar=cat(cols["static_polar"], np.uint8, 1), res_ptr=fb.ptr(NR), res_off=fb.ptr(F * NR, np.int64)[:-1].copy(),
-                points=pts.reshape(-1))
-    for k in ("lig", "pocket", "static"):
-        host[k + "_w"] = area_weights(host[k + "_rad"], float(opts.get("probe", DEFAULTS["probe"])), max(n_points, 1))
-    t = {k: torch.as_tensor(v, device=dev) for k, v in host.items()}
-    t["lig_pos"], t["pocket_pos"] = lig_pos, pocket_pos
-    n_frame, n_lrow, n_row = int(F.sum()), int((F * N).sum()), int((F * NR).sum())
+    st = fb.stage(groups, "the surface areas are computed on the GPU only (no CPU path): the poses are on ",
+                  fb.Block(MAX_LIG), fb.Block(MAX_POCKET), _ATOMS,
+                  count=fb.Count("n_res", "res_ptr", MAX_RES, "residue columns", "res_off"))
+    G, dev, n_frame, host = st.G, st.dev, st.n_frame, st.host
+    st.add(points=pts.reshape(-1), **{k + "_w": area_weights(host[k + "_rad"], float(opts.get("probe", DEFAULTS["probe"])), max(n_points, 1))
+                                      for k in ("lig", "pocket", "static")})
+    n_lrow, n_row = int(st.offsets("lig")[-1]), int(st.offsets("n_res")[-1])
     out = dict(lig_free=torch.zeros(n_lrow + 1, dtype=torch.int32, device=dev), lig_bound=torch.zeros(n_lrow + 1, dtype=torch.int32, device=dev),
                res_buried=torch.zeros(n_row + 1, dtype=torch.int32, device=dev),
                totals=torch.zeros(n_frame + 1, 6, dtype=torch.int64, device=dev))
-    order = [f for f, _ in SasaIn._fields_][2:25]
-    mx = lambda a: int(max(a)) if len(a) else 0
-    tail = (n_points, mx(N), mx(M), mx(NR), int(cand_cap))
+    tail = (n_points, fb.top(st.n["lig"]), fb.top(st.n["pocket"]), fb.top(st.n["n_res"]), int(cand_cap))
     cout = SasaOut(*[out[k].data_ptr() for k in ("lig_free", "lig_bound", "res_buried", "totals")])
-    launch = fb.launcher(lib.dbfr_sasa, SasaIn, (G, n_frame), order, tail, t, dev, o, cout, host)
-    loff, roff = fb.ptr(F * N, np.int64), fb.ptr(F * NR, np.int64)
-    res = {k: [out[k][loff[g]:loff[g + 1]].view(int(F[g]), int(N[g])) for g in range(G)] for k in ("lig_free", "lig_bound")}
-    res["res_buried"] = [out["res_buried"][roff[g]:roff[g + 1]].view(int(F[g]), int(NR[g])) for g in range(G)]
-    res["totals"] = out["totals"][:n_frame]
-    res["weights"] = [dict(lig=host["lig_w"][host["lig_ptr"][g]:host["lig_ptr"][g + 1]],
-                           pocket=host["pocket_w"][host["pocket_ptr"][g]:host["pocket_ptr"][g + 1]],
-                           static=host["static_w"][host["static_ptr"][g]:host["static_ptr"][g + 1]]) for g in range(G)]
+    launch = fb.launcher(lib.dbfr_sasa, SasaIn, (G, n_frame), st.order(SasaIn), tail, st.t, dev, o, cout, host)
+    res = dict(lig_free=st.views(out["lig_free"], "lig"), lig_bound=st.views(out["lig_bound"], "lig"),
+               res_buried=st.views(out["res_buried"], "n_res"), totals=out["totals"][:n_frame])
+    res["weights"] = [{k: host[k + "_w"][host[k + "_ptr"][g]:host[k + "_ptr"][g + 1]] for k in ("lig", "pocket", "static")} for g in range(G)]
     return launch, res
 
 

@@ -117,7 +117,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "pack.h"), os.path.join(CSRC, "frames.h"), os.path.join(CSRC, "residue_tables.inc"), os.path.join(HERE, "..", "include", "dbfr.h")]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".inc"))) + [os.path.join(HERE, "..", "include", "dbfr.h")]
     objs, jobs = [], []
     bid = source_hash(dev="-DDBFR_DEV_VARIANTS" in FLAGS)
     stamp = os.path.join(CSRC, ".build_id")
@@ -146,7 +146,8 @@ def build(force=False, verbose=True):
     if any(j[4].endswith("convz.hip") for j in jobs):
         check_m0(hipcc, os.path.join(CSRC, "convz.hip"))
     if jobs or force or _stale(LIB, objs):
-        run([hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", LIB] + objs)
+        # -z defs: a launcher declared in csrc/launch.h whose definition no longer matches (to C++ just another overload) fails the link, not the first call
+        run([hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-Wl,-z,defs", "-o", LIB] + objs)
     return LIB
 
 

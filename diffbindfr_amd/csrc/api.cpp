@@ -6,91 +6,15 @@
 #include <atomic>
 #include <map>
 
-#include "common.h"
+#include "launch.h"   // the kernel files' interface (+ common.h)
 #include "pack.h"
 
-// ---- kernel launchers (conv.hip / graph.hip / heads.hip)
-void launch_conv(const ConvArgs& a, hipStream_t st);
-void launch_conv_layer(const ConvArgs* c4, hipStream_t st);
-void launch_conv2(const Conv2Args& a, hipStream_t st);
-void launch_conv2h(const Conv2Args& a, hipStream_t st);
-void launch_convz(const ConvZArgs& a, hipStream_t st);
-void launch_reduce_ln(const float* msg, const int* row_start, const int* row_cnt, int N, int D, const LNDesc& ln,
-                      const float* old, int D_old, float* out, int ldo, int mode, hipStream_t st, const uint8_t* first = nullptr, unsigned long long sc_lanes = 0);
-struct ReduceLayerArgs {
-  const float* msg[4]; const int* row_start[4]; const int* row_cnt[4]; LNDesc ln[4];
-  int NL, NA, D, D_old;
-  const float* old_l; const float* old_a; float* out_l; float* out_a;
-  const uint8_t* first[4]; unsigned long long sc_lanes[4];   // (conv.hip: DBFR_GEMM_REDUCE_FIRST reads the scalar-output columns of a segment's first row only)
-};
 // the lanes (one float4 of message columns each) that hold the scalar-output columns k_convz writes: 12 per irrep from out_off / 4
 static unsigned long long convz_sc_lanes(const ConvZ& z) {
   unsigned long long m = 0;
   for (int i = 0; i < z.n_io; ++i) m |= 0xfffull << (z.out_off[i] / 4);
   return m;
 }
-void launch_reduce_ln_layer(const ReduceLayerArgs& a, hipStream_t st);
-enum SetKind { SET_LL = 0, SET_AA = 1, SET_AL = 2, SET_LA = 3, SET_TOR = 4, SET_SC = 5, N_SETS = 6 };
-struct GraphArgs {
-  dbfr_batch b;
-  const int* lig_batch; const int* atm_batch; const uint8_t* is_cab; const int* n_cab; const float* tr_sigma;
-  float lig_cut2, atom_cut2, cross_cut2;
-  int lig_cap, atom_cap, dynamic_cross;
-  EdgeSet set[N_SETS];
-  int* err;
-  int step, lds_nl, lds_na, n_chunk, lanes;
-};
-void dbfr_edge_form(const dbfr_batch& b, int* n_chunk, int* lanes);
-void launch_edges(const GraphArgs& A, bool heads_only, hipStream_t st);
-void launch_edge_log(const GraphArgs& A, int* log_row, int stride, hipStream_t st);
-void launch_edge_ties(const GraphArgs& A, int* log_row, int stride, float tol, hipStream_t st);
-void launch_graph_chunks(const GraphArgs& A, hipStream_t st);
-void launch_flat_chunks(const int* tgt, const int* n_edges, int max_edges, int span, int n_span, int* cnt0, int cap, int* chunk_es, int* chunk_gl, hipStream_t st);
-void launch_row_absmax(const float* lx, const int* lig_ptr, float* out_l, const float* ax, const int* atm_ptr, float* out_a, int ld, int D, int G, int n_rows_a, hipStream_t st);
-void launch_batch_vectors(const dbfr_batch& b, int* lig_batch, int* atm_batch, uint8_t* is_cab, int* n_cab,
-                          int* tor_batch, int* sc_batch, hipStream_t st);
-void launch_time_embed(const float* t, int G, float emb_scale, float* temb, hipStream_t st);
-enum MlpIn { IN_LIGNODE = 0, IN_LIGEDGE = 1, IN_TG = 2, IN_G = 3 };
-struct MlpArgs {
-  Mlp2 w; int mode; const int* n_rows_dev; int n_rows_max; const float* temb; const int* row_graph_tab; const int* tgt;
-  const int* aux; const float* dist; const float* bond_feat; int nfeat; const float* lig_node; int nnode;
-  const float* gs_offset; const float* gs_coeff; float* out;
-};
-void launch_mlp(const MlpArgs& a, hipStream_t st);
-struct AtomEncArgs {
-  const float* pocket_feat; const int* atm_batch; const float* temb; const float* emb[5]; int dims[5];
-  const float* lin_t; int NA; float* out;
-};
-void launch_atom_encoder(const AtomEncArgs& a, hipStream_t st);
-void launch_center_edges(const dbfr_batch& b, int* tgt, int* gth, float* dist, float* sh, int* row_start, int* row_cnt,
-                         hipStream_t st);
-struct TrRotArgs {
-  const float* gp; const float* temb; const float* tr_sigma; const float* rot_norm; Mlp2 tr, rot; int G;
-  int scale_by_sigma; float* tr_out; float* rot_out; int* err;
-};
-void launch_trrot(const TrRotArgs& a, hipStream_t st);
-void launch_bond_attr(const float* x, int ldx, const int* b0, const int* b1, const int* bsel, int stride, int n,
-                      float* out, hipStream_t st);
-void launch_tor_final(const float* feat, const Mlp2& w, const float* norm2, int scale, int n, float* out, hipStream_t st);
-struct SdeLigArgs {
-  dbfr_batch b; const float* tr_score; const float* rot_score; const float* tor_score; const float* z_tr;
-  const float* z_rot; const float* z_tor; float dt, tr_g2, tr_gsdt, rot_g2, rot_gsdt, tor_g2, tor_gsdt; float* traj;
-  int* err;
-};
-void launch_sde_ligand(const SdeLigArgs& a, hipStream_t st);
-void launch_sidechain(const dbfr_batch& b, const float* score, const float* z, float dt, float g2, float gsdt,
-                      const int* a14_group, float* atom14_out, float* traj14, const int* err, hipStream_t st);
-void launch_fill(float* p, float v, int n, hipStream_t st);
-void launch_set_int(int* p, int v, hipStream_t st);
-void launch_init_poses(const dbfr_batch& b, const dbfr_init_tape& z, const int* a14_group, float* atom14_out, hipStream_t st);
-void launch_extract_templates(int n_res, const int* aatype, const float* pos14, float* transl, float* rots, float* frames,
-                              float* rigid, float* angle, hipStream_t st);
-void launch_select_pocket(int n_prot, int n_res_total, const int* res_ptr, int m, const float* pos, const float* mask, const int* ref_ptr,
-                          const float* ref, float cut2, int max_neighbors, float* d2, unsigned char* out, hipStream_t st);
-void launch_acc_flops(const int* n_edges, double flops_per_edge, double bytes_per_edge, double fused_bytes_per_edge, double* counter, hipStream_t st);
-void launch_acc_executed(const int* n_edges, double flops_per_edge, double* counter, hipStream_t st);
-struct AccBatch { const int* n[32]; double coef[32]; double* dst[32]; int count; };   // (heads.hip)
-void launch_acc_batch(const AccBatch& b, hipStream_t st);
 // HBM bytes per edge of the FUSED conv (what the kernels of this library have to move): edge record (48 embedding floats, 9 harmonics,
 // 3 indices), two gathered 48-float rows for the radial MLP, the gathered D_in-float input row, the D_out-float message
 static inline double fused_bytes(int D_in, int D_out) { return 4.0 * (48 + 9 + 3 + 48 + 48 + D_in + D_out); }
@@ -533,8 +457,9 @@ static int plan(const dbfr_model* m, const dbfr_batch* B, const dbfr_limits* lim
 static int check_batch(const dbfr_model* m, const dbfr_batch* B) {
   if (!m || !B) return fail(DBFR_ERR_ARG, "null argument");
   if (B->G <= 0 || B->NL <= 0 || B->NA <= 0 || B->NR <= 0) return fail(DBFR_ERR_ARG, "empty batch");
-  if (B->max_nl > 256) return fail(DBFR_ERR_ARG, "ligand with more than 256 heavy atoms is not supported");
-  if (B->max_na > 8192) return fail(DBFR_ERR_ARG, "pocket with more than 8192 heavy atoms is not supported");
+  static_assert(MAX_NL == 256 && MAX_NA == 8192, "the two messages below spell the limits of launch.h out");
+  if (B->max_nl > MAX_NL) return fail(DBFR_ERR_ARG, "ligand with more than 256 heavy atoms is not supported");
+  if (B->max_na > MAX_NA) return fail(DBFR_ERR_ARG, "pocket with more than 8192 heavy atoms is not supported");
   if (B->max_nl <= 0 || B->max_na <= 0 || B->max_nr <= 0) return fail(DBFR_ERR_ARG, "max_nl/max_na/max_nr must be set");
   return DBFR_OK;
 }

@@ -16,6 +16,15 @@
 #define EDGE_CHUNK 64   // targets per workgroup of the edge builder (graph.hip: k_edges), 4 lanes each
 int dbfr_edge_chunks(int max_na, int max_nl);   // workgroups per (graph, edge set): sizes EdgeSet::g_cnt / g_base
 
+// register vectors: MFMA operands and accumulators, 8- and 16-byte memory accesses
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
 // kernel-side tensor-product path types: closed forms of the real Wigner-3j tensors
 enum PathType { PT_SS = 0, PT_SV = 1, PT_VS = 2, PT_VVS = 3, PT_VVV = 4, PT_VTV = 5 };
 

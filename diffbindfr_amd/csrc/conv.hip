@@ -30,7 +30,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.h"
+#include "launch.h"
 
 #ifndef CONV_PRIO
 #define CONV_PRIO 0
@@ -42,8 +42,6 @@
 #define CONV_NB2_WAVES 2     // developer: 3 = three 32-edge workgroups per CU (needs <= 168 VGPRs)
 #endif
 #define XS_LD (MAXD + 4)   // 172: rows 16-B aligned (ds_read_b128), 16 consecutive rows hit 16 distinct 16-B slots
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #define TRACE_BLOCKS 1024
 #define TRACE_TILES 48
@@ -608,13 +606,7 @@ void launch_reduce_ln(const float* msg, const int* row_start, const int* row_cnt
 // The four reductions of an interaction layer in ONE launch (used behind the fused k_conv2 layer launch, where every
 // conv has its own message buffer): per ligand node  out = (pad(old) + LN_ll(mean ll)) + LN_al(mean al), per pocket atom
 // out = (pad(old) + LN_aa(mean aa)) + LN_la(mean la) -- the very operation order of the mode 0 / mode 1 launch pair.
-struct ReduceLayerArgs {
-  const float* msg[4]; const int* row_start[4]; const int* row_cnt[4]; LNDesc ln[4];   // ll, al, aa, la
-  int NL, NA, D, D_old;
-  const float* old_l; const float* old_a; float* out_l; float* out_a;
-  const uint8_t* first[4]; unsigned long long sc_lanes[4];   // DBFR_GEMM_REDUCE_FIRST: the segment-start flags of the four edge sets and the lanes of scalar-output columns (row_sum), else null / 0
-};
-
+// (ReduceLayerArgs: launch.h)
 __device__ __forceinline__ void mean_ln(const float* __restrict__ msg, int rs, int rc, int D, const LNDesc& ln, float* bw, int lane, const uint8_t* first, unsigned long long sc_lanes) {
   const int d4 = D >> 2;
   const f32x4 acc = row_sum(msg, rs, rc, D, lane, first, sc_lanes);

@@ -25,9 +25,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "launch.h"
 
 #define C2_XLD 124                                   // LDS x row: 120 floats + 4 (odd multiple of 4: 16 rows -> 16 distinct 16-B slots)
 #define C2_WAVE_FLOATS (32 * C2_XLD + 32 * 10 + 32 * 8 + 32)   // x rows | harmonics | l=2 matrix | gather indices

@@ -37,15 +37,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "launch.h"
 
 #define CH_TILE_BYTES 9280          // W1h tile format of conv2h.hip
 #define CH_TAIL_OFF 8192

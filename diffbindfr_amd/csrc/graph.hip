@@ -14,32 +14,7 @@
 //   k_edges_count -> k_edges_scan (per set, one block) -> k_edges_fill.
 // torch_cluster semantics reproduced: strict d^2 < r^2, "first max_num_neighbors by index" per query,
 // radius_graph queries max+1 then drops the self loop.
-#include "common.h"
-
-#define MAX_NL 256      // per-graph ligand atoms (the ligand kernels of heads.hip keep a conformer in static LDS)
-#define MAX_NA 8192     // per-graph pocket atoms: the graph's coordinates are staged in dynamic LDS sized by the batch's
-                        // largest graph (16 B per atom, 128 KB of the CU's 160 KB at the limit)
-
-enum SetKind { SET_LL = 0, SET_AA = 1, SET_AL = 2, SET_LA = 3, SET_TOR = 4, SET_SC = 5, N_SETS = 6 };
-
-struct GraphArgs {
-  dbfr_batch b;
-  const int* lig_batch;   // [NL]
-  const int* atm_batch;   // [NA]
-  const uint8_t* is_cab;  // [NA]
-  const int* n_cab;       // [G]
-  const float* tr_sigma;  // [G]
-  float lig_cut2, atom_cut2, cross_cut2;
-  int lig_cap, atom_cap, dynamic_cross;
-  EdgeSet set[N_SETS];
-  int* err;               // device status block: [0] status bits, [1] first step (+1) whose edge lists overflowed,
-                          // [2+k] set k overflowed in THIS step, [8+k] largest edge count seen for set k
-  int step;               // sampler step index (0 for dbfr_score)
-  int lds_nl, lds_na;     // LDS staging capacities (>= max_nl / max_na of the batch)
-  int n_chunk;            // EDGE_CHUNK-target chunks per graph every set is split into (own workgroup each)
-  int lanes;              // lanes per target of the edge builder (1 | 4); n_chunk and lanes are chosen ONCE per call (dbfr_edge_form) and
-                          // shared by every launcher below: the g_cnt / g_base layout depends on both
-};
+#include "launch.h"   // MAX_NL, MAX_NA, SetKind, GraphArgs, MlpIn, MlpArgs, AtomEncArgs
 
 __device__ __forceinline__ float d2_rn(float ax, float ay, float az, float bx, float by, float bz) {
   // ((dx*dx + dy*dy) + dz*dz) with every op rounded (no fma contraction): the oracle's order
@@ -764,27 +739,7 @@ void launch_time_embed(const float* t, int G, float emb_scale, float* temb, hipS
 //   IN_LIGEDGE : [bond_feat(10) or 0 | temb[g] | gauss]  rows = edges of the ligand set
 //   IN_TG      : [temb[g] | gauss]                       rows = edges (atom / cross / centre sets)
 //   IN_G       : [gauss]                                 rows = edges (pseudotorque sets)
-enum MlpIn { IN_LIGNODE = 0, IN_LIGEDGE = 1, IN_TG = 2, IN_G = 3 };
-
-struct MlpArgs {
-  Mlp2 w;
-  int mode;
-  const int* n_rows_dev;   // device row count (edges) or null
-  int n_rows_max;
-  const float* temb;       // [G][EMB]
-  const int* row_graph_tab;  // batch vector indexed by tgt (edges) or by row (nodes)
-  const int* tgt;          // per-edge target (graph lookup) or null
-  const int* aux;          // bond index per edge (IN_LIGEDGE)
-  const float* dist;       // per-edge distance
-  const float* bond_feat;  // [EB][nfeat]
-  int nfeat;
-  const float* lig_node;   // [NL][nfeat_node]
-  int nnode;
-  const float* gs_offset;  // [EMB] GaussianSmearing buffers
-  const float* gs_coeff;   // [1]
-  float* out;              // [rows][NS]
-};
-
+// (MlpIn, MlpArgs: launch.h)
 #define MLP_ROWS 64
 #define MLP_MAXIN 80
 
@@ -810,7 +765,6 @@ __global__ __launch_bounds__(256, KS == 0 ? 2 : KS > 16 ? 3 : 4) void k_mlp(MlpA
   const int nrows = a.n_rows_dev ? min(*a.n_rows_dev, a.n_rows_max) : a.n_rows_max;
   if ((int)blockIdx.x * MLP_ROWS >= nrows) return;
   const int in = a.w.in;
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
   const int row = 16 * wave + n;
   // zero padding of the reduction dim to a multiple of 4 (MFMA k-step)
@@ -944,18 +898,7 @@ void launch_mlp(const MlpArgs& a, hipStream_t st) {
 }
 
 // AtomEncoder (equibind_encoder.py:68-88): sum of 5 categorical embeddings, then
-// x += Linear_nobias([x | temb[g]])   (scalar_dim = 0 + sigma_embed_dim)
-struct AtomEncArgs {
-  const float* pocket_feat;  // [NA][5]
-  const int* atm_batch;
-  const float* temb;
-  const float* emb[5];       // [dim_i][NS]
-  int dims[5];
-  const float* lin_t;        // [NS+EMB][NS] transposed scalar_lin.weight
-  int NA;
-  float* out;                // [NA][NS]
-};
-
+// x += Linear_nobias([x | temb[g]])   (scalar_dim = 0 + sigma_embed_dim; AtomEncArgs: launch.h)
 __global__ __launch_bounds__(256) void k_atom_encoder(AtomEncArgs a) {
   __shared__ float w[(NS + EMB) * NS];
   __shared__ float x[16][NS + EMB];

@@ -6,9 +6,7 @@
 //   Euler-Maruyama perturbations                                         scFlex.py:154-183,197-205
 //   update_batchlig_pos -> modify_conformer (+Kabsch)                    conformer_utils.py:305-355,420-473
 //   chi update + build_pdb_from_template                                 scFlex.py:207-226; aaframe.py:778-994
-#include "common.h"
-
-#define MAX_NL 256
+#include "launch.h"   // MAX_NL, TrRotArgs, SdeLigArgs, AccBatch
 
 __device__ __forceinline__ void vec_sh9(float vx, float vy, float vz, float* sh9, float* dist) {
   float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
@@ -47,12 +45,7 @@ void launch_center_edges(const dbfr_batch& b, int* tgt, int* gth, float* dist, f
   hipLaunchKernelGGL(k_center_edges, dim3(b.G), dim3(64), 0, st, b, tgt, gth, dist, sh, row_start, row_cnt);
 }
 
-// tr / rot heads: global_pred[G][12] = [1o_a 1o_b 1e_a 1e_b]
-struct TrRotArgs {
-  const float* gp; const float* temb; const float* tr_sigma; const float* rot_norm;
-  Mlp2 tr, rot; int G; int scale_by_sigma; float* tr_out; float* rot_out; int* err;
-};
-
+// tr / rot heads: global_pred[G][12] = [1o_a 1o_b 1e_a 1e_b]   (TrRotArgs: launch.h)
 // One hidden unit of the head MLP (tpscore.py:529-546: Linear(1 + 32 -> ns) - ReLU - Linear(ns -> 1)), times its output weight.
 __device__ __forceinline__ float head_hidden(const Mlp2& w, int h, float nrm, const float* temb) {
   float a = w.b0 ? w.b0[h] : 0.f;
@@ -207,15 +200,6 @@ __device__ double kabsch_rotation(const double* Hin, double* R) {
   if (det < 0) det = build(-1.0);
   return det;
 }
-
-struct SdeLigArgs {
-  dbfr_batch b;
-  const float* tr_score; const float* rot_score; const float* tor_score;
-  const float* z_tr; const float* z_rot; const float* z_tor;     // this step's slices
-  float dt, tr_g2, tr_gsdt, rot_g2, rot_gsdt, tor_g2, tor_gsdt;
-  float* traj;   // [NL,3] slice or null
-  int* err;
-};
 
 __device__ __forceinline__ float perturb(float g2, float score, float dt, float gsdt, float z) {
   return __fadd_rn(__fmul_rn(__fmul_rn(g2, score), dt), __fmul_rn(gsdt, z));
@@ -670,7 +654,6 @@ void launch_acc_executed(const int* n_edges, double flops_per_edge, double* coun
 }
 // (profiling) all the counter updates of one conv launch in ONE kernel: a launch per update was 66 one-thread launches per denoise step, ~1 % of the
 // step the profile is taken of
-struct AccBatch { const int* n[32]; double coef[32]; double* dst[32]; int count; };
 __global__ void k_acc_batch(AccBatch b) {
   const int i = threadIdx.x;
   if (i < b.count) atomicAdd(b.dst[i], b.coef[i] * (double)*b.n[i]);

@@ -8,10 +8,6 @@
 
 #include "common.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ unsigned probe_mix(unsigned h) { h ^= h >> 15; h *= 0x2c1b3c6du; h ^= h >> 12; h *= 0x297a2d39u; h ^= h >> 15; return h; }
 __device__ __forceinline__ f16x8 probe_rnd(unsigned seed) {          // +-[0.5, 2) with random significands
   u32x4 v;

@@ -332,6 +332,44 @@ def test_device_residue_tables_match_host_tables():
     assert res3 == [str(a) for a in T["restype_names3"]]
 
 
+def test_score_network_kernel_interface_is_declared_once():
+    """csrc/launch.h is the ONLY place that defines the score network's kernel-argument structs, their enums and the per-graph
+    limits, and the only place with a launcher prototype: the host fills the struct the kernel reads, and every launch_*
+    definition is compiled against the declaration its caller sees (the link's -z defs turns a mismatch into a build error)."""
+    csrc = os.path.join(ROOT, "diffbindfr_amd", "csrc")
+    text = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".cpp", ".hip", ".h", ".inc")):
+            s = open(os.path.join(csrc, f)).read()
+            text[f] = re.sub(r"//[^\n]*|/\*.*?\*/", "", s, flags=re.S)     # comments may name what they like
+    assert "launch.h" in text
+    defs = {n: r"\bstruct\s+%s\s*\{" % n for n in ("ReduceLayerArgs", "GraphArgs", "MlpArgs", "AtomEncArgs", "TrRotArgs", "SdeLigArgs", "AccBatch")}
+    defs.update({n: r"\benum\s+%s\s*\{" % n for n in ("SetKind", "MlpIn")})
+    defs.update({n: r"#\s*define\s+%s\b" % n for n in ("MAX_NL", "MAX_NA")})
+    for name, pat in defs.items():
+        where = [f for f, s in text.items() for _ in re.finditer(pat, s)]
+        assert where == ["launch.h"], (name, where)
+
+    def prototypes(s):
+        """launch_* declarations without a body: `<type> launch_x(...)` whose closing parenthesis is followed by `;`"""
+        out = []
+        for m in re.finditer(r"^[ \t]*(?:(?:static|inline|extern)\s+)*([A-Za-z_][\w:]*)[\s*&]+(launch_\w+)\s*\(", s, flags=re.M):
+            if m.group(1) in ("return", "else", "do", "case", "goto", "throw", "new", "delete"):
+                continue                                                  # a call, not a declaration
+            depth, i = 1, m.end()
+            while depth and i < len(s):
+                depth += {"(": 1, ")": -1}.get(s[i], 0)
+                i += 1
+            if s[i:].lstrip()[:1] == ";":
+                out.append(m.group(2))
+        return out
+
+    assert len(prototypes(text["launch.h"])) >= 30                       # the scan does see prototypes
+    assert len(set(prototypes(text["launch.h"]))) == len(prototypes(text["launch.h"]))
+    stray = {f: p for f, s in text.items() if f != "launch.h" for p in [prototypes(s)] if p}
+    assert not stray, stray
+
+
 def test_f1_f2_entry_points_have_no_cpu_path():
     from diffbindfr_amd import assemble, pocket
     z = np.load(os.path.join(ROOT, "tests", "golden", "pocket.npz"))

@@ -381,7 +381,7 @@ def evaluate_launcher(pairs, groups, **opts):
                sc_sq_sum=z(n_frame, torch.float32), sc_n=z(n_frame, torch.int32), chi=z(4 * n_row, torch.float32),
                altchi=z(2 * n_row, torch.float32), dchi=z(4 * n_row, torch.float32), plddt_num=z(n_row, torch.int32),
                lddt_num=z(n_frame, torch.int32))
-    order = [f for f, _ in HoloMetricsIn._fields_][2:25]
+    order = L.pointer_fields(HoloMetricsIn)
     tail = (fb.top(S), fb.top(R), max(fb.top(N), fb.top(H)))
     cout = HoloMetricsOut(*[out[k].data_ptr() for k, _ in HoloMetricsOut._fields_])
     # (once=False: dbfr_holo_metrics takes its site count from the host copies at every launch)

@@ -7,8 +7,6 @@ the small functions.  What a module checks of its own inputs stays with the modu
 ``export.ComplexOutput`` entries before they stage a batch (receptor, ligand frames, frame rows) is entries.py."""
 import ctypes as C
 from collections import namedtuple
-from functools import lru_cache
-from itertools import takewhile
 from types import SimpleNamespace
 
 import numpy as np
@@ -84,11 +82,6 @@ NULL = SimpleNamespace(data_ptr=lambda: None)                                 # 
 _SIDE = dict(lig="ligand", pocket="pocket", static="static", het="hetero")
 
 
-@lru_cache(maxsize=None)
-def _pointer_fields(In):
-    return [f for f, _ in takewhile(lambda f: f[1] is C.c_void_p, In._fields_[2:])]
-
-
 def _rows(gr, col):
     v = gr.get(col.field)
     a = np.asarray(np.zeros(0) if v is None else v, col.dtype)
@@ -126,7 +119,7 @@ class Staged:
     def order(self, In):
         """The pointer fields of the input struct in order -- everything between the two leading ints and the trailing ints --, all
         of which must have been staged."""
-        names = _pointer_fields(In)
+        names = L.pointer_fields(In)
         assert self.t.keys() >= set(names), f"{In.__name__}: {set(names) - self.t.keys()} not staged"
         return names
 

@@ -2,6 +2,8 @@
 library is missing: there is no CPU fallback in the product path."""
 import ctypes as C
 import os
+from functools import lru_cache
+from itertools import takewhile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DBFR_LIB") or os.path.join(HERE, "libdbfr.so")      # DBFR_LIB: developer override (kernel variants)
@@ -315,23 +317,138 @@ class SitesOut(C.Structure):
                                   "burial", "labels")]
 
 
-# every symbol include/dbfr.h declares (tests check that the library exports all of them)
-SYMBOLS = ["dbfr_model_create", "dbfr_model_destroy", "dbfr_model_set_edge_log", "dbfr_model_set_tie_log", "dbfr_model_fallback_convs", "dbfr_model_rowscaled_convs", "dbfr_model_set_gemm", "dbfr_model_get_gemm", "dbfr_workspace_bytes", "dbfr_score", "dbfr_sample",
-           "dbfr_sample_range", "dbfr_capacity_report",
-           "dbfr_init_poses", "dbfr_extract_templates", "dbfr_status_sync", "dbfr_abi_version", "dbfr_build_id", "dbfr_last_error", "dbfr_wigner3j", "dbfr_conv_paths", "dbfr_test_pack_f16_tiles", "dbfr_test_pack_f16_rows", "dbfr_test_chunk_table", "dbfr_test_pack_f16_depth", "dbfr_test_pack_conv", "dbfr_probe_mfma_f16",
-           "dbfr_profile_enable", "dbfr_profile_read", "dbfr_profile_fused_bytes", "dbfr_profile_executed_flops", "dbfr_profile_useful_flops", "dbfr_workspace_layout", "dbfr_test_conv", "dbfr_test_conv2", "dbfr_test_reduce_ln", "dbfr_test_reduce_ln2", "dbfr_test_sde_step",
-           "dbfr_test_time_embed", "dbfr_test_mlp", "dbfr_test_atom_encoder", "dbfr_test_reduce_ln_layer", "dbfr_test_center_edges", "dbfr_test_trrot", "dbfr_test_bond_attr", "dbfr_test_tor_final",
-           "dbfr_pose_metrics", "dbfr_pdb_format", "dbfr_pdb_write_files", "dbfr_select_pocket", "dbfr_sdf_format",
-           "dbfr_sdf_write_files", "dbfr_mdn_model_create", "dbfr_mdn_model_destroy", "dbfr_mdn_workspace_bytes", "dbfr_mdn_forward", "dbfr_mdn_pocket_features",
-           "dbfr_vina_workspace_bytes", "dbfr_vina_score", "dbfr_vina_score_at", "dbfr_vina_minimize",
-           "dbfr_vina_flex_workspace_bytes", "dbfr_vina_flex_score_at", "dbfr_vina_flex_minimize",
-           "dbfr_vina_search_workspace_bytes", "dbfr_vina_search", "dbfr_test_philox4x32", "dbfr_test_vina_mutation",
-           "dbfr_vina_flex_search_workspace_bytes", "dbfr_vina_flex_search",
-           "dbfr_pose_rmsd_matrix", "dbfr_select_modes", "dbfr_pose_check",
-           "dbfr_pdb_atom_map", "dbfr_complex_pdb_format", "dbfr_complex_pdb_write_files", "dbfr_xtc_workspace_bytes", "dbfr_xtc_encode",
-           "dbfr_sites_workspace_bytes", "dbfr_find_sites", "dbfr_interactions", "dbfr_pocket_check", "dbfr_sasa",
-           "dbfr_seq_align", "dbfr_holo_site", "dbfr_holo_metrics", "dbfr_hetero_check", "dbfr_hydrogens", "dbfr_vina_decompose",
-           "dbfr_pose_cavity_workspace_bytes", "dbfr_pose_cavity"]
+# every typedef struct of include/dbfr.h -> its mirror above (tests/test_abi_host.py compares names, order, kinds, sizes and offsets)
+STRUCTS = {
+    "dbfr_model_cfg": ModelCfg, "dbfr_tensor": Tensor, "dbfr_batch": Batch, "dbfr_limits": Limits, "dbfr_cond": Cond,
+    "dbfr_scores": Scores, "dbfr_step": Step, "dbfr_noise": Noise, "dbfr_init_tape": InitTape,
+    "dbfr_pose_metrics_in": PoseMetricsIn, "dbfr_pose_metrics_out": PoseMetricsOut, "dbfr_pdb_topology": PdbTopology,
+    "dbfr_pdb_ligand": PdbLigand, "dbfr_sdf_template": SdfTemplate, "dbfr_mdn_batch": MdnBatch,
+    "dbfr_vina_in": VinaIn, "dbfr_vina_opts": VinaOpts, "dbfr_vina_search_opts": VinaSearchOpts, "dbfr_vina_flex_in": VinaFlexIn,
+    "dbfr_pose_rmsd_in": PoseRmsdIn, "dbfr_modes_opts": ModesOpts,
+    "dbfr_pose_check_in": PoseCheckIn, "dbfr_pose_check_opts": PoseCheckOpts, "dbfr_pose_check_out": PoseCheckOut,
+    "dbfr_interactions_in": InteractionsIn, "dbfr_interactions_opts": InteractionsOpts, "dbfr_interactions_out": InteractionsOut,
+    "dbfr_pocket_check_in": PocketCheckIn, "dbfr_pocket_check_opts": PocketCheckOpts, "dbfr_pocket_check_out": PocketCheckOut,
+    "dbfr_sasa_in": SasaIn, "dbfr_sasa_opts": SasaOpts, "dbfr_sasa_out": SasaOut,
+    "dbfr_cavity_in": CavityIn, "dbfr_cavity_opts": CavityOpts, "dbfr_cavity_out": CavityOut,
+    "dbfr_holo_site_in": HoloSiteIn, "dbfr_holo_metrics_in": HoloMetricsIn, "dbfr_holo_metrics_opts": HoloMetricsOpts,
+    "dbfr_holo_metrics_out": HoloMetricsOut,
+    "dbfr_hetero_check_in": HeteroCheckIn, "dbfr_hetero_check_opts": HeteroCheckOpts, "dbfr_hetero_check_out": HeteroCheckOut,
+    "dbfr_hydrogens_in": HydrogensIn, "dbfr_hydrogens_opts": HydrogensOpts, "dbfr_hydrogens_out": HydrogensOut,
+    "dbfr_vina_decompose_in": VinaDecomposeIn, "dbfr_vina_decompose_opts": VinaDecomposeOpts,
+    "dbfr_vina_decompose_out": VinaDecomposeOut,
+    "dbfr_xtc_in": XtcIn, "dbfr_xtc_opts": XtcOpts, "dbfr_sites_opts": SitesOpts, "dbfr_sites_in": SitesIn, "dbfr_sites_out": SitesOut,
+}
+
+P, i64, u64, f64, sz, cp = C.POINTER, C.c_int64, C.c_uint64, C.c_double, C.c_size_t, C.c_char_p
+_TEST_CONV = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp]
+
+# every function of include/dbfr.h -> its argtypes (the same test compares arity, scalar kinds and struct-pointer targets)
+PROTOTYPES = {
+    "dbfr_abi_version": [],
+    "dbfr_build_id": [],
+    "dbfr_last_error": [],
+    "dbfr_model_create": [P(ModelCfg), P(Tensor), i32, P(vp)],
+    "dbfr_model_destroy": [vp],
+    "dbfr_model_set_edge_log": [vp, vp, i32, i32],
+    "dbfr_model_set_tie_log": [vp, vp, i32, i32, f32],
+    "dbfr_model_fallback_convs": [vp, cp, sz],
+    "dbfr_model_rowscaled_convs": [vp, cp, sz],
+    "dbfr_model_set_gemm": [vp, i32],
+    "dbfr_model_get_gemm": [vp],
+    "dbfr_workspace_bytes": [vp, P(Batch), P(Limits), P(sz)],
+    "dbfr_score": [vp, P(Batch), P(Cond), P(Scores), vp, sz, P(Limits), vp],
+    "dbfr_sample": [vp, P(Batch), P(Step), i32, P(Noise), vp, vp, vp, vp, sz, P(Limits), vp],
+    "dbfr_sample_range": [vp, P(Batch), P(Step), i32, i32, P(Noise), vp, vp, vp, vp, sz, P(Limits), vp],
+    "dbfr_capacity_report": [vp, vp, P(i32), P(i64)],
+    "dbfr_init_poses": [vp, P(Batch), P(InitTape), vp, vp],
+    "dbfr_extract_templates": [i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "dbfr_status_sync": [vp, vp, P(i64)],
+    "dbfr_wigner3j": [i32, i32, i32, P(f64)],
+    "dbfr_conv_paths": [i32, P(i32), i32, P(i32)],
+    "dbfr_test_pack_f16_tiles": [vp, vp, i32, vp, P(i32)],
+    "dbfr_test_pack_f16_depth": [vp, vp, i32, P(i32), P(i32)],
+    "dbfr_test_pack_f16_rows": [vp, vp, i32, vp, P(i32), vp, P(i32)],
+    "dbfr_test_pack_conv": [i32, vp, i32, vp, vp, i32, cp, sz, P(i32)],
+    "dbfr_test_chunk_table": [vp, vp, i32, i32, vp, i32, vp, vp, vp],
+    "dbfr_probe_mfma_f16": [f64, P(f64), vp],
+    "dbfr_profile_enable": [vp, i32],
+    "dbfr_profile_fused_bytes": [vp, P(f64)],
+    "dbfr_profile_executed_flops": [vp, P(f64)],
+    "dbfr_profile_useful_flops": [vp, P(f64), P(f64)],
+    "dbfr_profile_read": [vp, P(f64), P(i64), P(f64), P(f64), i32],
+    "dbfr_workspace_layout": [vp, P(Batch), P(Limits), cp, sz, P(sz), P(sz), i32],
+    "dbfr_test_conv": _TEST_CONV,
+    "dbfr_test_conv2": _TEST_CONV,
+    "dbfr_test_reduce_ln": [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp],
+    "dbfr_test_reduce_ln2": [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp],
+    "dbfr_test_sde_step": [vp, P(Batch), P(Step), P(Scores), P(Noise), vp, vp, vp],
+    "dbfr_test_time_embed": [vp, vp, i32, vp, vp],
+    "dbfr_test_mlp": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+    "dbfr_test_atom_encoder": [vp, vp, vp, vp, i32, vp, vp],
+    "dbfr_test_reduce_ln_layer": [vp, i32, P(vp), P(vp), P(vp), P(vp), i32, i32, vp, vp, vp, vp, vp],
+    "dbfr_test_center_edges": [P(Batch), vp, vp, vp, vp, vp, vp, vp],
+    "dbfr_test_trrot": [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "dbfr_test_bond_attr": [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp],
+    "dbfr_test_tor_final": [vp, i32, vp, vp, i32, vp, vp],
+    "dbfr_select_pocket": [i32, i32, vp, i32, vp, vp, vp, vp, f64, i32, vp, vp, vp],
+    "dbfr_pose_metrics": [P(PoseMetricsIn), P(PoseMetricsOut), vp],
+    "dbfr_pdb_format": [P(PdbTopology), i32, vp, vp, i32, i32, vp, i64],
+    "dbfr_pdb_write_files": [P(PdbTopology), i32, vp, vp, i32, P(cp), i32],
+    "dbfr_sdf_format": [P(SdfTemplate), vp, vp, i64],
+    "dbfr_sdf_write_files": [P(SdfTemplate), vp, i32, P(cp), i32],
+    "dbfr_mdn_model_create": [P(Tensor), i32, P(vp)],
+    "dbfr_mdn_model_destroy": [vp],
+    "dbfr_mdn_workspace_bytes": [P(MdnBatch), P(sz)],
+    "dbfr_mdn_pocket_features": [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+    "dbfr_mdn_forward": [vp, P(MdnBatch), vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_workspace_bytes": [P(VinaIn), P(sz)],
+    "dbfr_vina_score": [P(VinaIn), vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_score_at": [P(VinaIn), vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_minimize": [P(VinaIn), P(VinaOpts), vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_flex_workspace_bytes": [P(VinaFlexIn), P(sz)],
+    "dbfr_vina_flex_score_at": [P(VinaFlexIn), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_flex_minimize": [P(VinaFlexIn), P(VinaOpts), vp, vp, vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_search_workspace_bytes": [P(VinaIn), i32, P(sz)],
+    "dbfr_vina_search": [P(VinaIn), P(VinaOpts), P(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "dbfr_vina_flex_search_workspace_bytes": [P(VinaFlexIn), i32, P(sz)],
+    "dbfr_vina_flex_search": [P(VinaFlexIn), P(VinaOpts), P(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp],
+    "dbfr_test_philox4x32": [P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)],
+    "dbfr_test_vina_mutation": [u64, i64, i32, i32, i32, f32, f32, P(i32), P(f32)],
+    "dbfr_pose_rmsd_matrix": [P(PoseRmsdIn), vp, vp],
+    "dbfr_select_modes": [P(PoseRmsdIn), vp, vp, P(ModesOpts), vp, vp, vp, vp],
+    "dbfr_pose_check": [P(PoseCheckIn), P(PoseCheckOpts), P(PoseCheckOut), vp],
+    "dbfr_pdb_atom_map": [P(PdbTopology), i32, vp, vp, vp, i64, P(i64)],
+    "dbfr_complex_pdb_format": [P(PdbTopology), i32, vp, vp, P(PdbLigand), vp, vp, i64],
+    "dbfr_complex_pdb_write_files": [P(PdbTopology), i32, vp, vp, P(PdbLigand), vp, i32, P(cp), i32],
+    "dbfr_xtc_workspace_bytes": [P(XtcIn), P(sz), P(i64)],
+    "dbfr_xtc_encode": [P(XtcIn), P(XtcOpts), vp, i64, vp, vp, sz, vp],
+    "dbfr_sites_workspace_bytes": [P(SitesIn), P(sz)],
+    "dbfr_find_sites": [P(SitesIn), P(SitesOpts), P(SitesOut), vp, sz, vp],
+    "dbfr_interactions": [P(InteractionsIn), P(InteractionsOpts), P(InteractionsOut), vp],
+    "dbfr_pocket_check": [P(PocketCheckIn), P(PocketCheckOpts), P(PocketCheckOut), vp],
+    "dbfr_sasa": [P(SasaIn), P(SasaOpts), P(SasaOut), vp],
+    "dbfr_seq_align": [i32, vp, vp, vp, vp, vp, vp, i32],
+    "dbfr_holo_site": [P(HoloSiteIn), vp, vp],
+    "dbfr_holo_metrics": [P(HoloMetricsIn), P(HoloMetricsOpts), P(HoloMetricsOut), vp],
+    "dbfr_hetero_check": [P(HeteroCheckIn), P(HeteroCheckOpts), P(HeteroCheckOut), vp],
+    "dbfr_hydrogens": [P(HydrogensIn), P(HydrogensOpts), P(HydrogensOut), vp],
+    "dbfr_vina_decompose": [P(VinaDecomposeIn), P(VinaDecomposeOpts), P(VinaDecomposeOut), vp],
+    "dbfr_pose_cavity_workspace_bytes": [P(CavityIn), P(sz)],
+    "dbfr_pose_cavity": [P(CavityIn), P(CavityOpts), P(CavityOut), vp],
+}
+# the return types that are not int
+RESTYPES = {"dbfr_last_error": cp, "dbfr_build_id": cp, "dbfr_model_destroy": None, "dbfr_mdn_model_destroy": None,
+            "dbfr_pdb_format": i64, "dbfr_sdf_format": i64, "dbfr_pdb_atom_map": i64, "dbfr_complex_pdb_format": i64}
+SYMBOLS = list(PROTOTYPES)
+ABI_VERSION = 8                 # DBFR_ABI_VERSION
+
+
+@lru_cache(maxsize=None)
+def pointer_fields(cls, skip=2):
+    """The run of pointer (c_void_p) fields behind the first `skip` fields of a struct: the arrays of an input struct, between its
+    leading counts (or VinaFlexIn's `base`, skip=1) and its trailing ints."""
+    return [f for f, _ in takewhile(lambda f: f[1] is C.c_void_p, cls._fields_[skip:])]
+
 
 _lib = None
 
@@ -349,112 +466,12 @@ def load():
         raise DbfrError(f"{LIB_PATH} is missing: build the HIP library first "
                         f"(python -m diffbindfr_amd.build). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    lib.dbfr_last_error.restype = C.c_char_p
-    lib.dbfr_build_id.restype = C.c_char_p
-    lib.dbfr_model_create.argtypes = [C.POINTER(ModelCfg), C.POINTER(Tensor), i32, C.POINTER(vp)]
-    lib.dbfr_model_destroy.argtypes = [vp]
-    lib.dbfr_model_destroy.restype = None
-    lib.dbfr_model_set_edge_log.argtypes = [vp, vp, i32, i32]
-    lib.dbfr_model_set_tie_log.argtypes = [vp, vp, i32, i32, C.c_float]
-    lib.dbfr_model_fallback_convs.argtypes = [vp, C.c_char_p, C.c_size_t]
-    lib.dbfr_model_rowscaled_convs.argtypes = [vp, C.c_char_p, C.c_size_t]
-    lib.dbfr_model_set_gemm.argtypes = [vp, i32]
-    lib.dbfr_model_get_gemm.argtypes = [vp]
-    lib.dbfr_workspace_bytes.argtypes = [vp, C.POINTER(Batch), C.POINTER(Limits), C.POINTER(C.c_size_t)]
-    lib.dbfr_score.argtypes = [vp, C.POINTER(Batch), C.POINTER(Cond), C.POINTER(Scores), vp, C.c_size_t,
-                               C.POINTER(Limits), vp]
-    lib.dbfr_sample.argtypes = [vp, C.POINTER(Batch), C.POINTER(Step), i32, C.POINTER(Noise), vp, vp, vp, vp,
-                                C.c_size_t, C.POINTER(Limits), vp]
-    lib.dbfr_sample_range.argtypes = [vp, C.POINTER(Batch), C.POINTER(Step), i32, i32, C.POINTER(Noise), vp, vp, vp, vp,
-                                      C.c_size_t, C.POINTER(Limits), vp]
-    lib.dbfr_capacity_report.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(C.c_int64)]
-    lib.dbfr_init_poses.argtypes = [vp, C.POINTER(Batch), C.POINTER(InitTape), vp, vp]
-    lib.dbfr_extract_templates.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.dbfr_status_sync.argtypes = [vp, vp, C.POINTER(C.c_int64)]
-    lib.dbfr_wigner3j.argtypes = [i32, i32, i32, C.POINTER(C.c_double)]
-    lib.dbfr_conv_paths.argtypes = [i32, C.POINTER(i32), i32, C.POINTER(i32)]
-    lib.dbfr_test_pack_f16_tiles.argtypes = [vp, vp, i32, vp, C.POINTER(i32)]
-    lib.dbfr_test_pack_f16_depth.argtypes = [vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.dbfr_test_pack_f16_rows.argtypes = [vp, vp, i32, vp, C.POINTER(i32), vp, C.POINTER(i32)]
-    lib.dbfr_test_pack_conv.argtypes = [i32, vp, i32, vp, vp, i32, C.c_char_p, C.c_size_t, C.POINTER(i32)]
-    lib.dbfr_test_chunk_table.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
-    lib.dbfr_probe_mfma_f16.argtypes = [C.c_double, C.POINTER(C.c_double), vp]
-    lib.dbfr_profile_enable.argtypes = [vp, i32]
-    lib.dbfr_profile_fused_bytes.argtypes = [vp, C.POINTER(C.c_double)]
-    lib.dbfr_profile_executed_flops.argtypes = [vp, C.POINTER(C.c_double)]
-    lib.dbfr_profile_useful_flops.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    lib.dbfr_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
-                                      C.POINTER(C.c_double), i32]
-    lib.dbfr_workspace_layout.argtypes = [vp, C.POINTER(Batch), C.POINTER(Limits), C.c_char_p, C.c_size_t,
-                                          C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), i32]
-    lib.dbfr_test_conv.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp]
-    lib.dbfr_test_conv2.argtypes = lib.dbfr_test_conv.argtypes
-    lib.dbfr_test_reduce_ln.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp]
-    lib.dbfr_test_reduce_ln2.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp]
-    lib.dbfr_test_sde_step.argtypes = [vp, C.POINTER(Batch), C.POINTER(Step), C.POINTER(Scores), C.POINTER(Noise), vp, vp, vp]
-    lib.dbfr_test_time_embed.argtypes = [vp, vp, i32, vp, vp]
-    lib.dbfr_test_mlp.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.dbfr_test_atom_encoder.argtypes = [vp, vp, vp, vp, i32, vp, vp]
-    lib.dbfr_test_reduce_ln_layer.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), i32, i32, vp, vp, vp, vp, vp]
-    lib.dbfr_test_center_edges.argtypes = [C.POINTER(Batch), vp, vp, vp, vp, vp, vp, vp]
-    lib.dbfr_test_trrot.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
-    lib.dbfr_test_bond_attr.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, vp]
-    lib.dbfr_test_tor_final.argtypes = [vp, i32, vp, vp, i32, vp, vp]
-    lib.dbfr_select_pocket.argtypes = [i32, i32, vp, i32, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]
-    lib.dbfr_pose_metrics.argtypes = [C.POINTER(PoseMetricsIn), C.POINTER(PoseMetricsOut), vp]
-    lib.dbfr_pdb_format.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, i32, i32, vp, C.c_int64]
-    lib.dbfr_pdb_format.restype = C.c_int64
-    lib.dbfr_pdb_write_files.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, i32, C.POINTER(C.c_char_p), i32]
-    lib.dbfr_sdf_format.argtypes = [C.POINTER(SdfTemplate), vp, vp, C.c_int64]
-    lib.dbfr_sdf_format.restype = C.c_int64
-    lib.dbfr_sdf_write_files.argtypes = [C.POINTER(SdfTemplate), vp, i32, C.POINTER(C.c_char_p), i32]
-    lib.dbfr_mdn_model_create.argtypes = [C.POINTER(Tensor), i32, C.POINTER(vp)]
-    lib.dbfr_mdn_model_destroy.argtypes = [vp]
-    lib.dbfr_mdn_model_destroy.restype = None
-    lib.dbfr_mdn_workspace_bytes.argtypes = [C.POINTER(MdnBatch), C.POINTER(C.c_size_t)]
-    lib.dbfr_mdn_pocket_features.argtypes = [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.dbfr_mdn_forward.argtypes = [vp, C.POINTER(MdnBatch), vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_vina_workspace_bytes.argtypes = [C.POINTER(VinaIn), C.POINTER(C.c_size_t)]
-    lib.dbfr_vina_score.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_vina_score_at.argtypes = [C.POINTER(VinaIn), vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_vina_minimize.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_vina_flex_workspace_bytes.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(C.c_size_t)]
-    lib.dbfr_vina_flex_score_at.argtypes = [C.POINTER(VinaFlexIn), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_vina_flex_minimize.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(VinaOpts), vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_vina_search_workspace_bytes.argtypes = [C.POINTER(VinaIn), i32, C.POINTER(C.c_size_t)]
-    lib.dbfr_vina_search.argtypes = [C.POINTER(VinaIn), C.POINTER(VinaOpts), C.POINTER(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp, vp,
-                                     C.c_size_t, vp]
-    lib.dbfr_vina_flex_search_workspace_bytes.argtypes = [C.POINTER(VinaFlexIn), i32, C.POINTER(C.c_size_t)]
-    lib.dbfr_vina_flex_search.argtypes = [C.POINTER(VinaFlexIn), C.POINTER(VinaOpts), C.POINTER(VinaSearchOpts), vp, vp, vp, vp, vp, vp, vp,
-                                          vp, vp, vp, vp, C.c_size_t, vp]
-    lib.dbfr_test_philox4x32.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    lib.dbfr_test_vina_mutation.argtypes = [C.c_uint64, C.c_int64, i32, i32, i32, C.c_float, C.c_float, C.POINTER(i32),
-                                            C.POINTER(C.c_float)]
-    lib.dbfr_pose_rmsd_matrix.argtypes = [C.POINTER(PoseRmsdIn), vp, vp]
-    lib.dbfr_select_modes.argtypes = [C.POINTER(PoseRmsdIn), vp, vp, C.POINTER(ModesOpts), vp, vp, vp, vp]
-    lib.dbfr_pose_check.argtypes = [C.POINTER(PoseCheckIn), C.POINTER(PoseCheckOpts), C.POINTER(PoseCheckOut), vp]
-    lib.dbfr_pdb_atom_map.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, vp, C.c_int64, C.POINTER(C.c_int64)]
-    lib.dbfr_pdb_atom_map.restype = C.c_int64
-    lib.dbfr_complex_pdb_format.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, C.POINTER(PdbLigand), vp, vp, C.c_int64]
-    lib.dbfr_complex_pdb_format.restype = C.c_int64
-    lib.dbfr_complex_pdb_write_files.argtypes = [C.POINTER(PdbTopology), i32, vp, vp, C.POINTER(PdbLigand), vp, i32,
-                                                 C.POINTER(C.c_char_p), i32]
-    lib.dbfr_xtc_workspace_bytes.argtypes = [C.POINTER(XtcIn), C.POINTER(C.c_size_t), C.POINTER(C.c_int64)]
-    lib.dbfr_xtc_encode.argtypes = [C.POINTER(XtcIn), C.POINTER(XtcOpts), vp, C.c_int64, vp, vp, C.c_size_t, vp]
-    lib.dbfr_sites_workspace_bytes.argtypes = [C.POINTER(SitesIn), C.POINTER(C.c_size_t)]
-    lib.dbfr_find_sites.argtypes = [C.POINTER(SitesIn), C.POINTER(SitesOpts), C.POINTER(SitesOut), vp, C.c_size_t, vp]
-    lib.dbfr_interactions.argtypes = [C.POINTER(InteractionsIn), C.POINTER(InteractionsOpts), C.POINTER(InteractionsOut), vp]
-    lib.dbfr_pocket_check.argtypes = [C.POINTER(PocketCheckIn), C.POINTER(PocketCheckOpts), C.POINTER(PocketCheckOut), vp]
-    lib.dbfr_sasa.argtypes = [C.POINTER(SasaIn), C.POINTER(SasaOpts), C.POINTER(SasaOut), vp]
-    lib.dbfr_seq_align.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32]
-    lib.dbfr_holo_site.argtypes = [C.POINTER(HoloSiteIn), vp, vp]
-    lib.dbfr_holo_metrics.argtypes = [C.POINTER(HoloMetricsIn), C.POINTER(HoloMetricsOpts), C.POINTER(HoloMetricsOut), vp]
-    lib.dbfr_hetero_check.argtypes = [C.POINTER(HeteroCheckIn), C.POINTER(HeteroCheckOpts), C.POINTER(HeteroCheckOut), vp]
-    lib.dbfr_hydrogens.argtypes = [C.POINTER(HydrogensIn), C.POINTER(HydrogensOpts), C.POINTER(HydrogensOut), vp]
-    lib.dbfr_vina_decompose.argtypes = [C.POINTER(VinaDecomposeIn), C.POINTER(VinaDecomposeOpts), C.POINTER(VinaDecomposeOut), vp]
-    lib.dbfr_pose_cavity_workspace_bytes.argtypes = [C.POINTER(CavityIn), C.POINTER(C.c_size_t)]
-    lib.dbfr_pose_cavity.argtypes = [C.POINTER(CavityIn), C.POINTER(CavityOpts), C.POINTER(CavityOut), vp]
-    if lib.dbfr_abi_version() != 8:
+    for name, argtypes in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        if name in RESTYPES:
+            fn.restype = RESTYPES[name]
+    if lib.dbfr_abi_version() != ABI_VERSION:
         raise DbfrError("libdbfr ABI version mismatch")
     _lib = lib
     return lib

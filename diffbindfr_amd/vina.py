@@ -654,7 +654,7 @@ class VinaFlexBatch:
         ex_len = np.diff(np.asarray(excl_ptr))
         maxima = (self.n_flex, self.n_ftor, int(np.diff(fp).max()), int(np.diff(tp).max()), max(anchors),
                   int(ex_len.max()) if ex_len.size else 0)
-        names = [n for n, _ in VinaFlexIn._fields_][1:9]
+        names = L.pointer_fields(VinaFlexIn, skip=1)
         self._host_c = VinaFlexIn(None, *[self.host[n].ctypes.data for n in names], *maxima, None)
         self.c = VinaFlexIn(C.addressof(vb.c), *[self.t[n].data_ptr() for n in names], *maxima, C.addressof(self._host_c))
         nb = C.c_size_t(0)

@@ -171,25 +171,3 @@ def test_cpu_tensors_are_refused(fx):
     cin.max_site = 513
     assert lib.dbfr_holo_metrics(C.byref(cin), None, C.byref(L.HoloMetricsOut()), None) == -1 and b"max_site" in lib.dbfr_last_error()
     assert lib.dbfr_holo_site(None, None, None) == -1
-
-
-def test_ctypes_structs_match_the_header_layout(tmp_path):
-    """sizeof and the offsets of the last fields of the new ctypes mirrors == what a C compiler lays out for include/dbfr.h."""
-    import os
-    import subprocess
-    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    fields = {"dbfr_holo_site_in": (L.HoloSiteIn, ["atom_ptr", "res_ptr", "n_res", "cutoff"]),
-              "dbfr_holo_metrics_in": (L.HoloMetricsIn, ["frame_ptr", "holo_chi", "perms", "max_site", "max_lig", "host"]),
-              "dbfr_holo_metrics_opts": (L.HoloMetricsOpts, ["radius"]),
-              "dbfr_holo_metrics_out": (L.HoloMetricsOut, ["pair_dist", "altchi", "lddt_num"])}
-    body = "".join(f'printf("{s} %zu\\n", sizeof({s}));' + "".join(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));' for f in fs)
-                   for s, (_, fs) in fields.items())
-    src = tmp_path / "t.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dbfr.h"\nint main(void){' + body + 'return 0;}\n')
-    exe = tmp_path / "o"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    for s, (cls, fs) in fields.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f in fs:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)

@@ -1,11 +1,10 @@
 """Host side of the per-pose cavities (diffbindfr_amd/cavity.py): the float64 restatement (tests/cavity_ref.py) -- the exactness
 precondition of the bit-for-bit comparison on every batch the GPU tests use, hand-built motifs with known answers, the identities
-between the totals, the 3DBS crystal pose --, the columns, the report and the PDB text, and the C-side layout and refusals that
+between the totals, the 3DBS crystal pose --, the columns, the report and the PDB text, and the C-side refusals that
 need no device."""
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,7 +15,6 @@ from diffbindfr_amd import cavity, lib as L
 import cavity_ref as ref  # noqa: E402  (a module next to the test files: pytest puts their directory on sys.path)
 import pocketcheck_ref  # noqa: E402
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 SPACINGS = (0.75, 1.0, 2.0)
 
 
@@ -143,25 +141,8 @@ def test_3dbs_crystal_pose():
     assert w["margin"] > 5e-5                                   # no threshold is met exactly: nothing hangs on a tie here
 
 
-def test_new_symbols_resolve_and_structs_match_the_header(tmp_path):
-    lib = L.load()
-    for s in ("dbfr_pose_cavity", "dbfr_pose_cavity_workspace_bytes"):
-        assert s in L.SYMBOLS and hasattr(lib, s)
-    assert lib.dbfr_abi_version() == 8
-    structs = {"dbfr_cavity_in": L.CavityIn, "dbfr_cavity_opts": L.CavityOpts, "dbfr_cavity_out": L.CavityOut}
-    fields = {s: [f for f, _ in cls._fields_] for s, cls in structs.items()}
-    body = "".join(f'printf("{s} %zu\\n", sizeof({s}));' + "".join(f'printf("{s}.{f} %zu\\n", offsetof({s},{f}));' for f in fs)
-                   for s, fs in fields.items())
-    src = tmp_path / "m.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dbfr.h"\nint main(void){' + body + 'return 0;}\n')
-    exe = tmp_path / "m"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f in fields[s]:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
-    assert list(cavity.DEFAULTS) == fields["dbfr_cavity_opts"]
+def test_defaults_name_the_fields_of_the_options_struct():
+    assert list(cavity.DEFAULTS) == [f for f, _ in L.CavityOpts._fields_]
     o = cavity._opts()
     assert (o.spacing, o.ray_length, o.lining_cutoff, o.min_buried) == (1.0, 8.0, 4.0, 6) and o.probe == pytest.approx(1.2)
 
@@ -181,7 +162,7 @@ def _host_call(lib, **change):
             tail[k] = v
         elif k != "opts":
             a[k] = v
-    order = [f for f, _ in L.CavityIn._fields_][2:22]
+    order = L.pointer_fields(L.CavityIn)
     p = C.c_void_p(16)
     hin = L.CavityIn(1, 2, *[a[k].ctypes.data if k in a else None for k in order], *tail.values(), None)
     cin = L.CavityIn(1, 2, *([p] * 20), *tail.values(), C.addressof(hin))
@@ -220,7 +201,7 @@ def test_abi_refuses_bad_arguments_before_any_launch():
     with pytest.raises(cavity.DbfrError, match="unknown"):
         cavity._opts(unknown=1)
     # the workspace: 4 KB per frame with a reference frame, none without; too small a one is refused
-    order = [f for f, _ in L.CavityIn._fields_][2:22]
+    order = L.pointer_fields(L.CavityIn)
     p = C.c_void_p(16)
     cin = L.CavityIn(1, 2, *([p] * 20), 2, 2, 2, None)
     n = C.c_size_t(7)

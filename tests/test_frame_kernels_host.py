@@ -15,9 +15,9 @@ STATIC = ("static_ptr", "static_pos", "static_rad", "static_w", "static_col", "s
 i32, f32, u8, i64 = np.int32, np.float32, np.uint8, np.int64
 
 
-def _refusal(fn, In, n_ptr, host, tail, out):
+def _refusal(fn, In, host, tail, out):
     """The text fn refuses the host copies with; 2 groups, 3 frames; device pointers are 1 except the static ones (NULL)."""
-    order = [f for f, _ in In._fields_][2:2 + n_ptr]
+    order = L.pointer_fields(In)
     hin = In(2, 3, *[host[k].ctypes.data if k in host else None for k in order], *tail, None)
     cin = In(2, 3, *[None if k in STATIC else 1 for k in order], *tail, C.addressof(hin))
     lib = L.load()
@@ -49,7 +49,7 @@ def _pocket_host():
 def test_sasa_walks_every_group_without_static_arrays(key, value, text):
     host = _sasa_host()
     host[key][3] = value                                               # group 1's last pocket atom: the last receptor atom of all
-    got = _refusal(lambda lib: lib.dbfr_sasa, L.SasaIn, 23, host, (64, 3, 2, 3, 0), L.SasaOut(1, 1, 1, 1))
+    got = _refusal(lambda lib: lib.dbfr_sasa, L.SasaIn, host, (64, 3, 2, 3, 0), L.SasaOut(1, 1, 1, 1))
     assert got.startswith("dbfr_sasa: " + text), got
 
 
@@ -58,5 +58,5 @@ def test_sasa_walks_every_group_without_static_arrays(key, value, text):
 def test_pocket_check_walks_every_group_without_static_arrays(key, value, text):
     host = _pocket_host()
     host[key][4] = value
-    got = _refusal(lambda lib: lib.dbfr_pocket_check, L.PocketCheckIn, 20, host, (3, 1, 2, 0), L.PocketCheckOut(*[1] * 7))
+    got = _refusal(lambda lib: lib.dbfr_pocket_check, L.PocketCheckIn, host, (3, 1, 2, 0), L.PocketCheckOut(*[1] * 7))
     assert got.startswith("dbfr_pocket_check: " + text), got

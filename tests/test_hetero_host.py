@@ -121,7 +121,7 @@ def _host():
 
 
 def _refusal(host, tail=(3, 2, 3, 0), opts=None):
-    order = [f for f, _ in L.HeteroCheckIn._fields_][2:25]
+    order = L.pointer_fields(L.HeteroCheckIn)
     hin = L.HeteroCheckIn(2, 3, *[host[k].ctypes.data if k in host else None for k in order], *tail, None)
     cin = L.HeteroCheckIn(2, 3, *[1] * 23, *tail, C.addressof(hin))
     lib = L.load()

@@ -213,7 +213,7 @@ def test_unusable_coordinates_and_refusals():
     from diffbindfr_amd import lib as L
     lib = L.load()
     t = {k: torch.as_tensor(v, device=DEV) for k, v in _flat_inputs(gr).items()}
-    order = [f for f, _ in L.SasaIn._fields_][2:25]
+    order = L.pointer_fields(L.SasaIn)
     tot = torch.zeros(5, 6, dtype=torch.int64, device=DEV)
     c_in = L.SasaIn(1, 5, *[t[k].data_ptr() for k in order], 256, 12, int(gr["pocket"].shape[1]), int(gr["n_res"]), 0, None)
     for c_out in (L.SasaOut(None, None, None, tot.data_ptr()), L.SasaOut(None, None, None, None)):

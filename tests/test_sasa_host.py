@@ -1,10 +1,8 @@
 """Host side of the surface areas (diffbindfr_amd/sasa.py): the float64 restatement (tests/sasa_ref.py) -- how narrow its
 interval is, the float32 arithmetic inside it, known answers --, the point set, the weights, the column names and the report, and
-the C-side layout and refusals that need no device."""
+the C-side refusals that need no device."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +11,6 @@ from diffbindfr_amd import lib as L, sasa
 
 import sasa_ref as ref  # noqa: E402  (a module next to the test files: pytest puts their directory on sys.path)
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 KEYS = ("lig_free", "lig_bound", "rec_buried", "res_buried", "totals")
 
 
@@ -96,23 +93,8 @@ def test_area_weights():
     assert sasa.UNIT == 4096 and sasa.N_POINTS == 256
 
 
-def test_new_symbol_resolves_and_structs_match_the_header(tmp_path):
-    lib = L.load()
-    assert "dbfr_sasa" in L.SYMBOLS and hasattr(lib, "dbfr_sasa")
-    structs = {"dbfr_sasa_in": L.SasaIn, "dbfr_sasa_opts": L.SasaOpts, "dbfr_sasa_out": L.SasaOut}
-    fields = {s: [f for f, _ in cls._fields_] for s, cls in structs.items()}
-    body = "".join(f'printf("{s} %zu\\n", sizeof({s}));' + "".join(f'printf("{s}.{f} %zu\\n", offsetof({s},{f}));' for f in fs)
-                   for s, fs in fields.items())
-    src = tmp_path / "m.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dbfr.h"\nint main(void){' + body + 'return 0;}\n')
-    exe = tmp_path / "m"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    for s, cls in structs.items():
-        assert int(out[s]) == C.sizeof(cls), s
-        for f in fields[s]:
-            assert int(out[f"{s}.{f}"]) == getattr(cls, f).offset, (s, f)
-    assert list(sasa.DEFAULTS) == fields["dbfr_sasa_opts"]
+def test_defaults_name_the_fields_of_the_options_struct():
+    assert list(sasa.DEFAULTS) == [f for f, _ in L.SasaOpts._fields_]
     assert sasa._opts().probe == pytest.approx(1.4)
 
 
@@ -132,7 +114,7 @@ def _host_call(lib, **change):
             tail[k] = v
         elif k != "opts":
             a[k] = v
-    order = [f for f, _ in L.SasaIn._fields_][2:25]
+    order = L.pointer_fields(L.SasaIn)
     p = C.c_void_p(16)
     hin = L.SasaIn(1, 1, *[a[k].ctypes.data if k in a else None for k in order], *tail.values(), None)
     cin = L.SasaIn(1, 1, *([p] * 23), *tail.values(), C.addressof(hin))

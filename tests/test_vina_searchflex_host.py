@@ -13,14 +13,6 @@ from diffbindfr_amd import lib as L, vina
 import vina_search_ref as ref  # noqa: E402  (a module next to the test files: pytest puts their directory on sys.path)
 
 
-def test_symbols_resolve_and_the_abi_number_stays():
-    lib = L.load()
-    for sym in ("dbfr_vina_flex_search_workspace_bytes", "dbfr_vina_flex_search"):
-        assert sym in L.SYMBOLS and hasattr(lib, sym)
-    assert lib.dbfr_abi_version() == 8
-    assert C.sizeof(L.VinaSearchOpts) == 40                       # dbfr_vina_search_opts is reused unchanged
-
-
 def _host_call(lib, call="search", search=None, opts=None, null=(), ws_bytes=1 << 20, **change):
     """A flexible search on one graph (a 4-atom ligand, 6 pocket atoms, 1 extra atom; flexible atoms 3 and 4, one torsion about
     (1, 3) that turns atom 4) whose device pointers are never dereferenced: every refused call fails its host-side checks before any
@@ -41,7 +33,7 @@ def _host_call(lib, call="search", search=None, opts=None, null=(), ws_bytes=1 <
     for k in L._BATCH_PTRS:
         setattr(batch, k, p)
     base = L.VinaIn(C.addressof(batch), p, p, p, p, 0, p, p, p, num["max_tor"], num["max_ext"])
-    names = [n for n, _ in L.VinaFlexIn._fields_][1:9]
+    names = L.pointer_fields(L.VinaFlexIn, skip=1)
     counts = [num[k] for k in ("n_flex", "n_ftor", "max_flex", "max_ftor", "max_anchor", "max_excl")]
     hin = L.VinaFlexIn(None, *[None if a[k] is None else a[k].ctypes.data for k in names], *counts, None)
     cin = L.VinaFlexIn(C.addressof(base), *([p] * 8), *counts, C.addressof(hin) if num["G"] == 1 else None)

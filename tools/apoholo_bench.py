@@ -10,10 +10,7 @@ one per complex as its interface takes them, host staging included).  No time is
 records of tests/apoholo_ref.py (a few drawn, reused across the batch).
 """
 import argparse
-import json
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -22,7 +19,8 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from diffbindfr_amd import apoholo as ah, build as dbuild, export as pex  # noqa: E402
+import benchkit  # noqa: E402
+from diffbindfr_amd import apoholo as ah, export as pex  # noqa: E402
 import apoholo_ref as ref  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -32,35 +30,6 @@ ap.add_argument("--poses", type=int, default=40)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-
-
-def events(fn, inner=10):
-    """Seconds per call: ``inner`` calls back to back between two events (a window long enough to time), --reps times."""
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) / 1e3 / inner)
-    return float(np.median(ts)), [round(t * 1e3, 4) for t in ts]
-
-
-def resource_lines():
-    """The compiler's resource report of the kernels of apoholo.hip: the file compiled for the device alone with the build's flags."""
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "-c", "--cuda-device-only", os.path.join(dbuild.CSRC, "apoholo.hip"),
-           "-o", os.devnull] + dbuild.FLAGS + dbuild.FILE_FLAGS["apoholo.hip"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    out = {}
-    for name, body in re.findall(r"Function Name: _Z\d+(k_holo_[a-z]+)(.*?)(?=Function Name:|\Z)", r.stderr, re.S):
-        got = dict(re.findall(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\d+)", body))
-        keep = ("TotalSGPRs", "VGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
-        out[name] = {k: int(got[k]) for k in keep if k in got}
-    return out
 
 
 def measure(n_complex, poses):
@@ -76,7 +45,7 @@ def measure(n_complex, poses):
                                    tmscore=1.0, n_aligned=S))
         groups.append(dict(pocket=torch.as_tensor(pocket, device=dev), lig=torch.as_tensor(lig, device=dev)))
     launch, out = ah.evaluate_launcher(pairs, groups)
-    t_call, runs = events(launch, inner=100)
+    t_call, runs = benchkit.events(launch, args.reps, inner=100)
     # the restatement holds the device outputs of the first frame of the first complexes
     inside = True
     for g in range(2):
@@ -98,7 +67,7 @@ def measure(n_complex, poses):
         for g, (rec, pocket, lig, _) in zip(groups, made):
             pex.pose_metrics(g["lig"][:, None], g["pocket"][:, None], np.zeros(3, np.float32), rec["holo_lig"], pocket[0],
                              np.ones(pocket.shape[1:3], np.float32), np.zeros(pocket.shape[1], np.int32))
-    t_pm, _ = events(pose_metrics_all, inner=2)
+    t_pm, _ = benchkit.events(pose_metrics_all, args.reps, inner=2)
     return {"complexes": n_complex, "frames": n_complex * poses, "site_residues_mean": float(S.mean()), "pocket_atoms_mean": float(14 * R.mean()),
             "lig_atoms_mean": float(N.mean()), "holo_lig_atoms_mean": float(H.mean()), "call_ms": round(t_call * 1e3, 4), "call_ms_runs": runs,
             "frames_per_s": round(n_complex * poses / t_call, 1), "bytes_read_min": read, "bytes_written_min": write,
@@ -110,12 +79,9 @@ def measure(n_complex, poses):
 res = {"what": "holo-pocket recovery (dbfr_holo_metrics, one call = two launches) next to dbfr_pose_metrics on the same frames",
        "device": torch.cuda.get_device_name(0)}
 res["cfg2"] = measure(args.complexes, args.poses)
-res["resources"] = resource_lines()
+res["resources"] = benchkit.resource_usage("apoholo.hip")
 res["timing"] = (f"dbfr_holo_metrics: HIP events around 100 calls back to back, per call, median of {args.reps} after one warm-up "
                  f"(call_ms_runs: every repeat; the host validation of the index arrays is part of every call); dbfr_pose_metrics: HIP events "
                  f"around 2 passes over the {args.complexes} per-complex calls of export.pose_metrics, host staging included; bytes: every frame's "
                  f"pocket rows and ligand once, the pair table of every group written and read once, the pair records, and every output once")
-print(json.dumps(res))
-if args.out:
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(res) + "\n")
+benchkit.emit(res, args.out)

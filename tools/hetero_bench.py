@@ -2,24 +2,21 @@
 
     python tools/hetero_bench.py [--reps 5] [--out profiles/r16_hetero_bench.json] [--kernel-only]
 
-Prints one JSON line (and writes it to --out).  For the config-2 shape of tools/posecheck_bench.py (128 synthetic complexes x 40
+Prints one JSON line (and writes it to --out).  For the config-2 shape of benchkit.cavity_entries (128 synthetic complexes x 40
 frames = 5 120 frames, about 30 ligand atoms and 200 pocket atoms per frame and a few thousand static atoms per complex, one
 launch) with a record of 40 cofactor atoms, 2 metal ions and 150 waters per complex: the kernel time of dbfr_hetero_check (HIP
 events around 10 launches back to back, per launch, median of --reps after one warm-up), the kernel time of dbfr_pose_check on the
 same frames in the same run (the yardstick) and their ratio, the time with a one-entry candidate list (the lattice passes read
 memory), the wall time of hetero.annotate over export.ComplexOutput entries of the same poses (host staging included,
-synchronised) and the compiler's resource line for k_hetero_check.  No time is fixed in advance.  Complexes: the synthetic
-proteins of tools/pocketcheck_bench.py (a cavity of 10 A around the origin) with rigid random moves of a synthetic ligand in the
-cavity; the cofactor is a blob at the cavity wall, the metals sit next to it and the waters fill the shell from 3 to 14 A.
+synchronised) and the compiler's resource line for k_hetero_check.  No time is fixed in advance.  Complexes:
+benchkit.cavity_entries (a cavity of 10 A around the origin) with rigid random moves of a synthetic ligand in the cavity;
+benchkit.hetero_record: the cofactor is a blob at the cavity wall, the metals sit next to it and the waters fill the shell from
+3 to 14 A.
 """
 import argparse
 import dataclasses
-import json
 import os
-import re
-import subprocess
 import sys
-import time
 
 import numpy as np
 import pandas as pd
@@ -27,8 +24,8 @@ import torch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
-from diffbindfr_amd import build as dbuild, export as pex, hetero, posecheck, sasa, synthetic  # noqa: E402
-from diffbindfr_amd.ligand import SdfTemplate  # noqa: E402
+import benchkit  # noqa: E402
+from diffbindfr_amd import hetero, posecheck, sasa  # noqa: E402
 from diffbindfr_amd.vina import _entry_receptor  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -37,134 +34,11 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--kernel-only", action="store_true", help="launch the kernel on the config-2 shape only (for a profiler)")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-T = synthetic.residue_tables()
-N_COFACTOR, N_METAL, N_WATER = 40, 2, 150
-
-
-def events(fn, inner=10):
-    """Seconds per launch: ``inner`` launches back to back between two events (a window long enough to time), --reps times."""
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(inner):
-            fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) / 1e3 / inner)
-    return float(np.median(ts)), [round(t * 1e3, 4) for t in ts]
-
-
-def wall(fn):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts))
-
-
-def rot(rng):
-    q = rng.standard_normal(4)
-    w, x, y, z = q / np.linalg.norm(q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
-
-
-def molblock(sym, bonds, pos):
-    lines = ["lig", "  bench", "", f"{len(sym):3d}{len(bonds):3d}  0  0  0  0  0  0  0  0999 V2000"]
-    lines += [f"{x:10.4f}{y:10.4f}{z:10.4f} {s:<3s} 0  0  0  0  0  0  0  0  0  0  0  0" for (x, y, z), s in zip(pos, sym)]
-    lines += [f"{a + 1:3d}{b + 1:3d}{o:3d}  0" for a, b, o in bonds]
-    return "\n".join(lines + ["M  END", "$$$$", ""])
-
-
-def protein(rng, n_static):
-    p = synthetic.make_pocket(rng, n_static + 600)
-    keep = np.linalg.norm(p["backbone_transl"], axis=1) > 10.0                      # the cavity: no CA within 10 A
-    seq = p["sequence"][keep]
-    chi = rng.uniform(-np.pi, np.pi, (keep.sum(), 5)) * np.concatenate([np.ones((keep.sum(), 1)), p["sc_torsion_edge_mask"][keep]], 1)
-    build = lambda rows, angles: synthetic.build_atom14_np(seq[rows], p["backbone_transl"][keep][rows], p["backbone_rots"][keep][rows],
-                                                           p["default_frame"][keep][rows], p["rigid_group_positions"][keep][rows],
-                                                           angles, T["atom14_to_group"])
-    a14 = build(np.arange(len(seq)), chi)
-    m14 = T["atom14_mask"][seq] > 0.5
-    order = np.argsort(np.linalg.norm(p["backbone_transl"][keep], axis=1))
-    pocket = np.sort(order[:np.searchsorted(np.cumsum(m14[order].sum(1)), 200) + 1])
-    n_r = len(seq)
-    a37, m37 = np.zeros((n_r, 37, 3), np.float32), np.zeros((n_r, 37), np.float32)
-    slot = T["atom14_to_atom37"][seq]
-    for r in range(n_r):
-        for s in np.nonzero(m14[r])[0]:
-            a37[r, slot[r, s]] = a14[r, s]
-            m37[r, slot[r, s]] = 1
-    topo = pex.ProteinTopology(seq, a37, m37, np.arange(1, n_r + 1), np.zeros(n_r), np.zeros((n_r, 37)), None, pocket)
-    mask = np.concatenate([np.zeros((len(pocket), 1)), p["sc_torsion_edge_mask"][keep][pocket]], 1)
-
-    def frames(n):                                                                  # the pocket with every chi re-drawn, n times
-        return np.stack([build(pocket, chi[pocket] + rng.normal(scale=0.5, size=(len(pocket), 5)) * mask) * m14[pocket][..., None]
-                         for _ in range(n)]).astype(np.float32)
-    return topo, a14[pocket] * m14[pocket][..., None], m14[pocket].astype(np.float32), seq[pocket], frames
-
-
-def entries(cfg_id, n_complex, poses, seed=0):
-    c = synthetic.CONFIGS[cfg_id]
-    rng = np.random.default_rng(seed)
-    proteins = [protein(rng, 3000) for _ in range(4)]                              # a few receptors, reused
-    out = []
-    for k in range(n_complex):
-        n = max(4, int(round(c["n_lig"] * rng.uniform(0.85, 1.15))))
-        lg = synthetic.make_ligand(rng, n)
-        x0 = lg["lig_pos_ref"] - lg["lig_pos_ref"].mean(0)
-        ei = lg["lig_edge_index"]
-        bonds = [(int(a), int(b), 1) for a, b in ei.T if a < b]
-        u = rng.random(n)
-        sym = np.where(u < 0.2, "N", np.where(u < 0.3, "O", "C"))
-        x = np.stack([x0 @ rot(rng).T + rng.normal(scale=1.0, size=3) for _ in range(poses)]).astype(np.float32)
-        topo, a14, m14, aa, frames = proteins[k % len(proteins)]
-        out.append(pex.ComplexOutput(name=f"c{k}", ligand_traj=torch.as_tensor(x[:, None], device=dev),
-                                     protein_traj=torch.as_tensor(frames(poses)[:, None], dtype=torch.float32, device=dev),
-                                     pocket_center_pos=np.zeros(3, np.float32), ligand_pos=x0.astype(np.float32),
-                                     ligand_labels=np.array([{"C": 6, "N": 7, "O": 8}[s] for s in sym]), ligand_edge_index=ei,
-                                     topology=topo, atom14_position=a14, atom14_mask=m14, aatype=aa,
-                                     sdf_template=SdfTemplate.from_molblock(molblock(sym, bonds, x0))))
-    return out
-
-
-def record(rng):
-    """40 cofactor atoms in a blob at the cavity wall, 2 zinc ions next to it, 150 waters in the shell from 3 to 14 A."""
-    unit = lambda n: (lambda v: v / np.linalg.norm(v, axis=1, keepdims=True))(rng.normal(size=(n, 3)))
-    centre = unit(1)[0] * 7.0
-    cof = centre + unit(N_COFACTOR) * 3.0 * rng.random((N_COFACTOR, 1)) ** (1 / 3)
-    met = centre + unit(N_METAL) * rng.uniform(3.0, 4.5, (N_METAL, 1))
-    wat = unit(N_WATER) * (27.0 + (14.0 ** 3 - 27.0) * rng.random((N_WATER, 1))) ** (1 / 3)
-    u = rng.random(N_COFACTOR)
-    el = list(np.where(u < 0.15, "N", np.where(u < 0.3, "O", "C"))) + ["Zn"] * N_METAL + ["O"] * N_WATER
-    n = len(el)
-    return hetero.HeteroRecord(pos=np.concatenate([cof, met, wat]), element=el, klass=[0] * N_COFACTOR + [1] * N_METAL + [2] * N_WATER,
-                               name=[f"{e.upper()}{k}" for k, e in enumerate(el)], resname=["COF"] * N_COFACTOR + ["ZN"] * N_METAL + ["HOH"] * N_WATER,
-                               chain=["A"] * n, resnum=[900] * N_COFACTOR + list(range(901, 901 + N_METAL)) + list(range(1000, 1000 + N_WATER)))
-
-
-def resource_line():
-    """The compiler's resource report of k_hetero_check: the file compiled for the device alone with the flags of the build."""
-    flags = dbuild.FLAGS + dbuild.FILE_FLAGS["hetero.hip"]
-    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "-c", "--cuda-device-only", os.path.join(dbuild.CSRC, "hetero.hip"),
-           "-o", os.devnull] + flags
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    got = dict(re.findall(r"remark:\s+([A-Za-z \[\]/]+?):\s+(\d+)", r.stderr))
-    keep = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Occupancy [waves/SIMD]", "LDS Size [bytes/block]")
-    return {k: int(got[k]) for k in keep if k in got}
 
 
 def measure(cfg_id, n_complex, poses):
     rng = np.random.default_rng(1)
-    es = [dataclasses.replace(e, hetero=record(rng)) for e in entries(cfg_id, n_complex, poses)]
+    es = [dataclasses.replace(e, hetero=benchkit.hetero_record(rng)) for e in benchkit.cavity_entries(cfg_id, n_complex, poses, dev)]
     df = pd.DataFrame({"sample_id": np.arange(n_complex * poses)})
     groups, pb_groups, made = [], [], {}
     rad_table = posecheck.receptor_radius_table()
@@ -179,15 +53,15 @@ def measure(cfg_id, n_complex, poses):
         rec, rec_rad, ext_pos, ext_rad = _entry_receptor(e, rad_table)
         pb_groups.append(dict(lig=e.ligand_traj[:, -1], chem=chem, pocket=rec, pocket_rad=rec_rad, static=ext_pos, static_rad=ext_rad))
     launch, out = hetero.check_launcher(groups)
-    t_kernel, runs = events(launch)
+    t_kernel, runs = benchkit.events(launch, args.reps, inner=10)
     if args.kernel_only:
         return {"frames": n_complex * poses, "kernel_ms": round(t_kernel * 1e3, 4)}
-    spilled, _ = events(hetero.check_launcher(groups, cand_cap=1)[0])
+    spilled, _ = benchkit.events(hetero.check_launcher(groups, cand_cap=1)[0], args.reps, inner=10)
     pb_launch, _ = posecheck.check_launcher(pb_groups)
-    t_pose_check, pb_runs = events(pb_launch)
-    t_annotate = wall(lambda: hetero.annotate(es, df))
+    t_pose_check, pb_runs = benchkit.events(pb_launch, args.reps, inner=10)
+    t_annotate = benchkit.wall(lambda: hetero.annotate(es, df), args.reps)
     passed = out["passed"].cpu().numpy()
-    return {"complexes": n_complex, "frames": n_complex * poses, "hetero_atoms": N_COFACTOR + N_METAL + N_WATER,
+    return {"complexes": n_complex, "frames": n_complex * poses, "hetero_atoms": len(es[0].hetero),
             "lig_atoms_mean": float(np.mean([g["lig"].shape[1] for g in groups])),
             "pocket_atoms_mean": float(np.mean([g["pocket"].shape[1] for g in groups])),
             "static_atoms_mean": float(np.mean([len(g["static"]) for g in groups])),
@@ -205,11 +79,8 @@ res = {"what": "hetero-atom checks (dbfr_hetero_check, one launch) next to dbfr_
        "device": torch.cuda.get_device_name(0)}
 res["cfg2"] = measure(2, 128, 40)
 if not args.kernel_only:
-    res["k_hetero_check_resources"] = resource_line()
+    res["k_hetero_check_resources"] = benchkit.resource_usage("hetero.hip")
 res["timing"] = (f"kernels: HIP events around 10 launches back to back, per launch, median of {args.reps} after one warm-up "
                  f"(kernel_ms_runs: every repeat); annotate: wall clock of hetero.annotate (host chemistry, staging, launch, copy "
                  f"back, names), synchronised, median of {args.reps}")
-print(json.dumps(res))
-if args.out:
-    with open(args.out, "w") as fh:
-        fh.write(json.dumps(res) + "\n")
+benchkit.emit(res, args.out)

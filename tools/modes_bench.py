@@ -13,52 +13,22 @@ how the poses were made).
 """
 import argparse
 import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
-import bench  # noqa: E402
-import diffbindfr_amd as dba  # noqa: E402
+import benchkit  # noqa: E402
 from diffbindfr_amd import lib as L, ligand, modes, synthetic  # noqa: E402
-from diffbindfr_amd.packing import PackedBatch  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--steps", type=int, default=20)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-
-
-def events(fn):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) / 1e3)
-    return float(np.median(ts))
-
-
-def wall(fn):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts))
 
 
 def rot(rng, n, spread=None):
@@ -98,9 +68,9 @@ def measure(cfg_id, n_complex, poses):
     launch, _, R = modes.rmsd_launcher(pos, perms)
     launch()
     scores = [torch.randn(poses, device=dev) for _ in range(n_complex)]
-    t_mat = events(launch)
-    t_mat_py = wall(lambda: modes.rmsd_matrix(pos, perms))
-    t_sel_py = wall(lambda: modes.select_modes(R, scores))
+    t_mat = benchkit.events(launch, args.reps)[0]
+    t_mat_py = benchkit.wall(lambda: modes.rmsd_matrix(pos, perms), args.reps)
+    t_sel_py = benchkit.wall(lambda: modes.select_modes(R, scores), args.reps)
     # the selection launch alone: the Python staging above (pose_ptr, concatenation) is done once here
     P = np.full(n_complex, poses)
     pose_ptr = torch.as_tensor(np.concatenate([[0], np.cumsum(P)]).astype(np.int32), device=dev)
@@ -111,8 +81,8 @@ def measure(cfg_id, n_complex, poses):
     o = modes._opts()
     lib = L.load()
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    t_sel = events(lambda: L.check(lib.dbfr_select_modes(C.byref(cin), flat.data_ptr(), S.data_ptr(), C.byref(o), out[0].data_ptr(),
-                                                         out[1].data_ptr(), out[2].data_ptr(), st)))
+    t_sel = benchkit.events(lambda: L.check(lib.dbfr_select_modes(C.byref(cin), flat.data_ptr(), S.data_ptr(), C.byref(o), out[0].data_ptr(),
+                                                         out[1].data_ptr(), out[2].data_ptr(), st)), args.reps)[0]
     n_perm = np.array([len(p) for p in perms])
     pairs = n_complex * poses * (poses - 1) // 2
     return {"groups": n_complex, "poses": poses, "pairs": pairs, "atoms_mean": float(np.mean([p.shape[1] for p in pos])),
@@ -123,33 +93,15 @@ def measure(cfg_id, n_complex, poses):
             "pairs_per_s": round(pairs / t_mat, 1)}
 
 
-def sample_seconds_per_pose(cfg_id):
-    d = synthetic.make_batch(cfg_id, n_complex=16, poses=40, seed=1)
-    pb = PackedBatch(d, dev)
-    G = pb.G
-    samp = dba.DiffBindFRHIP(diffusion_model=bench.seeded_params().to(dev), test_cfg={"sample_cfg": {"actual_steps": args.steps}})
-    gen = torch.Generator().manual_seed(3)
-    z = {"tr": torch.randn(args.steps, G, 3, generator=gen), "rot": torch.randn(args.steps, G, 3, generator=gen),
-         "tor": torch.randn(args.steps, max(pb.dims["NTOR"], 1), generator=gen),
-         "sc": torch.randn(args.steps, max(pb.dims["NSC"], 1), generator=gen)}
-    z = {k: v.to(dev).contiguous() for k, v in z.items()}
-    lig0, rec0, tor0 = pb.lig_pos.clone(), pb.rec_pos.clone(), pb.torsion_angle.clone()
-
-    def run():
-        pb.lig_pos.copy_(lig0), pb.rec_pos.copy_(rec0), pb.torsion_angle.copy_(tor0)
-        return samp.sample_packed(pb, z)
-    return wall(run) / G
-
-
 res = {"what": "binding modes (dbfr_pose_rmsd_matrix + dbfr_select_modes, one launch each) next to the sampling of the same poses",
        "device": torch.cuda.get_device_name(0)}
 for cfg_id, n_complex in ((3, 1250), (2, 128)):
     m = measure(cfg_id, n_complex, 40)
-    per_pose = sample_seconds_per_pose(cfg_id)
+    per_pose = benchkit.sample_seconds_per_pose(cfg_id, args.steps, args.reps, dev)
     sample_s = per_pose * n_complex * 40
     m["sample_s_scaled"] = round(sample_s, 3)
     m["modes_over_sample"] = round((m["matrix_ms"] + m["select_ms"]) / 1e3 / sample_s, 6)
     res[f"cfg{cfg_id}"] = m
 res["timing"] = (f"kernel times: HIP events around the launch, median of {args.reps} after one warm-up; *_py_ms: wall clock of the "
                  f"Python call, synchronised; sampling: {args.steps} steps of a 640-pose batch of the same config, per pose")
-print(json.dumps(res))
+benchkit.emit(res)

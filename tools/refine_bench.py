@@ -8,10 +8,8 @@ batch; and for the 3DBS fixture with 40 poses (the crystal pose moved by 1 A and
 Times are wall clock around synchronised calls, the median of --reps repetitions after one warm-up.
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -19,9 +17,9 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import benchkit  # noqa: E402
 import diffbindfr_amd as dba  # noqa: E402
-from diffbindfr_amd import synthetic, vina  # noqa: E402
-from diffbindfr_amd.packing import PackedBatch  # noqa: E402
+from diffbindfr_amd import vina  # noqa: E402
 from oracle import score_model as sm  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -33,30 +31,9 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 
 
-def timed(fn):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
-
-
-d = synthetic.make_batch(2, n_complex=args.complexes, poses=args.poses, seed=1)
-pb = PackedBatch(d, dev)
+rng = np.random.default_rng(0)              # the types first, the 3DBS frames below go on from there
+d, pb, types, pairs = benchkit.vina_typed_batch(args.complexes, args.poses, dev, rng)
 G, NT = pb.G, pb.dims["NTOR"]
-rng = np.random.default_rng(0)
-ei, tm = d.lig_edge_index.numpy(), d.tor_edge_mask.numpy().astype(bool)
-lp = pb.lig_ptr_host.long()
-types, pairs = [], []
-for g in range(G):
-    n = int(lp[g + 1] - lp[g])
-    types.append(np.array([vina.XS[t] for t in rng.choice(["C_H", "C_P", "N_A", "N_D", "O_A", "O_DA"], n)], np.int8))
-    sel = (ei[0] >= lp[g].item()) & (ei[0] < lp[g + 1].item())
-    pairs.append(vina.intra_pairs(n, ei[:, sel] - lp[g].item(), tm[sel]))
 
 # sampling of the same batch (positions restored after every run)
 mcfg = sm.default_cfg()
@@ -76,10 +53,10 @@ def sample():
     return samp.sample_packed(pb, z)
 
 
-t_sample, _ = timed(sample)
+t_sample, _ = benchkit.timed(sample, args.reps)
 vb = vina.VinaBatch(pb, types, pairs)       # scores the sampled poses
-t_score, _ = timed(vb.score)
-t_min, (pos, terms, iters) = timed(vb.minimize)
+t_score, _ = benchkit.timed(vb.score, args.reps)
+t_min, (pos, terms, iters) = benchkit.timed(vb.minimize, args.reps)
 it = iters.cpu().numpy()
 
 # 3DBS x 40 poses against the whole protein
@@ -92,9 +69,9 @@ for _ in range(args.poses):
     dd = rng.normal(size=3)
     frames.append((xc - c) @ tv._rot(rng.normal(size=3), 10.0).T + c + dd / np.linalg.norm(dd))
 e, _ = tv._3dbs_entry(np.stack(frames))
-t_3dbs, (_, t3, i3) = timed(lambda: vina.refine_entry(e))
+t_3dbs, (_, t3, i3) = benchkit.timed(lambda: vina.refine_entry(e), args.reps)
 
-print(json.dumps({
+benchkit.emit({
     "what": "Vina refinement (dbfr_vina_score / dbfr_vina_minimize, one workgroup per pose) next to the sampling of the same batch",
     "device": torch.cuda.get_device_name(0),
     "cfg2_batch": {"graphs": G, "ligand_atoms": pb.dims["NL"], "pocket_atoms": pb.dims["NA"], "torsions": NT,
@@ -104,4 +81,4 @@ print(json.dumps({
                    "objective_mean": float(terms[:, 6].mean())},
     "3dbs_x40": {"poses": args.poses, "refine_entry_s": round(t_3dbs, 4), "iters_mean": float(i3.float().mean()),
                  "affinity_mean": float(t3[:, 7].mean())},
-    "timing": f"wall clock around synchronised calls, median of {args.reps} after one warm-up"}))
+    "timing": f"wall clock around synchronised calls, median of {args.reps} after one warm-up"})

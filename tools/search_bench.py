@@ -2,7 +2,7 @@
 
     python tools/search_bench.py [--complexes 16] [--poses 40] [--chains 8] [--steps 64] [--reps 1] [--drift-poses 64] [--drift-steps 1024]
 
-Prints one JSON line.  For a cfg-2-shape batch (16 complexes x 40 poses = 640 graphs, the inputs of tools/refine_bench.py) and for
+Prints one JSON line.  For a cfg-2-shape batch (16 complexes x 40 poses = 640 graphs, benchkit.vina_typed_batch) and for
 the 3DBS fixture with 40 poses (the crystal pose moved by 1 A and 10 degrees): the time of one search (chains x steps), its BFGS
 steps, the share of accepted Monte-Carlo steps, the mean objective of the minimised and of the searched poses and the number of
 poses the search improved by more than 0.1 kcal/mol.  Then the largest bond-length drift of a chain's current pose (which is the
@@ -11,7 +11,6 @@ base of `rebuild` after every accepted step) and of its best pose after --steps 
 repetitions after a one-step warm-up.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -22,8 +21,8 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from diffbindfr_amd import synthetic, vina  # noqa: E402
-from diffbindfr_amd.packing import PackedBatch  # noqa: E402
+import benchkit  # noqa: E402
+from diffbindfr_amd import vina  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--complexes", type=int, default=16)
@@ -37,22 +36,10 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 
 
-def timed(fn, warm):
-    warm()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
-
-
 def report(vb, n_atoms):
-    t_min, (_, mt, mi) = timed(vb.minimize, vb.minimize)
-    t, r = timed(lambda: vb.search(chains=args.chains, n_steps=args.steps),
-                 lambda: vb.search(chains=args.chains, n_steps=1))
+    t_min, (_, mt, mi) = benchkit.timed(vb.minimize, args.reps)
+    t, r = benchkit.timed(lambda: vb.search(chains=args.chains, n_steps=args.steps), args.reps,
+                          warm=lambda: vb.search(chains=args.chains, n_steps=1))
     gain = (mt[:, 6] - r["terms"][:, 6]).cpu().numpy()
     return {"poses": int(mt.shape[0]), "chains": args.chains, "steps": args.steps, "search_s": round(t, 4), "minimize_s": round(t_min, 5),
             "search_over_minimize": round(t / t_min, 1), "bfgs_steps_minimize_mean": float(mi.float().mean()),
@@ -69,18 +56,7 @@ def bond_drift(pos, ref, src, dst):
 
 
 def cfg2_batch(n_complex):
-    """The cfg-2-shape batch of tools/refine_bench.py with its random ligand types."""
-    d = synthetic.make_batch(2, n_complex=n_complex, poses=args.poses, seed=1)
-    pb = PackedBatch(d, dev)
-    rng = np.random.default_rng(0)
-    ei, tm = d.lig_edge_index.numpy(), d.tor_edge_mask.numpy().astype(bool)
-    lp = pb.lig_ptr_host.long()
-    types, pairs = [], []
-    for g in range(pb.G):
-        n = int(lp[g + 1] - lp[g])
-        types.append(np.array([vina.XS[t] for t in rng.choice(["C_H", "C_P", "N_A", "N_D", "O_A", "O_DA"], n)], np.int8))
-        sel = (ei[0] >= lp[g].item()) & (ei[0] < lp[g + 1].item())
-        pairs.append(vina.intra_pairs(n, ei[:, sel] - lp[g].item(), tm[sel]))
+    d, pb, types, pairs = benchkit.vina_typed_batch(n_complex, args.poses, dev)
     return d, pb, vina.VinaBatch(pb, types, pairs)
 
 
@@ -119,7 +95,7 @@ ref = torch.as_tensor(z0["lig_pos"], dtype=torch.float32, device=dev)
 dbs["rmsd_to_crystal_searched_mean_A"] = float(((r3["lig"] - ref) ** 2).sum(-1).mean(-1).sqrt().mean())
 dbs["modes_over_all_optima"] = int((r3["modes"]["rank"] >= 0).sum())
 
-print(json.dumps({
+benchkit.emit({
     "what": "Monte-Carlo search (dbfr_vina_search, one workgroup per pose and chain) next to dbfr_vina_minimize on the same poses",
     "device": torch.cuda.get_device_name(0), "cfg2_batch": cfg2, "3dbs_x40": dbs, "bond_drift": drift,
-    "timing": f"wall clock around synchronised calls, median of {args.reps} after a one-step warm-up"}))
+    "timing": f"wall clock around synchronised calls, median of {args.reps} after a one-step warm-up"})

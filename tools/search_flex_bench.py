@@ -4,7 +4,7 @@ minimisation (dbfr_vina_flex_minimize) of the same poses.
     python tools/search_flex_bench.py [--complexes 16] [--poses 40] [--chains 8] [--steps 64] [--reps 1] [--flex-dist 3.5]
                                       [--max-flex-res 12] [--drift-poses 64] [--drift-steps 1024]
 
-Prints one JSON line.  For the cfg-2-shape batch of tools/refine_bench.py (16 complexes x 40 poses = 640 graphs; the flexible set of
+Prints one JSON line.  For the cfg-2-shape batch of benchkit.vina_typed_batch (16 complexes x 40 poses = 640 graphs; the flexible set of
 a pose: the eligible residues with a movable atom within --flex-dist A of a ligand atom, nearest first, at most --max-flex-res) and
 for the 3DBS fixture with 40 poses (the crystal pose moved by 1 A and 10 degrees; `select_flexible`): the time of one call of each
 of the three, their mean objective and E_rec, BFGS steps, the share of accepted Monte-Carlo steps, the poses either search improved
@@ -14,7 +14,6 @@ residue) of a chain's current and best pose after --steps and --drift-steps step
 chain.  Times are wall clock around synchronised calls, the median of --reps repetitions after a one-step warm-up.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -25,8 +24,8 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from diffbindfr_amd import synthetic, vina  # noqa: E402
-from diffbindfr_amd.packing import PackedBatch  # noqa: E402
+import benchkit  # noqa: E402
+from diffbindfr_amd import vina  # noqa: E402
 import vinaflex_cases as cases  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -43,24 +42,12 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 
 
-def timed(fn, warm):
-    warm()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts)), out
-
-
 def report(vb, fb):
     """The three calls on one batch."""
     so = dict(chains=args.chains, n_steps=args.steps)
-    t_min, (_, _, _, mt, mi) = timed(fb.minimize, fb.minimize)
-    t_rig, rr = timed(lambda: vb.search(**so), lambda: vb.search(chains=args.chains, n_steps=1))
-    t_flex, rf = timed(lambda: fb.search(**so), lambda: fb.search(chains=args.chains, n_steps=1))
+    t_min, (_, _, _, mt, mi) = benchkit.timed(fb.minimize, args.reps)
+    t_rig, rr = benchkit.timed(lambda: vb.search(**so), args.reps, warm=lambda: vb.search(chains=args.chains, n_steps=1))
+    t_flex, rf = benchkit.timed(lambda: fb.search(**so), args.reps, warm=lambda: fb.search(chains=args.chains, n_steps=1))
     gain = (mt[:, 6] - rf["terms"][:, 6]).cpu().numpy()
     nt = np.diff(fb.ftor_ptr)
     out = {"poses": int(mt.shape[0]), "chains": args.chains, "steps": args.steps,
@@ -81,21 +68,15 @@ def report(vb, fb):
 
 
 def cfg2_batch(n_complex):
-    """The cfg-2-shape batch of tools/refine_bench.py with its random ligand types, and a flexible set per pose."""
-    d = synthetic.make_batch(2, n_complex=n_complex, poses=args.poses, seed=1)
-    pb = PackedBatch(d, dev)
-    rng = np.random.default_rng(0)
-    ei, tm = d.lig_edge_index.numpy(), d.tor_edge_mask.numpy().astype(bool)
+    """benchkit.vina_typed_batch and a flexible set per pose."""
+    d, pb, types, pairs = benchkit.vina_typed_batch(n_complex, args.poses, dev)
     lp, apt, rp = (pb.t[k].cpu().long().numpy() for k in ("lig_ptr", "atm_ptr", "res_ptr"))
     tp = pb.t["tor_ptr"].cpu().long().numpy()
     seq, m14 = d.sequence.numpy(), d.atom14_mask.numpy().astype(bool)
     rec, lig = pb.t["rec_pos"].cpu().numpy(), pb.t["lig_pos"].cpu().numpy()
-    types, pairs, flex, bonds = [], [], [], []
+    flex, bonds = [], []
     for g in range(pb.G):
         n = int(lp[g + 1] - lp[g])
-        types.append(np.array([vina.XS[t] for t in rng.choice(["C_H", "C_P", "N_A", "N_D", "O_A", "O_DA"], n)], np.int8))
-        sel = (ei[0] >= lp[g]) & (ei[0] < lp[g + 1])
-        pairs.append(vina.intra_pairs(n, ei[:, sel] - lp[g], tm[sel]))
         x, xl = rec[apt[g]:apt[g + 1]], lig[lp[g]:lp[g + 1]]
         sets, topo = cases.residue_sets(seq[rp[g]:rp[g + 1]], m14[rp[g]:rp[g + 1]], x)
         near = np.array([np.linalg.norm(x[s["atoms"]][:, None] - xl[None], axis=-1).min() if s else np.inf for s in sets])
@@ -161,9 +142,9 @@ rows, _ = vina.select_flexible(e, e.ligand_traj[:, -1], e.protein_traj[:, -1], a
 fb3 = vina.VinaFlexBatch(vb3, vina._flex_sets(topo, [np.sort(r) for r in rows]))
 dbs, rr3, rf3 = report(vb3, fb3)
 ref = torch.as_tensor(z0["lig_pos"], dtype=torch.float32, device=dev)
-t_entry, r3 = timed(lambda: vina.search_entry_flex(e, flex_dist=args.flex_dist, max_flex_res=args.max_flex_res, exhaustiveness=args.chains,
-                                                   n_steps=args.steps, minimized=True),
-                    lambda: vina.search_entry_flex(e, exhaustiveness=1, n_steps=1))
+t_entry, r3 = benchkit.timed(lambda: vina.search_entry_flex(e, flex_dist=args.flex_dist, max_flex_res=args.max_flex_res,
+                                                            exhaustiveness=args.chains, n_steps=args.steps, minimized=True), args.reps,
+                             warm=lambda: vina.search_entry_flex(e, exhaustiveness=1, n_steps=1))
 heavy = torch.as_tensor(np.asarray(z0["ha_mask"], bool), device=dev)
 rmsd_h = lambda lig: float(((lig[:, heavy] - ref[heavy]) ** 2).sum(-1).mean(-1).sqrt().mean())
 a14 = e.protein_traj[:, -1]
@@ -174,8 +155,8 @@ dbs.update({"search_entry_flex_s": round(t_entry, 4),
                                               "flex_search": float((r3["atom14"] - a14).norm(dim=-1).max())},
             "modes_over_all_optima": int((r3["modes"]["rank"] >= 0).sum())})
 
-print(json.dumps({
+benchkit.emit({
     "what": "Monte-Carlo search with flexible side chains (dbfr_vina_flex_search, k_vina_search<122>, one workgroup per pose and chain) "
             "next to dbfr_vina_search and dbfr_vina_flex_minimize on the same poses",
     "device": torch.cuda.get_device_name(0), "cfg2_batch": cfg2, "3dbs_x40": dbs, "bond_drift": drift,
-    "timing": f"wall clock around synchronised calls, median of {args.reps} after a one-step warm-up"}))
+    "timing": f"wall clock around synchronised calls, median of {args.reps} after a one-step warm-up"})

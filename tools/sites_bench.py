@@ -14,10 +14,8 @@ site found; *_over_sample are the ratios.
 """
 import argparse
 import ctypes as C
-import json
 import os
 import sys
-import time
 
 import numpy as np
 import torch
@@ -25,10 +23,8 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import bench  # noqa: E402
-import diffbindfr_amd as dba  # noqa: E402
-from diffbindfr_amd import lib as L, sites, synthetic  # noqa: E402
-from diffbindfr_amd.packing import PackedBatch  # noqa: E402
+import benchkit  # noqa: E402
+from diffbindfr_amd import lib as L, posecheck, sites  # noqa: E402
 import sites_ref  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -38,32 +34,6 @@ ap.add_argument("--n", type=int, default=2000)
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_sites_bench.json"))
 args = ap.parse_args()
 dev = torch.device("cuda:0")
-
-
-def median_wall(fn):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append(time.perf_counter() - t0)
-    return float(np.median(ts))
-
-
-def median_events(fn):
-    fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(args.reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) / 1e3)
-    return float(np.median(ts))
 
 
 def stage(recs):
@@ -94,7 +64,7 @@ def library_calls(aa, pos, msk, rp):
     L.check(lib.dbfr_sites_workspace_bytes(C.byref(L.SitesIn(n_prot=max(e - s for s, e, _ in chunks), n_res=len(aa), max_points=cap)),
                                            C.byref(nb)))
     ws = torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
-    rad = torch.as_tensor(dba.posecheck.receptor_radius_table(), device=dev).contiguous()
+    rad = torch.as_tensor(posecheck.receptor_radius_table(), device=dev).contiguous()
     aa32 = aa.int().contiguous()
     opts = sites._c_opts(o)
     calls, keep = [], [ws, rad, aa32]
@@ -117,35 +87,17 @@ def library_calls(aa, pos, msk, rp):
     return run, len(chunks), sum(npts)
 
 
-def sample_seconds_per_pose(cfg_id):
-    d = synthetic.make_batch(cfg_id, n_complex=16, poses=40, seed=1)
-    pb = PackedBatch(d, dev)
-    G = pb.G
-    samp = dba.DiffBindFRHIP(diffusion_model=bench.seeded_params().to(dev), test_cfg={"sample_cfg": {"actual_steps": args.steps}})
-    gen = torch.Generator().manual_seed(3)
-    z = {"tr": torch.randn(args.steps, G, 3, generator=gen), "rot": torch.randn(args.steps, G, 3, generator=gen),
-         "tor": torch.randn(args.steps, max(pb.dims["NTOR"], 1), generator=gen),
-         "sc": torch.randn(args.steps, max(pb.dims["NSC"], 1), generator=gen)}
-    z = {k: v.to(dev).contiguous() for k, v in z.items()}
-    lig0, rec0, tor0 = pb.lig_pos.clone(), pb.rec_pos.clone(), pb.torsion_angle.clone()
-
-    def run():
-        pb.lig_pos.copy_(lig0), pb.rec_pos.copy_(rec0), pb.torsion_angle.copy_(tor0)
-        return samp.sample_packed(pb, z)
-    return median_wall(run) / G
-
-
 recs = sites_ref.load_receptors(os.path.join(ROOT, "tests", "golden", "sites_receptors.npz"))
 legs = {"3dbs": recs[:1], "six": recs, "tiled": [recs[k % 6] for k in range(args.n)]}
 res = {"what": "binding-site detection (dbfr_find_sites) next to sampling 40 poses per site found",
        "device": torch.cuda.get_device_name(0)}
-per_pose = sample_seconds_per_pose(4)
+per_pose = benchkit.sample_seconds_per_pose(4, args.steps, args.reps, dev)
 for name, rr in legs.items():
     aa, pos, msk, rp = stage(rr)
     run, n_launch, n_points = library_calls(aa, pos, msk, rp)
-    t_call = median_events(run)
+    t_call = benchkit.events(run, args.reps)[0]
     found = []
-    t_wall = median_wall(lambda: found.__setitem__(slice(None), sites.find_sites(aa, pos, msk, res_ptr=rp)))
+    t_wall = benchkit.wall(lambda: found.__setitem__(slice(None), sites.find_sites(aa, pos, msk, res_ptr=rp)), args.reps)
     n_sites = sum(len(x) for x in found)
     sample_s = per_pose * 40 * n_sites
     res[name] = {"receptors": len(rr), "grid_points": int(n_points), "launches": n_launch, "sites_kept": n_sites,
@@ -159,6 +111,4 @@ res["timing"] = (f"call: HIP events around the dbfr_find_sites calls of the leg 
                  f"{args.reps} after one warm-up; find_sites: wall clock, synchronised, median of {args.reps}; sampling: {args.steps} "
                  f"steps of a 640-pose batch of synthetic config 4, per pose, scaled to 40 poses per site kept")
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-with open(args.out, "w") as f:
-    f.write(json.dumps(res) + "\n")
-print(json.dumps(res))
+benchkit.emit(res, args.out)

@@ -40,6 +40,14 @@ def rel_err(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp(min=1e-30))
 
 
+def molblock(sym, bonds, pos):
+    """A V2000 SD record of the atoms sym at pos; bonds: (a, b) for a single bond or (a, b, order), 0-based."""
+    lines = ["lig", "  test", "", f"{len(sym):3d}{len(bonds):3d}  0  0  0  0  0  0  0  0999 V2000"]
+    lines += [f"{x:10.4f}{y:10.4f}{z:10.4f} {s:<3s} 0  0  0  0  0  0  0  0  0  0  0  0" for (x, y, z), s in zip(pos, sym)]
+    lines += [f"{a + 1:3d}{b + 1:3d}{o[0] if o else 1:3d}  0" for a, b, *o in bonds]
+    return "\n".join(lines + ["M  END", "$$$$", ""])
+
+
 def oracle_batch_from_packed(raw_records, poses, pb):
     """Reference-format collated batch (oracle.pose_init.collate) whose graphs start from the very poses the device
     produced in ``pb`` (after ``assemble`` + ``init_poses``).  ``raw_records``: the per-complex record dicts the

@@ -14,8 +14,6 @@ compaction tile), a candidate list that fills, a group without static atoms and 
 always passes a `static_ptr`, all zeros for a batch without static atoms: a NULL `static_ptr` cannot be reached from Python, so
 "no static atoms" is pinned here as S = 0 and the NULL form of the host walk in tests/test_frame_kernels_host.py.)"""
 import functools
-import hashlib
-import json
 import os
 import sys
 
@@ -29,7 +27,7 @@ for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
         sys.path.insert(0, p)
 
 from diffbindfr_amd import apoholo, interactions, pocketcheck, posecheck, sasa
-from diffbindfr_amd import lib as L
+from tests import pinned
 
 import apoholo_ref  # noqa: E402  (modules next to the test files)
 import interactions_ref  # noqa: E402
@@ -110,15 +108,8 @@ def _outputs(module, case):
     return {k: host(v) for k, v in posecheck.check([_dev(g) for g in groups], cand_cap=cap).items()}
 
 
-def _sha(v):
-    h = hashlib.sha256()
-    for x in v if isinstance(v, list) else [v]:
-        h.update(np.ascontiguousarray(x).tobytes())
-    return h.hexdigest()
-
-
 def _hashes(module, case):
-    return {k: _sha(v) for k, v in sorted(_outputs(module, case).items())}
+    return {k: pinned.sha(v) for k, v in sorted(_outputs(module, case).items())}
 
 
 def _counts(gr):
@@ -179,7 +170,7 @@ def test_the_batches_hold_what_the_shared_pieces_can_go_wrong_on():
 
 @pytest.fixture(scope="module")
 def golden():
-    return json.load(open(GOLDEN))["sha256"]
+    return pinned.load(GOLDEN)
 
 
 @pytest.mark.parametrize("module,case", CASES)
@@ -199,10 +190,8 @@ def record(path):
            "tests/test_frame_kernels_pinned_gpu.py, recorded on an MI355X with `python tests/test_frame_kernels_pinned_gpu.py --record "
            "<this file>` in a checkout of the commit before csrc/frames.h and diffbindfr_amd/frames.py existed (its Python modules and "
            "the library built from it, build id below), with this file and tests/posecheck_ref.py copied in")
-    json.dump({"how": how, "library_build_id": L.load().dbfr_build_id().decode(), "sha256": sha}, open(path, "w"), indent=1)
-    print(open(path).read())
+    pinned.write(path, how, sha)
 
 
 if __name__ == "__main__":
-    assert len(sys.argv) == 3 and sys.argv[1] == "--record", __doc__
-    record(sys.argv[2])
+    pinned.main(record, __doc__)

@@ -4,7 +4,6 @@
      BASELINE.json shapes (SE(3) equivariance of the scores, graph-permutation invariance).
 Tolerances (fp32 path, stated per test): scores relative 1e-4 of the per-output max (achieved
 ~1e-6); poses 1e-3 A after 20 steps (achieved ~2e-4 A)."""
-import contextlib
 import copy
 import ctypes as C
 
@@ -19,21 +18,10 @@ from diffbindfr_amd import lib as L, synthetic
 from diffbindfr_amd.packing import PackedBatch
 from oracle import e3nn_lite as o3, sampler as osampler, schedule as osched, score_model as sm
 from oracle.cluster import scatter
+from tests.conv_hook import (DEFAULT_GEMM, SPAN, chunk_starts, device_inputs, gemm, layout, node_sums, run as run_conv_hook)
 from tests.helpers import load_golden_batch, namespace_to, rel_err
 
 SCORE_RTOL = 1e-4
-
-
-def _default_gemm():
-    """Name of include/dbfr.h's DBFR_GEMM_DEFAULT (what a model runs in when nobody sets a mode)."""
-    import os, re
-    from diffbindfr_amd.score_model import GEMM_MODES
-    hdr = open(os.path.join(os.path.dirname(__file__), "..", "include", "dbfr.h")).read()
-    d = dict(re.findall(r"#define (DBFR_GEMM_[A-Z0-9_]+) (\w+)", hdr))
-    return {v: k for k, v in GEMM_MODES.items()}[int(d[d["DBFR_GEMM_DEFAULT"]])]
-
-
-DEFAULT_GEMM = _default_gemm()
 POSE_ATOL = 1e-3
 
 
@@ -54,20 +42,6 @@ def setup(dev):
 
 def hip_scores(model, d, dev):
     return model(namespace_to(d, dev))
-
-
-@contextlib.contextmanager
-def gemm(model, mode):
-    """Run a block with the radial MLP's big GEMM on the fp32 matrix instruction ("f32": k_conv / k_conv2) or on the bf16 one
-    (round 2's three-bf16-piece kernel, "split", was retired in round 5), or on the fp16 one with two-piece operands ("split_f16":
-    k_conv2h; "reduce_first": k_convz for the scalar-output rows, reduced over a target's edges BEFORE the big GEMM, + k_conv2h for the
-    vector-output rows); include/dbfr.h: dbfr_model_set_gemm."""
-    before = model.gemm
-    model.set_gemm(mode)
-    try:
-        yield
-    finally:
-        model.set_gemm(before if before is not None else DEFAULT_GEMM)
 
 
 @pytest.fixture(params=["split_f16", "f32", "reduce_first"])
@@ -432,7 +406,7 @@ def _fused_conv_and_reduce(setup, dev, layer, fam, name, kernel):
         sl = o3.Irreps(o).slices()
         first = torch.ones(E, dtype=torch.bool)
         first[1:] = tgt[1:] != tgt[:-1]
-        first[torch.tensor(_hook_chunk_starts(tgt))] = True          # (the hook's chunks: <= 32 edges and <= 4 targets each)
+        first[torch.tensor(chunk_starts(tgt))] = True          # (the hook's chunks: <= 32 edges and <= 4 targets each)
         for k, mir in enumerate(o3.Irreps(o)):
             if mir.ir.l == 0:
                 assert float(mh[~first][:, sl[k]].abs().max()) == 0.0
@@ -633,29 +607,6 @@ def test_the_documented_size_limits(setup, dev):
             hip_scores(model, d, dev)
 
 
-def _random_conv_inputs(dev, layer, E):
-    Din = [48, 84, 120, 168][min(layer, 3)] if layer >= 0 else 168
-    Dout = [84, 120, 168, 168][min(layer, 3)] if layer >= 0 else 96
-    g = torch.Generator(device=dev).manual_seed(100 + E)
-    N = max(E // 9, 8)
-    x, xt = torch.randn(N, Din, device=dev, generator=g), torch.randn(N, max(Din, 48), device=dev, generator=g)
-    tgt = torch.sort(torch.randint(0, N, (E,), device=dev, generator=g)).values.to(torch.int32)
-    gth = torch.randint(0, N, (E,), device=dev, generator=g).to(torch.int32)
-    emb, sh = torch.randn(E, 48, device=dev, generator=g), torch.randn(E, 9, device=dev, generator=g)
-    return dict(x=x, xt=xt, tgt=tgt, gth=gth, emb=emb, sh=sh, Din=Din, Dout=Dout)
-
-
-def _run_conv_hook(fn, h, layer, fam, c, E, dev):
-    """One fused conv over the first E edges of the inputs c through a C-ABI test hook; messages [E, Dout]."""
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    ne = torch.tensor([E], dtype=torch.int32, device=dev)
-    msg = torch.full((E, c["Dout"]), float("nan"), device=dev)
-    L.check(fn(h, layer, fam, E, ptr(ne), ptr(c["tgt"]), ptr(c["gth"]), ptr(c["emb"]), ptr(c["sh"]), ptr(c["xt"]), c["xt"].shape[1],
-               ptr(c["tgt"]), ptr(c["x"]), c["Din"], ptr(c["gth"]), ptr(c["x"]), c["Din"], ptr(msg), None))
-    torch.cuda.synchronize()
-    return msg
-
-
 @pytest.mark.gpu
 def test_split_f16_vanishing_weights_next_to_an_ordinary_bias(setup, dev):
     """A conv whose lin.3 weights are 1e-30 of their usual size while its bias is not: the run factors of the W2h tiles stop where the
@@ -669,11 +620,11 @@ def test_split_f16_vanishing_weights_next_to_an_ordinary_bias(setup, dev):
     model.load_state_dict(p2, strict=True)
     lib, h = L.load(), model.handle(dev)
     layer, fam, E = 3, 2, 6000
-    c = _random_conv_inputs(dev, layer, E)
+    c = device_inputs(dev, layer, E)
     with gemm(model, "f32"):
-        ref = _run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
+        ref = run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
     with gemm(model, "split_f16"):
-        a = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
+        a = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
     assert torch.isfinite(a).all() and torch.isfinite(ref).all() and float(ref.abs().max()) > 1e-3
     assert float((a - ref).abs().max()) <= 2e-6 * float(ref.abs().max())
 
@@ -688,9 +639,9 @@ def test_k_conv2_equals_k_conv_bitwise(setup, dev, layer, fam, E):
     k_conv: both keep the channel-owner summation order."""
     mcfg, p, model = setup
     lib, h = L.load(), model.handle(dev)
-    c = _random_conv_inputs(dev, layer, E)
+    c = device_inputs(dev, layer, E)
     with gemm(model, "f32"):
-        outs = [_run_conv_hook(fn, h, layer, fam, c, E, dev) for fn in (lib.dbfr_test_conv, lib.dbfr_test_conv2)]
+        outs = [run_conv_hook(fn, h, layer, fam, c, E, dev) for fn in (lib.dbfr_test_conv, lib.dbfr_test_conv2)]
     assert torch.isfinite(outs[1]).all()                     # every message element was written exactly by its owner
     assert torch.equal(outs[0], outs[1])
 
@@ -704,59 +655,27 @@ def test_split_kernels_match_k_conv_and_are_unit_independent(setup, dev, layer, 
     unit boundaries, another split of the last round -- gives the very same bits for those edges)."""
     mcfg, p, model = setup
     lib, h = L.load(), model.handle(dev)
-    c = _random_conv_inputs(dev, layer, E)
-    ref = _run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
+    c = device_inputs(dev, layer, E)
+    ref = run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
     with gemm(model, mode):
-        a = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
-        b = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
+        a = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
+        b = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
         E3 = E // 3
-        part = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E3, dev)
+        part = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E3, dev)
     assert torch.isfinite(a).all()
     assert rel_err(a, ref) < 2e-6
     assert torch.equal(a, b)
     assert torch.equal(part, a[:E3])
 
 
-def _hook_chunk_starts(tgt, span=2048, max_edges=32, max_targets=4):
-    """First edge of every chunk the single-conv hooks cut a flat, target-sorted edge list into for DBFR_GEMM_REDUCE_FIRST (graph.hip chunk_len,
-    api.cpp test_conv_impl): the list is cut every `span` edges as if those were graphs; inside a span a chunk takes consecutive edges until it
-    holds 32 of them or the 5th target would begin (CZ_MAXSEG = 4)."""
-    t = tgt.tolist()
-    E, starts, es = len(t), [], 0
-    while es < E:
-        hi = min((es // span + 1) * span, E)
-        starts.append(es)
-        n, runs = 1, 1
-        while es + n < hi and n < max_edges:
-            if t[es + n] != t[es + n - 1]:
-                if runs == max_targets:
-                    break
-                runs += 1
-            n += 1
-        es += n
-    return starts
-
-
 @pytest.mark.parametrize("case", ["random", "one_target", "all_distinct", "runs_of_9", "empty", "span_edge"])
 def test_chunk_table_follows_the_rule(dev, case):
     """The chunk table k_convz walks (graph.hip chunk_len / k_flat_chunk_*, the same walk as the sampler's per-graph kernels) against the rule stated in
-    docs/kernels/conv_reduce_first.md, restated in Python (`_hook_chunk_starts`): consecutive edges, at most 32 and at most four targets per chunk,
+    docs/kernels/conv_reduce_first.md, restated in Python (tests/conv_hook.py `chunks`): consecutive edges, at most 32 and at most four targets per chunk,
     a new chunk at every span boundary; every edge lies in exactly one chunk."""
-    g = torch.Generator().manual_seed(3)
-    span = 2048
-    E = {"random": 9000, "one_target": 300, "all_distinct": 500, "runs_of_9": 4097, "empty": 0, "span_edge": 2 * span}[case]
-    if case == "random":
-        tgt = torch.sort(torch.randint(0, 700, (E,), generator=g)).values
-    elif case == "one_target":
-        tgt = torch.zeros(E, dtype=torch.int64)
-    elif case == "all_distinct":
-        tgt = torch.arange(E)
-    elif case == "runs_of_9":
-        tgt = torch.arange(E) // 9
-    elif case == "span_edge":
-        tgt = torch.arange(E) // 40                       # a target straddles the span boundary
-    else:
-        tgt = torch.zeros(0, dtype=torch.int64)
+    span = SPAN
+    tgt = layout(case, span)
+    E = len(tgt)
     lib = L.load()
     cap = E // 32 + E // 4 + E // span + 16
     n_span = max((E + span - 1) // span, 1)
@@ -768,7 +687,7 @@ def test_chunk_table_follows_the_rule(dev, case):
     L.check(lib.dbfr_test_chunk_table(ptr(tgtd), ptr(ned), E, span, ptr(scratch), cap, ptr(ces), ptr(cgl), None))
     torch.cuda.synchronize()
     n = int(scratch[n_span])
-    want = _hook_chunk_starts(tgt, span=span)
+    want = chunk_starts(tgt, span=span)
     assert n == len(want)
     if n == 0:
         assert E == 0
@@ -780,10 +699,6 @@ def test_chunk_table_follows_the_rule(dev, case):
         assert len(torch.unique(tgt[a:a + b])) <= 4
 
 
-def _node_sums(m, tgt, n):
-    return torch.zeros(n, m.shape[1], dtype=torch.float64).index_add_(0, tgt.cpu().long(), m.cpu().double())
-
-
 @pytest.mark.parametrize("layer,fam,E", CONV_CASES)
 def test_reduce_first_matches_k_conv_and_is_unit_independent(setup, dev, layer, fam, E):
     """DBFR_GEMM_REDUCE_FIRST (k_convz + k_conv2h on the vector-output rows) against k_conv (fp32 matrix instruction) on the same random
@@ -793,16 +708,16 @@ def test_reduce_first_matches_k_conv_and_is_unit_independent(setup, dev, layer, 
     same bits for every message row of the nodes it holds completely."""
     mcfg, p, model = setup
     lib, h = L.load(), model.handle(dev)
-    c = _random_conv_inputs(dev, layer, E)
-    ref = _run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
+    c = device_inputs(dev, layer, E)
+    ref = run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
     with gemm(model, "reduce_first"):
-        a = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
-        b = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
-        E3 = max(e for e in _hook_chunk_starts(c["tgt"].cpu()) if e <= E // 3)   # (a chunk boundary of the full run: the chunks in front of it are the same)
-        part = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E3, dev)
+        a = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
+        b = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
+        E3 = max(e for e in chunk_starts(c["tgt"].cpu()) if e <= E // 3)   # (a chunk boundary of the full run: the chunks in front of it are the same)
+        part = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E3, dev)
     assert torch.isfinite(a).all()
     n = int(c["tgt"].max()) + 1
-    sa, sr = _node_sums(a, c["tgt"], n), _node_sums(ref, c["tgt"], n)
+    sa, sr = node_sums(a, c["tgt"], n), node_sums(ref, c["tgt"], n)
     assert float((sa - sr).abs().max() / sr.abs().max()) < 4e-6
     assert torch.equal(a, b)
     assert torch.equal(part, a[:E3])
@@ -819,7 +734,7 @@ def test_reduce_first_accuracy_against_float64(setup, dev):
     for name, layer, fam, E, outlier in (("atom_conv_layers.3", 3, 2, 600, 0), ("lig_conv_layers.0", 0, 0, 600, 0), ("tor_bond_conv", -2, 0, 600, 0),
                                          ("atom_conv_layers.3", 3, 2, 600, 1), ("lig_conv_layers.0", 0, 0, 600, 2)):
         i, shirr, o, nef = sm.conv_specs(mcfg)[name]
-        c = _random_conv_inputs(dev, layer, E)
+        c = device_inputs(dev, layer, E)
         if outlier == 1:      # ONE gathered node whose features are 3e4 x the others': the y scale is taken per chunk (per graph in the model), so every
             c["x"] = c["x"].clone(); c["x"][5] *= 3e4      # other edge of that chunk is cut into fp16 pieces 15 binades below the largest
         if outlier == 2:      # ... and one radial-MLP input row (the target's scalar features) 1e4 x the others': the per-edge input scale and the chunk's h scale
@@ -833,13 +748,13 @@ def test_reduce_first_accuracy_against_float64(setup, dev):
         shf = sh if "tor" not in name else sh[:, :o3.Irreps(shirr).dim]
         m64 = sm._tp(i, shirr, o)(x[gth], shf, sm.simple_linear(p64, f"{name}.fc", a64))
         n = int(tgt.max()) + 1
-        s64 = _node_sums(m64, tgt, n)
+        s64 = node_sums(m64, tgt, n)
         col = s64.abs().amax(dim=0).clamp_min(1e-300)
         res = {}
         for mode, fn in (("f32", lib.dbfr_test_conv), ("reduce_first", lib.dbfr_test_conv2)):
             with gemm(model, mode):
-                m = _run_conv_hook(fn, h, layer, fam, c, E, dev)
-            dm = (_node_sums(m, tgt, n) - s64) / col
+                m = run_conv_hook(fn, h, layer, fam, c, E, dev)
+            dm = (node_sums(m, tgt, n) - s64) / col
             res[mode] = (float(dm.abs().max()), float(dm.pow(2).mean().sqrt()))
         print(name, "outlier" if outlier else "", "node sums vs float64 (max, rms per column):", res)
         assert res["reduce_first"][0] < (2e-6 if not outlier else 2e-5), (name, res)
@@ -856,7 +771,7 @@ def test_split_gemm_is_no_less_accurate_than_the_fp32_matrix_instruction(setup, 
     lib, h = L.load(), model.handle(dev)
     name, layer, fam, E = "atom_conv_layers.3", 3, 2, 600
     i, shirr, o, nef = sm.conv_specs(mcfg)[name]
-    c = _random_conv_inputs(dev, layer, E)
+    c = device_inputs(dev, layer, E)
     c["sh"] = o3.spherical_harmonics(shirr, torch.randn(E, 3, generator=torch.Generator().manual_seed(4)), True, "component").to(dev).contiguous()
     x, xt, emb, sh = (c[k].cpu().double() for k in ("x", "xt", "emb", "sh"))
     tgt, gth = c["tgt"].cpu().long(), c["gth"].cpu().long()
@@ -867,7 +782,7 @@ def test_split_gemm_is_no_less_accurate_than_the_fp32_matrix_instruction(setup, 
     err, rms = {}, {}
     for mode, fn in (("f32", lib.dbfr_test_conv), ("split_f16", lib.dbfr_test_conv2)):
         with gemm(model, mode):
-            m = _run_conv_hook(fn, h, layer, fam, c, E, dev)
+            m = run_conv_hook(fn, h, layer, fam, c, E, dev)
         dm = m.cpu().double() - m64
         err[mode] = float(dm.abs().max() / m64.abs().max())
         rms[mode] = float(dm.pow(2).mean().sqrt() / m64.pow(2).mean().sqrt())
@@ -1118,7 +1033,7 @@ def test_default_gemm_on_weights_nobody_has_seen(dev, dist):
         res = {}
         for mode, fn in (("f32", lib.dbfr_test_conv), ("split_f16", lib.dbfr_test_conv2)):
             with gemm(model, mode):
-                m = _run_conv_hook(fn, h, layer, fam, c, E, dev)
+                m = run_conv_hook(fn, h, layer, fam, c, E, dev)
             assert torch.isfinite(m).all(), (name, mode)
             dm = (m.cpu().double() - m64) / col
             res[mode] = (float(dm.abs().max()), float(dm.pow(2).mean().sqrt()))
@@ -1126,14 +1041,14 @@ def test_default_gemm_on_weights_nobody_has_seen(dev, dist):
         # what is compared is what the scatter defines -- the per-node sums -- per output column, next to those of the fp32 instruction; the gate of
         # test_reduce_first_accuracy_against_float64 (2.5 x rms / 4 x max of the fp32 instruction's, measured 1.1-1.8 / 1.5-2.5) on every distribution
         # (the fixed Z scale 2^-20, the per-chunk y / h scales and the per-output-row W2' factors had seen seeded weights only)
-        s64 = _node_sums(m64, tgt, N)
+        s64 = node_sums(m64, tgt, N)
         coln = s64.abs().amax(dim=0).clamp_min(1e-300)
         resn = {}
         for mode, fn in (("f32", lib.dbfr_test_conv), ("reduce_first", lib.dbfr_test_conv2)):
             with gemm(model, mode):
-                m = _run_conv_hook(fn, h, layer, fam, c, E, dev)
-            assert torch.isfinite(_node_sums(m, tgt, N)).all(), (name, mode)
-            dn = (_node_sums(m, tgt, N) - s64) / coln
+                m = run_conv_hook(fn, h, layer, fam, c, E, dev)
+            assert torch.isfinite(node_sums(m, tgt, N)).all(), (name, mode)
+            dn = (node_sums(m, tgt, N) - s64) / coln
             resn[mode] = (float(dn.abs().max()), float(dn.pow(2).mean().sqrt()))
         print(f"  {dist:10s} {name:24s} node sums: f32 {resn['f32'][0]:.2e} / {resn['f32'][1]:.2e}   reduce_first {resn['reduce_first'][0]:.2e} / {resn['reduce_first'][1]:.2e}")
         assert resn["reduce_first"][1] <= 2.5 * resn["f32"][1] + 2e-8 and resn["reduce_first"][0] <= 4.0 * resn["f32"][0] + 1e-7, (name, resn)
@@ -1169,7 +1084,7 @@ def test_split_f16_scales_its_operands_per_edge(setup, dev, scale):
     mcfg, p, model = setup
     lib, h = L.load(), model.handle(dev)
     layer, fam, E = 3, 2, 9000
-    c = _random_conv_inputs(dev, layer, E)
+    c = device_inputs(dev, layer, E)
     if scale == "ragged":        # every edge its own magnitude: 10^-4 .. 10^4 (emb is per edge; the gathered rows follow their nodes)
         g = torch.Generator(device=dev).manual_seed(5)
         c["emb"] = c["emb"] * torch.pow(10.0, 8 * torch.rand(E, 1, device=dev, generator=g) - 4)
@@ -1178,9 +1093,9 @@ def test_split_f16_scales_its_operands_per_edge(setup, dev, scale):
         c["emb"], c["xt"] = c["emb"] * scale, c["xt"] * scale
         c["x"] = c["x"] * scale                                  # (x also feeds the radial MLP as its third input block)
     with gemm(model, "f32"):
-        ref = _run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
+        ref = run_conv_hook(lib.dbfr_test_conv, h, layer, fam, c, E, dev)
     with gemm(model, "split_f16"):
-        a = _run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
+        a = run_conv_hook(lib.dbfr_test_conv2, h, layer, fam, c, E, dev)
     assert torch.isfinite(a).all() and torch.isfinite(ref).all()
     # per edge: messages of differently scaled edges differ by orders of magnitude, so the error is taken relative to each edge's own size
     err = (a - ref).abs().amax(dim=1) / ref.abs().amax(dim=1).clamp_min(1e-30)

@@ -9,6 +9,7 @@ import torch
 from diffbindfr_amd import export as pex, ligand, modes, synthetic, vina
 
 import modes_ref  # noqa: E402  (a module next to the test files: pytest puts their directory on sys.path)
+from tests.helpers import molblock
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -164,13 +165,6 @@ def test_selection_refuses_bad_options_and_large_groups():
 
 
 # ------------------------------------------------------------------------------------------------ end to end
-def _molblock(sym, bonds, pos):
-    lines = ["lig", "  test", "", f"{len(sym):3d}{len(bonds):3d}  0  0  0  0  0  0  0  0999 V2000"]
-    lines += [f"{x:10.4f}{y:10.4f}{z:10.4f} {s:<3s} 0  0  0  0  0  0  0  0  0  0  0  0" for (x, y, z), s in zip(pos, sym)]
-    lines += [f"{a + 1:3d}{b + 1:3d}  1  0" for a, b in bonds]
-    return "\n".join(lines + ["M  END", "$$$$", ""])
-
-
 def _sampled_entries(n_complex=2, poses=8):
     """A small config-2-shaped batch sampled on the device (seeded weights) as export.ComplexOutput entries: the pocket is
     the whole protein, the frame is the sampler's (centre 0), the ligand an SD record of the synthetic graph."""
@@ -208,7 +202,7 @@ def _sampled_entries(n_complex=2, poses=8):
         sym[rng.random(n) < 0.2] = "N"
         ei = lg["lig_edge_index"]
         bonds = [(int(a), int(b)) for a, b in ei.T if a < b]
-        mb = _molblock(sym, bonds, cr.lig_pos.numpy())
+        mb = molblock(sym, bonds, cr.lig_pos.numpy())
         entries.append(pex.ComplexOutput(name=f"set:c{k}", ligand_traj=lig_traj, protein_traj=prot_traj, pocket_center_pos=np.zeros(3),
                                          ligand_pos=cr.lig_pos.numpy(), ligand_labels=np.array([{"C": 6, "N": 7}[s] for s in sym]),
                                          ligand_edge_index=ei, topology=topo, atom14_position=a14, atom14_mask=m14, aatype=seq,

@@ -10,6 +10,7 @@ from diffbindfr_amd import lib as L
 from diffbindfr_amd import ligand, posecheck
 
 import posecheck_ref  # noqa: E402
+from tests.helpers import molblock
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -18,13 +19,6 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 def _fixtures():
     z = np.load(os.path.join(GOLDEN, "posecheck_ligands.npz"))
     return {k: str(z[k]) for k in z.files}
-
-
-def _molblock(sym, bonds, pos):
-    lines = ["lig", "  test", "", f"{len(sym):3d}{len(bonds):3d}  0  0  0  0  0  0  0  0999 V2000"]
-    lines += [f"{x:10.4f}{y:10.4f}{z:10.4f} {s:<3s} 0  0  0  0  0  0  0  0  0  0  0  0" for (x, y, z), s in zip(pos, sym)]
-    lines += [f"{a + 1:3d}{b + 1:3d}{o:3d}  0" for a, b, o in bonds]
-    return "\n".join(lines + ["M  END", "$$$$", ""])
 
 
 def _double_bonds(ch):
@@ -71,22 +65,22 @@ def test_3dbs_ligand_flatness_only():
 def test_symmetric_end_is_skipped_for_stereo():
     # (CH3)2C=CH-CH3: the end with two methyls is exchanged by an automorphism fixing the bond
     pos = [(0, 0, 0), (1.34, 0, 0), (-0.75, 1.3, 0), (-0.75, -1.3, 0), (2.1, 1.3, 0)]
-    ch = posecheck.ligand_chemistry(_molblock(["C"] * 5, [(0, 1, 2), (0, 2, 1), (0, 3, 1), (1, 4, 1)], pos))
+    ch = posecheck.ligand_chemistry(molblock(["C"] * 5, [(0, 1, 2), (0, 2, 1), (0, 3, 1), (1, 4, 1)], pos))
     assert len(ch["stereo"]) == 0 and ch["stereo_skipped"] == [(0, 1, "symmetric end")]
     assert ch["flat"][:, :2].tolist() == [[0, 1]]
     # CH3-CH=CH-CH3 (E): checked, cos(phi) < 0
     pos = [(0, 0, 0), (1.34, 0, 0), (-0.75, 1.3, 0), (2.1, -1.3, 0)]
-    ch = posecheck.ligand_chemistry(_molblock(["C"] * 4, [(0, 1, 2), (0, 2, 1), (1, 3, 1)], pos))
+    ch = posecheck.ligand_chemistry(molblock(["C"] * 4, [(0, 1, 2), (0, 2, 1), (1, 3, 1)], pos))
     assert ch["stereo"].tolist() == [[2, 0, 1, 3]] and ch["stereo_sign"].tolist() == [-1]
     # a ring double bond is not checked; a dihedral near 90 degrees is skipped
     pos = [(0, 0, 0), (1.34, 0, 0), (-0.75, 1.3, 0), (2.1, 0, 1.3)]
-    ch = posecheck.ligand_chemistry(_molblock(["C"] * 4, [(0, 1, 2), (0, 2, 1), (1, 3, 1)], pos))
+    ch = posecheck.ligand_chemistry(molblock(["C"] * 4, [(0, 1, 2), (0, 2, 1), (1, 3, 1)], pos))
     assert len(ch["stereo"]) == 0 and ch["stereo_skipped"][0][2].startswith("input dihedral")
 
 
 def test_hydrogens_are_dropped_and_radii():
     pos = [(0, 0, 0), (1.2, 0, 0), (-0.6, 0.9, 0), (2.0, 0.5, 0), (3.0, 0, 0)]
-    ch = posecheck.ligand_chemistry(_molblock(["C", "O", "H", "Cl", "Xe"], [(0, 1, 2), (0, 2, 1), (1, 3, 1), (3, 4, 1)], pos))
+    ch = posecheck.ligand_chemistry(molblock(["C", "O", "H", "Cl", "Xe"], [(0, 1, 2), (0, 2, 1), (1, 3, 1), (3, 4, 1)], pos))
     assert ch["symbols"] == ["C", "O", "Cl", "Xe"]
     assert ch["radii"].tolist() == pytest.approx([1.70, 1.52, 1.75, 2.00])
     assert ch["bonds"] == [(0, 1, 2), (1, 2, 1), (2, 3, 1)]
@@ -102,7 +96,7 @@ def test_internal_pairs_match_a_shortest_path_restatement():
         want = posecheck_ref.pairs_4_apart(len(ch["symbols"]), ch["bonds"])
         assert [tuple(p) for p in ch["pairs"].tolist()] == want
     # two fragments: every cross pair counts
-    ch = posecheck.ligand_chemistry(_molblock(["C", "C", "N"], [(0, 1, 1)], [(0, 0, 0), (1.5, 0, 0), (5, 0, 0)]))
+    ch = posecheck.ligand_chemistry(molblock(["C", "C", "N"], [(0, 1, 1)], [(0, 0, 0), (1.5, 0, 0), (5, 0, 0)]))
     assert ch["pairs"].tolist() == [[0, 2], [1, 2]]
 
 

@@ -38,7 +38,6 @@ import copy
 import ctypes as C
 import functools
 import hashlib
-import json
 import os
 import sys
 
@@ -54,6 +53,7 @@ import diffbindfr_amd as dba  # noqa: E402
 from diffbindfr_amd import lib as L, synthetic  # noqa: E402
 from diffbindfr_amd.packing import PackedBatch  # noqa: E402
 from oracle import sampler as osampler, schedule as osched, score_model as sm  # noqa: E402
+from tests import pinned  # noqa: E402
 from tests.helpers import GOLDEN as GOLDEN_DIR, load_golden_batch, namespace_to  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -129,27 +129,23 @@ def _at_step(d):
     return osampler.set_time(copy.deepcopy(d), osched.step_scalars(osched.default_sample_cfg(), STEP), d.num_graphs)
 
 
-def _sha(x):
-    return hashlib.sha256(np.ascontiguousarray(x.detach().cpu().numpy()).tobytes()).hexdigest()
-
-
 def _outputs(model, case):
     """{output name: sha256} of the case's score call and 3-step trajectory."""
     d, z = _batch()
     out = {}
     for nm, x in zip(("tr", "rot", "tor", "sc_tor"), model(namespace_to(_at_step(d), DEV))):
         if x is not None:
-            out["score_" + nm] = _sha(x)
+            out["score_" + nm] = pinned.sha(x)
     samp = dba.DiffBindFRHIP(diffusion_model=model, test_cfg={})
     noise = {k: torch.from_numpy(z[f"noise_{k}"]).to(DEV).contiguous() for k in ("tr", "rot", "tor", "sc")}
     lig, a14 = samp.sample_packed(PackedBatch(namespace_to(d, DEV), DEV), noise, visualize=True, stop=N_STEPS)
     assert lig.shape[0] == N_STEPS and a14.shape[0] == N_STEPS
-    out["traj_lig"] = _sha(lig)
+    out["traj_lig"] = pinned.sha(lig)
     if not model.no_sc_torsion:
-        out["traj_atom14"] = _sha(a14)
+        out["traj_atom14"] = pinned.sha(a14)
     if case in NO_TOR_CASES:
         for nm, x in zip(("tr", "rot", "tor", "sc_tor"), model(namespace_to(_at_step(_no_tor_batch()), DEV))):
-            out["no_tor_score_" + nm] = _sha(x)
+            out["no_tor_score_" + nm] = pinned.sha(x)
     return out
 
 
@@ -216,7 +212,7 @@ def test_the_batch_holds_what_the_walk_can_go_wrong_on():
 
 @pytest.fixture(scope="module")
 def golden():
-    return json.load(open(GOLDEN))["cases"]
+    return pinned.load(GOLDEN, "cases")
 
 
 @pytest.mark.parametrize("case", list(CASES))
@@ -246,10 +242,8 @@ def record(path):
            "workspace size and layout hash, recorded on an MI355X with `python tests/test_score_walk_pinned_gpu.py --record <this file>` "
            "in a checkout of the commit before the host walk of the score network was rewritten (its Python modules and the library "
            "built from it, build id below), with only this file copied in; two recordings agreed")
-    json.dump({"how": how, "library_build_id": L.load().dbfr_build_id().decode(), "cases": cases}, open(path, "w"), indent=1, sort_keys=True)
-    print(open(path).read())
+    pinned.write(path, how, cases, "cases", sort_keys=True)
 
 
 if __name__ == "__main__":
-    assert len(sys.argv) == 3 and sys.argv[1] == "--record", __doc__
-    record(sys.argv[2])
+    pinned.main(record, __doc__)

@@ -22,8 +22,6 @@ and 65 rows, at 64 x 1 024 + 1 rows for one weight set per input mode (the grid-
 capacity of 200 rows with a device row count of 130, 200 and 300.  Targets are not monotone over the five graphs, distances reach past the
 last Gaussian offset (walk_cases.mlp_case)."""
 import ctypes as C
-import hashlib
-import json
 import os
 import sys
 
@@ -34,10 +32,10 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-import diffbindfr_amd as dba  # noqa: E402
 from diffbindfr_amd import lib as L  # noqa: E402
-from oracle import score_model as sm  # noqa: E402
-from tests import walk_cases as wc  # noqa: E402
+from tests import pinned, walk_cases as wc  # noqa: E402
+from tests.conv_hook import seeded_model  # noqa: E402
+from tests.gpu_fixtures import dev, model  # noqa: E402, F401  (fixtures)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "small_kernel_hashes.json")
 NS = 48
@@ -68,21 +66,8 @@ def _nan(dev, *shape):
     return torch.full(shape, float("nan"), device=dev)
 
 
-def _sha(*ts):
-    h = hashlib.sha256()
-    for t in ts:
-        h.update(t.contiguous().cpu().numpy().tobytes())
-    return h.hexdigest()
-
-
 def _four(ts):
     return (C.c_void_p * 4)(*(t.data_ptr() for t in ts))
-
-
-def _model(dev):
-    m = dba.TensorProductModelHIP({}).to(dev)
-    m.load_state_dict(sm.init_params(sm.default_cfg(), seed=1), strict=True)
-    return m
 
 
 def _permutation(c):
@@ -149,46 +134,33 @@ def test_the_cases_are_the_ones_named():
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    return _model(dev)
-
-
-@pytest.fixture(scope="module")
 def golden():
-    return json.load(open(GOLDEN))["sha256"]
+    return pinned.load(GOLDEN)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("layer,form,var", REDUCE_CASES)
 def test_reduce_ln_layer_keeps_every_bit(model, dev, golden, layer, form, var):
-    assert _sha(*_reduce(model, dev, layer, form, var)) == golden[_reduce_key(layer, form, var)]
+    assert pinned.sha(*_reduce(model, dev, layer, form, var)) == golden[_reduce_key(layer, form, var)]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("nm,n,count", MLP_CASES)
 def test_mlp_keeps_every_bit(model, dev, golden, nm, n, count):
-    assert _sha(_mlp(model, dev, nm, n, count)) == golden[_mlp_key(nm, n, count)]
+    assert pinned.sha(_mlp(model, dev, nm, n, count)) == golden[_mlp_key(nm, n, count)]
 
 
 def record(path):
     dev = torch.device("cuda:0")
-    model = _model(dev)
-    sha = {_reduce_key(*k): _sha(*_reduce(model, dev, *k)) for k in REDUCE_CASES}
-    sha.update({_mlp_key(*k): _sha(_mlp(model, dev, *k)) for k in MLP_CASES})
+    model = seeded_model(dev)
+    sha = {_reduce_key(*k): pinned.sha(*_reduce(model, dev, *k)) for k in REDUCE_CASES}
+    sha.update({_mlp_key(*k): pinned.sha(_mlp(model, dev, *k)) for k in MLP_CASES})
     how = ("sha256 of the float32 output bytes of dbfr_test_reduce_ln_layer (out_l, then out_a) and dbfr_test_mlp (the rows written) for the "
            "cases of tests/test_small_kernels_pinned_gpu.py (inputs: tests/walk_cases.py; weights: oracle.score_model.init_params(seed=1)), "
            "recorded on an MI355X with `python tests/test_small_kernels_pinned_gpu.py --record <this file>` and DBFR_LIB pointing at the "
            "library built from the commit before k_reduce_ln_layer and k_mlp were rescheduled (library build id below)")
-    json.dump({"how": how, "library_build_id": L.load().dbfr_build_id().decode(), "sha256": sha}, open(path, "w"), indent=1)
-    print(open(path).read())
+    pinned.write(path, how, sha)
 
 
 if __name__ == "__main__":
-    assert len(sys.argv) == 3 and sys.argv[1] == "--record", __doc__
-    record(sys.argv[2])
+    pinned.main(record, __doc__)

@@ -20,20 +20,8 @@ from diffbindfr_amd import assemble, lib as L
 from diffbindfr_amd.packing import PackedBatch
 from oracle import sampler as osampler, schedule as osched, score_model as sm
 from tests import update_cases as uc, update_ref as ur
+from tests.gpu_fixtures import dev, model  # noqa: F401  (fixtures)
 from tests.helpers import namespace_to
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    m = dba.TensorProductModelHIP({}).to(dev)
-    m.load_state_dict(sm.init_params(sm.default_cfg(), seed=1), strict=True)
-    return m
 
 
 @pytest.fixture(scope="module")

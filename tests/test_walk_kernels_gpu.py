@@ -21,23 +21,11 @@ from diffbindfr_amd import lib as L, synthetic
 from diffbindfr_amd.packing import PackedBatch
 from oracle import sampler as osampler, schedule as osched, score_model as sm
 from tests import walk_cases as wc, walk_ref as wr
+from tests.gpu_fixtures import dev, model  # noqa: F401  (fixtures)
 from tests.helpers import namespace_to
 
 NS, EMB = 48, 32
 GUARD = 5                   # rows behind every output buffer that no kernel may touch
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def model(dev):
-    m = dba.TensorProductModelHIP({}).to(dev)
-    m.load_state_dict(sm.init_params(sm.default_cfg(), seed=1), strict=True)
-    return m
 
 
 def ptr(t):

@@ -6,7 +6,8 @@ sys.path.insert(0, ROOT)
 import diffbindfr_amd as dba
 from diffbindfr_amd import lib as L
 from oracle import e3nn_lite as o3, score_model as sm
-from tests.test_gpu_parity import _reshape_weights, K144_CONVS, _run_conv_hook
+from tests.conv_hook import run as _run_conv_hook
+from tests.test_gpu_parity import _reshape_weights, K144_CONVS
 dev = torch.device("cuda:0")
 mcfg = sm.default_cfg()
 for dist in ["seeded", "student_t2", "rows_4dec", "rows_6dec", "chan_6dec", "x1e-3", "x1e3"]:

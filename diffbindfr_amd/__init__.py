@@ -21,5 +21,6 @@ from . import hetero  # noqa: F401
 from . import hydrogens  # noqa: F401
 from . import decompose  # noqa: F401
 from . import cavity  # noqa: F401
+from . import pocketstates  # noqa: F401
 
 register_into_druglib()

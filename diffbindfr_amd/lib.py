@@ -288,6 +288,22 @@ class VinaDecomposeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("col_terms", "atom_terms", "totals", "col_fixed", "atom_fixed", "totals_fixed")]
 
 
+class PocketStatesIn(C.Structure):
+    _fields_ = [("n_group", C.c_int32), ("n_frame", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("frame_ptr", "res_ptr", "pocket_off", "pocket", "aatype", "atom14_mask", "res_mask", "ref_last",
+                                          "pair_off")] + \
+               [("max_frame", C.c_int32), ("max_res", C.c_int32), ("host", C.c_void_p)]
+
+
+class PocketStatesOpts(C.Structure):
+    _fields_ = [("ref_last", C.c_int32), ("tile_rows", C.c_int32)]
+
+
+class PocketStatesOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dist_max", "dist_pooled", "worst_res", "chi", "rot", "n_rot", "top_rot", "top_count", "ref_rot",
+                                          "ref_count", "mob_max", "mob_sq", "dev_ref_max", "n_used", "frame_ok")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -336,6 +352,7 @@ STRUCTS = {
     "dbfr_hydrogens_in": HydrogensIn, "dbfr_hydrogens_opts": HydrogensOpts, "dbfr_hydrogens_out": HydrogensOut,
     "dbfr_vina_decompose_in": VinaDecomposeIn, "dbfr_vina_decompose_opts": VinaDecomposeOpts,
     "dbfr_vina_decompose_out": VinaDecomposeOut,
+    "dbfr_pocket_states_in": PocketStatesIn, "dbfr_pocket_states_opts": PocketStatesOpts, "dbfr_pocket_states_out": PocketStatesOut,
     "dbfr_xtc_in": XtcIn, "dbfr_xtc_opts": XtcOpts, "dbfr_sites_opts": SitesOpts, "dbfr_sites_in": SitesIn, "dbfr_sites_out": SitesOut,
 }
 
@@ -435,6 +452,7 @@ PROTOTYPES = {
     "dbfr_vina_decompose": [P(VinaDecomposeIn), P(VinaDecomposeOpts), P(VinaDecomposeOut), vp],
     "dbfr_pose_cavity_workspace_bytes": [P(CavityIn), P(sz)],
     "dbfr_pose_cavity": [P(CavityIn), P(CavityOpts), P(CavityOut), vp],
+    "dbfr_pocket_states": [P(PocketStatesIn), P(PocketStatesOpts), P(PocketStatesOut), vp],
 }
 # the return types that are not int
 RESTYPES = {"dbfr_last_error": cp, "dbfr_build_id": cp, "dbfr_model_destroy": None, "dbfr_mdn_model_destroy": None,

@@ -54,7 +54,8 @@ extern "C" {
                                    dbfr_test_philox4x32, dbfr_test_vina_mutation,
                                    dbfr_vina_flex_search_workspace_bytes, dbfr_vina_flex_search,
                                    dbfr_test_pack_conv,
-                                   dbfr_cavity_in, dbfr_cavity_opts, dbfr_cavity_out, dbfr_pose_cavity_workspace_bytes, dbfr_pose_cavity */
+                                   dbfr_cavity_in, dbfr_cavity_opts, dbfr_cavity_out, dbfr_pose_cavity_workspace_bytes, dbfr_pose_cavity,
+                                   dbfr_pocket_states_in, dbfr_pocket_states_opts, dbfr_pocket_states_out, dbfr_pocket_states */
 
 typedef enum {
   DBFR_OK = 0,
@@ -1152,6 +1153,80 @@ typedef struct {                 /* device arrays; all but pair_dist may be NULL
 /* Two launches for the whole batch: the pairs of every group, then every frame.  opts NULL = defaults.                      */
 int dbfr_holo_metrics(const dbfr_holo_metrics_in* in, const dbfr_holo_metrics_opts* opts, const dbfr_holo_metrics_out* out,
                       void* hip_stream);
+
+/* ---- Pocket conformational states of the sampled poses (csrc/pocketstates.hip; docs/pocketstates.md): the receptor across the
+ * frames of a complex.  A batch of G groups (one group = one complex), group g holding F_g frames of R_g pocket rows (atom14,
+ * pocket-centred) with one residue type, atom14 mask and `counted` flag (res_mask) per row.  With ref_last the last frame of a group
+ * is a reference frame (the input structure): it takes part in the matrices, not in the statistics over the poses.
+ *   side-chain distance of frames i < j at residue s: A_s = the present atom14 slots 4..13, n_s = |A_s|,
+ *     q_id = sum_{a in A_s} |x_i[a] - x_j[a]|^2, q_sw the same against x_j[swap(a)] (the 180-degree renamings of ASP, GLU, PHE, TYR;
+ *     formed where the type's swap is not the identity and maps A_s onto itself), each ONE serial float32 sum in slot order,
+ *     q_s = min(q_id, q_sw), D_s = sqrtf(q_s / n_s).  A residue with n_s = 0 or res_mask = 0 does not count.
+ *   dist_max    [F, F]  max_s D_s                              worst_res [F, F] the lowest s attaining it (int32)
+ *   dist_pooled [F, F]  sqrtf(sum_s q_s / sum_s n_s), both sums serial in ascending s
+ *     Only i < j is computed and mirrored: the matrices equal their transposes bit for bit.  The diagonal is an exact 0 with
+ *     worst_res -1; where no residue counts the distances are 0 and worst_res is -1.
+ *   chi [frame, s, 4]   chi1..chi4 in radians (IUPAC sign, the chi atom table of dbfr_holo_metrics), NaN where undefined
+ *   rot [frame, s]      sum_k bin_k 3^k over the chi the type defines, a = chi in degrees: not pi-periodic: a wrapped into [0, 360),
+ *                       bin 0 = [0, 120), 1 = [120, 240), 2 = [240, 360); pi-periodic: a folded into [-45, 135) by 180, bin 0 =
+ *                       [-45, 45), 1 = [45, 135).  -1 when a chi the type defines is NaN; 0 for a type without chi.
+ *   per (group, s), over the usable pose frames: n_rot (distinct codes >= 0), top_rot / top_count (the most common code, ties to the
+ *     smaller code; -1 / 0 of none), ref_rot / ref_count (the reference frame's code and the poses sharing it; -1 / 0 without one),
+ *     mob_max = max_{i<j} D_s, mob_sq = sum_{i<j} llrintf(min(q_s / n_s, 4096) 2^20) (int64), dev_ref_max = max_i D_s(i, ref);
+ *     0 / -1 for a residue that does not count (the rotamer statistics read res_mask only).
+ *   n_used [G] the usable pose frames; frame_ok [n_frame] 1 = usable.
+ * A frame is unusable when a present atom (all 14 slots) of a counted residue is non-finite or beyond 1e4 A: its row and column
+ * (diagonal included) are NaN in both matrices with worst_res -1, its chi NaN, its rot -1, and no statistic reads it.  Maxima and
+ * integer sums are exact in any order and no float sum depends on the tiling: a group's outputs are bitwise the same alone, in any
+ * batch, in any group order and at any tile size.  Limits (DBFR_ERR_ARG): 512 frames per group (reference included), 585 pocket
+ * rows, 65 535 groups.  A group whose device-side counts exceed max_frame / max_res gets NaN / -1 / 0 in its own slices only.   */
+#define DBFR_PKS_MAX_FRAME 512
+#define DBFR_PKS_MAX_RES 585
+typedef struct {
+  int32_t        n_group;
+  int32_t        n_frame;        /* frame_ptr[G]                                                                            */
+  const int32_t* frame_ptr;      /* [G+1] first frame of every group; per-frame outputs are indexed by frame                 */
+  const int32_t* res_ptr;        /* [G+1] first pocket row of every group in aatype / atom14_mask / res_mask and the per-residue outputs */
+  const int64_t* pocket_off;     /* [G] sum_{h<g} F_h R_h: frame k of g at rows pocket_off[g] + k R_g of pocket, chi and rot    */
+  const float*   pocket;         /* [rows, 14, 3]                                                                           */
+  const int32_t* aatype;         /* [res_ptr[G]] 0..19 (others: no chi, no swap)                                            */
+  const uint8_t* atom14_mask;    /* [res_ptr[G], 14]                                                                        */
+  const int8_t*  res_mask;       /* [res_ptr[G]] 0 = the residue does not count; NULL = every residue counts                  */
+  const int8_t*  ref_last;       /* [G] 1 = the group's last frame is its reference frame; NULL = opts.ref_last for every group */
+  const int64_t* pair_off;       /* [G] sum_{h<g} F_h^2: where the group's matrices start                                    */
+  int32_t        max_frame;      /* host-known maxima over the groups (<= 512, <= 585)                                      */
+  int32_t        max_res;
+  const void*    host;           /* required: a dbfr_pocket_states_in whose pointers are HOST copies of frame_ptr, res_ptr, pocket_off,
+                                    pair_off and (where given) ref_last: every count and offset is validated before the launches  */
+} dbfr_pocket_states_in;
+
+typedef struct {
+  int32_t ref_last;              /* 0 / 1 for every group when in.ref_last is NULL (default 0)                               */
+  int32_t tile_rows;             /* frames per LDS tile, 0 = 16, at most 16 (same bits whatever the value; for tests)         */
+} dbfr_pocket_states_opts;
+
+typedef struct {                 /* device arrays, all required                                                             */
+  float*   dist_max;             /* [sum_g F_g^2]                                                                           */
+  float*   dist_pooled;          /* [sum_g F_g^2]                                                                           */
+  int32_t* worst_res;            /* [sum_g F_g^2]                                                                           */
+  float*   chi;                  /* [sum_g F_g R_g, 4]                                                                      */
+  int32_t* rot;                  /* [sum_g F_g R_g]                                                                         */
+  int32_t* n_rot;                /* [res_ptr[G]], as the seven below                                                        */
+  int32_t* top_rot;
+  int32_t* top_count;
+  int32_t* ref_rot;
+  int32_t* ref_count;
+  float*   mob_max;
+  int64_t* mob_sq;
+  float*   dev_ref_max;
+  int32_t* n_used;               /* [G]                                                                                     */
+  uint8_t* frame_ok;             /* [n_frame] written by the first launch, read by the other two                             */
+} dbfr_pocket_states_out;
+
+/* Three launches for the whole batch on the stream: every frame (chi, rot, frame_ok), every group (the rotamer statistics), every
+ * (pair tile, group) (the matrices and the mobility statistics, which the call zeroes first).  opts NULL = defaults.             */
+int dbfr_pocket_states(const dbfr_pocket_states_in* in, const dbfr_pocket_states_opts* opts, const dbfr_pocket_states_out* out,
+                       void* hip_stream);
 
 /* ---- Checks of poses against cofactors, metal ions and waters (csrc/hetero.hip; docs/hetero.md).  A batch of G groups (one
  * group = the frames of one ligand in one complex), group g holding F_g frames of N_g ligand heavy atoms (L), H_g hetero atoms

@@ -376,7 +376,7 @@ struct Bump {
 };
 
 struct Ws {
-  int* err; int64_t* counters;
+  int* err; int64_t* counters;   // counters [N_SETS]: the segment sum of every edge set's chunks (GraphArgs::chunk_segs; written in profiling mode only)
   int *lig_batch, *atm_batch, *n_cab, *tor_batch, *sc_batch; uint8_t* is_cab;
   float* temb;
   float *c_t, *c_tr_sigma, *c_rot_norm, *c_tor_n2, *c_sc_n2;
@@ -494,6 +494,7 @@ struct ConvSite {
   float* msg;
   const int *row_start, *row_cnt; const uint8_t* seg_first;                        // the reduction's view (null where the site is not reduced by its builder)
   const int *chunk_es, *chunk_gl, *n_chunks; int max_chunks; const float* xmax;    // k_convz: the chunk table of the edge list, the y scale (or null)
+  const int64_t* chunk_segs;                                                       // summed segment counts of that table's chunks (null: a flat list's table has none)
 };
 
 static ConvSite flat_site(const int* n_edges, int max_edges, const int* tgt, const int* gth, const float* emb, const float* sh, const float* tab1, int ld1,
@@ -507,10 +508,10 @@ static ConvSite flat_site(const int* n_edges, int max_edges, const int* tgt, con
 
 // ... on an edge set of the workspace; xmax: the per-graph |x| maximum of the node set x belongs to (launch_row_absmax)
 static ConvSite conv_site(const EdgeSet& S, int G, const float* tab1, int ld1, const int* idx1, const float* tab2, int ld2, const int* idx2, const float* x,
-                          int ldx, float* msg, const float* xmax) {
+                          int ldx, float* msg, const float* xmax, const int64_t* chunk_segs) {
   ConvSite s = flat_site(S.n_edges, S.cap, S.tgt, S.gth, S.emb, S.sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg);
   s.row_start = S.row_start; s.row_cnt = S.row_cnt; s.seg_first = S.seg_first;
-  s.chunk_es = S.chunk_es; s.chunk_gl = S.chunk_gl; s.n_chunks = S.chunk0 + G; s.max_chunks = S.chunk_cap; s.xmax = xmax;
+  s.chunk_es = S.chunk_es; s.chunk_gl = S.chunk_gl; s.n_chunks = S.chunk0 + G; s.max_chunks = S.chunk_cap; s.xmax = xmax; s.chunk_segs = chunk_segs;
   return s;
 }
 
@@ -562,7 +563,9 @@ static void conv_call(dbfr_model* m, const ConvW& cw, const ConvSite& site, hipS
 // one fused k_conv2 launch over up to four K=144 convs (an interaction layer, or the two torsion heads)
 // DBFR_GEMM_REDUCE_FIRST: `descs` hold the vector-output rows only (ConvW2 packed with vector_only) and `z` (same order) the reduce-first form of
 // the scalar-output rows: k_conv2h for the former (convs without l = 1 outputs are left out), k_convz for the latter, both writing the same message buffers.
-static void conv2_call(dbfr_model* m, const Conv2Desc* descs, const int* Ws, int n, hipStream_t st, bool f16_fallback = false, const ConvZDesc* z = nullptr) {
+// `zsegs` (with z): per conv the segment sum of its edge set's chunks; null: k_convz_useful walks the chunk table in front of k_convz (the single-conv test hook).
+static void conv2_call(dbfr_model* m, const Conv2Desc* descs, const int* Ws, int n, hipStream_t st, bool f16_fallback = false, const ConvZDesc* z = nullptr,
+                       const int64_t* const* zsegs = nullptr) {
   Conv2Args a;
   memset(&a, 0, sizeof a);
   for (int i = 0; i < n; ++i) a.c[i] = descs[i];
@@ -597,14 +600,16 @@ static void conv2_call(dbfr_model* m, const Conv2Desc* descs, const int* Ws, int
     za.n_conv = n;
     za.dbg = nullptr;
     za.executed = m->profile ? m->flops_dev + 3 : nullptr;      // k_convz counts the matrix instructions it issues (one atomic per wave and unit)
-    launch_convz(za, st);
+    launch_convz(za, st, !zsegs);
   }
   else if (m->gemm_split >= DBFR_GEMM_SPLIT_F16 && !f16_fallback) launch_conv2h(a, st);
   else launch_conv2(a, st);   // DBFR_GEMM_F32, and a launch holding a conv that even per-row factors cannot fit into two fp16 pieces: the fp32 instruction
   if (m->profile == 1) (void)hipEventRecord(e1, st);
   if (m->profile) {
     AccBatch ab; ab.count = 0;
-    auto acc = [&](const int* ne, double coef, double* dst) { if (ab.count < 32) { ab.n[ab.count] = ne; ab.coef[ab.count] = coef; ab.dst[ab.count] = dst; ++ab.count; } };
+    ab.wide = 0;
+    auto acc = [&](const int* ne, double coef, double* dst) { if (ab.count < ACC_BATCH_MAX) { ab.n[ab.count] = ne; ab.coef[ab.count] = coef; ab.dst[ab.count] = dst; ++ab.count; } };
+    auto acc64 = [&](const int64_t* s, double coef, double* dst) { if (ab.count < ACC_BATCH_MAX) { ab.wide |= 1ull << ab.count; acc(reinterpret_cast<const int*>(s), coef, dst); } };
     for (int i = 0; i < n; ++i) {
       acc(descs[i].n_edges, 2.0 * 144 * (144.0 + Ws[i]), m->flops_dev);
       acc(descs[i].n_edges, 4.0 * (Ws[i] + descs[i].w.D_in + 9) + 16.0, m->flops_dev + 1);
@@ -625,6 +630,17 @@ static void conv2_call(dbfr_model* m, const Conv2Desc* descs, const int* Ws, int
       const double in_bytes = 4.0 * (48 + 9 + 3 + 48 + 48 + D_in);
       if (!z) acc(descs[i].n_edges, fused_bytes(D_in, D_out), m->flops_dev + 5);
       else acc(descs[i].n_edges, in_bytes + 1.0 + (descs[i].w.n_tiles > 0 ? in_bytes + 4.0 * (D_out - 48 * z[i].w.n_io) : 0.0), m->flops_dev + 5);
+      // k_convz's own share of the useful flops and of the form bytes, from the edges and the segments of the set's chunks (every edge lies in exactly one chunk:
+      // chunk_cap bounds their number, graph.hip k_graph_chunks, so none is cut off and the lengths sum to the edge count): per chunk the hidden layer
+      // of its edges; step A the edges x the (path, u) pairs that exist x 145 (the k tile 9: one column); step B one column per segment x (c, k) values x 48;
+      // three partial products each; 4 x 48 message bytes per segment and output irrep.  Integers times integer constants: exact in a double.
+      if (z && zsegs) {
+        double ncv = 0.0;
+        for (int io = 0; io < z[i].w.n_io; ++io) ncv += (double)z[i].w.nc_valid[io];
+        acc(descs[i].n_edges, 6.0 * (144.0 * 144.0 + 145.0 * ncv), m->flops_dev + 4);
+        acc64(zsegs[i], 6.0 * 145.0 * 48.0 * ncv, m->flops_dev + 4);
+        acc64(zsegs[i], 4.0 * 48.0 * z[i].w.n_io, m->flops_dev + 5);
+      }
     }
     launch_acc_batch(ab, st);
   }
@@ -644,6 +660,7 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
   ga.lig_cap = cfg.lig_max_neighbors; ga.atom_cap = cfg.atom_max_neighbors; ga.dynamic_cross = cfg.dynamic_max_cross;
   for (int k = 0; k < N_SETS; ++k) ga.set[k] = w.set[k];
   ga.err = w.err; ga.step = step; ga.lds_nl = ga.lds_na = 0;
+  ga.chunk_segs = m->profile ? reinterpret_cast<long long*>(w.counters) : nullptr;
   dbfr_edge_form(*B, &ga.n_chunk, &ga.lanes);      // one choice of the edge builder's form for every launcher of this call
   launch_edges(ga, false, st);
   // (a launcher that could not prepare its launch left the edge sets unbuilt: nothing below may run on them)
@@ -687,22 +704,23 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     const EdgeSet &LL = w.set[SET_LL], &AA = w.set[SET_AA], &AL = w.set[SET_AL], &LA = w.set[SET_LA];
     // the four convs of the layer, in family order: the radial MLP reads the target node's row and the source node's, the tensor product the source's;
     // all four read the OLD features
-    const ConvSite sites[4] = {conv_site(LL, G, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], w.xmax_l),    // 0 ligand <- ligand
-                               conv_site(AL, G, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1], w.xmax_a),    // 1 ligand <- pocket
-                               conv_site(AA, G, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2], w.xmax_a),    // 2 pocket <- pocket
-                               conv_site(LA, G, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3], w.xmax_l)};   // 3 pocket <- ligand
+    const ConvSite sites[4] = {conv_site(LL, G, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], w.xmax_l, w.counters + SET_LL),    // 0 ligand <- ligand
+                               conv_site(AL, G, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1], w.xmax_a, w.counters + SET_AL),    // 1 ligand <- pocket
+                               conv_site(AA, G, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2], w.xmax_a, w.counters + SET_AA),    // 2 pocket <- pocket
+                               conv_site(LA, G, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3], w.xmax_l, w.counters + SET_LA)};   // 3 pocket <- ligand
     const bool fallback = (m->layer_fallback >> l) & 1u;
     const bool rf = w.conv2 && m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;
     if (w.conv2) {   // all four convs of the layer in ONE persistent launch (conv2.hip), or the k_convz + k_conv2h pair
-      Conv2Desc ds[4]; ConvZDesc zs[4]; int Ws[4];
+      Conv2Desc ds[4]; ConvZDesc zs[4]; int Ws[4]; const int64_t* sums[4];
       for (int i = 0; i < 4; ++i) {
+        sums[i] = sites[i].chunk_segs;
         ds[i] = conv2_desc(sites[i], rf ? m->layer2v[l][i] : m->layer2[l][i]);
         zs[i] = convz_desc(sites[i], m->layerz[l][i], Do);
         Ws[i] = m->layer[l][i].W;
       }
       // the y scale of k_convz: largest |x| per graph and node set (x = the rows a conv gathers: LL, LA read ligand rows, AL, AA pocket rows)
       if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, Di, Di, G, NA, st);
-      conv2_call(m, ds, Ws, 4, st, fallback, rf ? zs : nullptr);
+      conv2_call(m, ds, Ws, 4, st, fallback, rf ? zs : nullptr, sums);
     } else {   // bench-sized batches in f32 mode: the layer's four convs as ONE k_conv grid
       ConvArgs c4[4];
       for (int i = 0; i < 4; ++i) c4[i] = conv_args(sites[i], m->layer[l][i]);
@@ -759,7 +777,7 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
   {
     TorHead& h = heads[0];   // ligand torsions: edges bond <- ligand atom
     h.on = B->NTOR > 0; h.n = B->NTOR; h.S = &T;
-    h.site = conv_site(T, G, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, w.msg[0], w.xmax_l);
+    h.site = conv_site(T, G, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, w.msg[0], w.xmax_l, w.counters + SET_TOR);
     h.nodes = lx; h.b0 = B->bond_src; h.b1 = B->bond_dst; h.bsel = B->tor_bond; h.stride = 0; h.attr = w.tor_attr;
     h.emb = &m->tor_edge_emb; h.gs_off = m->gs_lig_off; h.gs_c = m->gs_lig_c;
     h.cw = &m->tor_conv; h.cw2 = &m->tor_conv2; h.cz = &m->tor_convz;
@@ -768,7 +786,7 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
   {
     TorHead& h = heads[1];   // side-chain torsions: edges bond <- pocket atom
     h.on = !cfg.no_sc_torsion && B->NSC > 0; h.n = B->NSC; h.S = &S;
-    h.site = conv_site(S, G, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, w.msg[w.conv2 ? 1 : 0], w.xmax_a);
+    h.site = conv_site(S, G, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, w.msg[w.conv2 ? 1 : 0], w.xmax_a, w.counters + SET_SC);
     h.nodes = ax; h.b0 = B->sc_bond; h.b1 = nullptr; h.bsel = nullptr; h.stride = 2; h.attr = w.sc_attr;
     h.emb = &m->sc_edge_emb; h.gs_off = m->gs_atom_off; h.gs_c = m->gs_atom_c;
     h.cw = &m->sc_conv; h.cw2 = &m->sc_conv2; h.cz = &m->sc_convz;
@@ -789,7 +807,7 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     launch_tor_final(h.feat, *h.fin, h.norm2, cfg.scale_by_sigma, h.n, h.out, st);
   };
   if (w.conv2) {   // both prologues, ONE fused launch over the heads present, both epilogues
-    Conv2Desc ds[2]; ConvZDesc zs[2]; int Ws[2]; int nd = 0;
+    Conv2Desc ds[2]; ConvZDesc zs[2]; int Ws[2]; const int64_t* sums[2]; int nd = 0;
     if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, D, D, G, NA, st);
     for (const TorHead& h : heads) {
       if (!h.on) continue;
@@ -797,9 +815,10 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
       ds[nd] = conv2_desc(h.site, *h.cw2);
       if (rf) ds[nd].w.n_tiles = 0;   // (all outputs of a torsion conv are scalars: k_convz serves every row)
       zs[nd] = convz_desc(h.site, *h.cz, 2 * NS);
+      sums[nd] = h.site.chunk_segs;
       Ws[nd++] = h.cw->W;
     }
-    if (nd) conv2_call(m, ds, Ws, nd, st, fallback, rf ? zs : nullptr);
+    if (nd) conv2_call(m, ds, Ws, nd, st, fallback, rf ? zs : nullptr, sums);
     for (const TorHead& h : heads)
       if (h.on) epilogue(h);
   } else {         // one k_conv per head

@@ -727,6 +727,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_convz(ConvZArgs a) {
 }
 
 // (profiling only, its own launch -- k_convz itself is not touched: a handful of extra live values moved its spills and cost 14 % of its speed)
+// Only the single-conv test hook still launches it: the score network's edge sets carry the segment sum it walks the chunk table for (GraphArgs::chunk_segs,
+// graph.hip k_chunk_fill, once per step), and conv2_call (api.cpp) forms the same two values from it and the edge count.
 // The flops among those k_convz issues that are not padding, [1] of the counters, and the message bytes of the form that runs, [2]: per chunk the hidden
 // layer of its edges; step A the edges x the (path, u) pairs that exist x 145 (the k tile 9: one column); step B one column per segment x (c, k) values
 // x 48; three partial products each.  One thread per chunk.
@@ -752,7 +754,7 @@ __global__ void k_convz_useful(ConvZArgs a) {
 
 size_t convz_lds_bytes() { return CZ_ZBYTES + 8 * CZ_WAVE_FLOATS * sizeof(float) + (8 + 2 * 16 * CZ_NCB + CZ_MAXCT * 16) * sizeof(int); }
 
-void launch_convz(const ConvZArgs& a0, hipStream_t st) {
+void launch_convz(const ConvZArgs& a0, hipStream_t st, bool useful_pass) {
   constexpr int NW = 8;
   ConvZArgs a = a0;
   static float* dbg_dev = nullptr;
@@ -773,7 +775,7 @@ void launch_convz(const ConvZArgs& a0, hipStream_t st) {
   static int abl = getenv("DBFR_CONVZ_ABL") ? atoi(getenv("DBFR_CONVZ_ABL")) : 0;
   if (abl == 1) V(1) if (abl == 2) V(2) if (abl == 4) V(4) if (abl == 8) V(8) if (abl == 16) V(16) if (abl == 32) V(32) if (abl == 12) V(12) if (abl == 5) V(5) if (abl == 64) V(64) if (abl == 128) V(128)
 #endif
-  if (a.executed) hipLaunchKernelGGL(k_convz_useful, dim3(64), dim3(256), 0, st, a);
+  if (a.executed && useful_pass) hipLaunchKernelGGL(k_convz_useful, dim3(64), dim3(256), 0, st, a);
   V(0)
 #undef V
 }

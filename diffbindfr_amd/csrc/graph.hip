@@ -483,24 +483,38 @@ __global__ __launch_bounds__(256) void k_graph_chunks(GraphArgs A) {
   }
   // (chunk_cap = cap / 32 + targets / 4 + G + 8 bounds the total: a chunk ends after 32 edges, at the end of its graph, or with the end of its
   // fourth target -- and every target ends once)
-  if (threadIdx.x == 0) { S.chunk0[G] = min(running, S.chunk_cap); S.gedge0[G] = S.cap > 0 ? min(*S.n_edges, S.cap) : 0; }
+  if (threadIdx.x == 0) {
+    S.chunk0[G] = min(running, S.chunk_cap); S.gedge0[G] = S.cap > 0 ? min(*S.n_edges, S.cap) : 0;
+    if (A.chunk_segs) A.chunk_segs[blockIdx.x] = 0;      // (k_chunk_fill, the next launch, adds this step's)
+  }
 }
 // pass 3, one wave per (graph, set): the chunk table
 __global__ __launch_bounds__(256) void k_chunk_fill(GraphArgs A) {
   const EdgeSet& S = A.set[blockIdx.y];
+  __shared__ int s_seg[4];
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (g >= A.b.G || S.cap == 0) return;
-  int lo, hi;
-  graph_edge_range(A, S, g, lo, hi);
-  int ch = S.chunk0[g];
+  if (S.cap == 0) return;
   const int lane = threadIdx.x & 63;
-  chunk_walk(S.tgt, lo, hi, [&](int es, int len, unsigned starts) {
-    if (ch >= S.chunk_cap) return false;
-    if (lane == 0) { S.chunk_es[ch] = es; S.chunk_gl[ch] = (g << 6) | len; }
-    if (lane < len) S.seg_first[es + lane] = (starts >> lane) & 1u;      // (every edge lies in exactly one chunk: no clearing pass)
-    ++ch;
-    return true;
-  });
+  int sum_seg = 0;      // (wave-uniform) segments of the graph's chunks: a chunk holds the first `len` of the 32 edges `starts` covers
+  if (g < A.b.G) {
+    int lo, hi;
+    graph_edge_range(A, S, g, lo, hi);
+    int ch = S.chunk0[g];
+    chunk_walk(S.tgt, lo, hi, [&](int es, int len, unsigned starts) {
+      if (ch >= S.chunk_cap) return false;
+      if (lane == 0) { S.chunk_es[ch] = es; S.chunk_gl[ch] = (g << 6) | len; }
+      if (lane < len) S.seg_first[es + lane] = (starts >> lane) & 1u;      // (every edge lies in exactly one chunk: no clearing pass)
+      sum_seg += __popc(len >= 32 ? starts : starts & ((1u << len) - 1u));
+      ++ch;
+      return true;
+    });
+  }
+  if (!A.chunk_segs) return;
+  // profiling: one atomic per workgroup (one per wave, 640 graphs x 6 sets on six addresses, doubled this kernel's time)
+  if (lane == 0) s_seg[threadIdx.x >> 6] = sum_seg;
+  __syncthreads();
+  const int segs = s_seg[0] + s_seg[1] + s_seg[2] + s_seg[3];
+  if (threadIdx.x == 0 && segs) atomicAdd(reinterpret_cast<unsigned long long*>(A.chunk_segs + blockIdx.y), (unsigned long long)segs);
 }
 
 void launch_graph_chunks(const GraphArgs& A0, hipStream_t st) {
@@ -755,7 +769,13 @@ __device__ __forceinline__ void wave_lds_order() {
 // tile of the launch -- live in registers: a lane loads its 3 KS + 36 weights once and no MFMA waits for an LDS read.  Without the 24 KB of
 // staged weights four workgroups fit a CU, so the 1 024 workgroups of a launch are all resident and one's input assembly runs under another's
 // MFMAs.  KS = 0: any other input width, weights staged in LDS.  Same instruction, same k order, same operands: same bits.
-template <int KS>
+// MODE >= 0: the input mode is known at compile time too, and with it the width and the column layout ([lig_node(27) | temb], [bond_feat(10) | temb |
+// gauss], [temb | gauss], [gauss]; launch_mlp checks the run-time widths against them).  A thread's KS columns of a row are then a fully unrolled
+// sequence with no mode test: its loads (temb, bond_feat, lig_node) leave together, ahead of the expf work of its Gaussian columns.  MODE < 0: a.mode is
+// read per element, as for any other width.  Same values into the same xin cells either way.
+#define MLP_NNODE 27
+#define MLP_NFEAT 10
+template <int KS, int MODE>
 __global__ __launch_bounds__(256, KS == 0 ? 2 : KS > 16 ? 3 : 4) void k_mlp(MlpArgs a) {
   __shared__ float xin[MLP_ROWS][MLP_MAXIN + 1];
   __shared__ float hid[MLP_ROWS][NS + 1];
@@ -765,6 +785,7 @@ __global__ __launch_bounds__(256, KS == 0 ? 2 : KS > 16 ? 3 : 4) void k_mlp(MlpA
   const int nrows = a.n_rows_dev ? min(*a.n_rows_dev, a.n_rows_max) : a.n_rows_max;
   if ((int)blockIdx.x * MLP_ROWS >= nrows) return;
   const int in = a.w.in;
+  const int mode = MODE >= 0 ? MODE : a.mode;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 15, g = lane >> 4;
   const int row = 16 * wave + n;
   // zero padding of the reduction dim to a multiple of 4 (MFMA k-step)
@@ -801,9 +822,9 @@ __global__ __launch_bounds__(256, KS == 0 ? 2 : KS > 16 ? 3 : 4) void k_mlp(MlpA
   float dist_n = 0.f;
   auto row_scalars = [&](int r0) {      // (rows behind the end read the last row's: loaded, never used)
     const int arow = min(r0 + r, nrows - 1);
-    gph_n = a.mode == IN_G ? 0 : a.row_graph_tab[a.tgt ? a.tgt[arow] : arow];
+    gph_n = mode == IN_G ? 0 : a.row_graph_tab[a.tgt ? a.tgt[arow] : arow];
     dist_n = a.dist ? a.dist[arow] : 0.f;
-    bond_n = a.mode == IN_LIGEDGE ? a.aux[arow] : -1;
+    bond_n = mode == IN_LIGEDGE ? a.aux[arow] : -1;
   };
   row_scalars(blockIdx.x * MLP_ROWS);
   for (int r0 = blockIdx.x * MLP_ROWS; r0 < nrows; r0 += gridDim.x * MLP_ROWS) {
@@ -815,21 +836,50 @@ __global__ __launch_bounds__(256, KS == 0 ? 2 : KS > 16 ? 3 : 4) void k_mlp(MlpA
     const int arow = r0 + (live ? r : 0);
     const int gph = gph_n, bond = bond_n;
     const float dcl = a.dist ? fminf(dist_n, s_gs[EMB - 1]) : 0.f;
+    if constexpr (MODE >= 0 && KS > 0) {
+      // column c = q + 4 j of the row: which part of the input it lies in is known per j, but for the one j a boundary that is no multiple of 4 cuts
+      constexpr int IN = MODE == IN_LIGNODE ? MLP_NNODE + EMB : MODE == IN_LIGEDGE ? MLP_NFEAT + 2 * EMB : MODE == IN_TG ? 2 * EMB : EMB;
+      constexpr int T0 = MODE == IN_LIGNODE ? MLP_NNODE : MODE == IN_LIGEDGE ? MLP_NFEAT : 0;      // first temb column (IN_G: none)
+      constexpr int G0 = MODE == IN_LIGNODE ? IN : MODE == IN_G ? 0 : T0 + EMB;                   // first Gaussian column (IN_LIGNODE: none)
+      static_assert(4 * KS >= IN && 4 * KS - IN < 4, "KS k-steps hold the mode's columns");
+      float v[KS];
+#pragma unroll
+      for (int j = 0; j < KS; ++j) {      // the loads
+        const int c = q + 4 * j;
+        v[j] = 0.f;
+        if (live && c < IN && c < G0) {
+          if (c >= T0) v[j] = a.temb[gph * EMB + c - T0];
+          else if (MODE == IN_LIGNODE) v[j] = a.lig_node[(size_t)arow * MLP_NNODE + c];
+          else if (bond >= 0) v[j] = a.bond_feat[(size_t)bond * MLP_NFEAT + c];
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KS; ++j) {      // the Gaussians
+        const int c = q + 4 * j;
+        if (4 * j + 3 >= G0 && live && c < IN && c >= G0) {
+          const float d = dcl - s_gs[c - G0];
+          v[j] = expf(coeff * (d * d));
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < KS; ++j)
+        if (q + 4 * j < IN) xin[r][q + 4 * j] = v[j];
+    } else
     for (int c = q; c < in; c += 4) {
       float v = 0.f;
       if (live) {
         int cc = c;
-        if (a.mode == IN_LIGNODE) {
+        if (mode == IN_LIGNODE) {
           v = cc < a.nnode ? a.lig_node[(size_t)arow * a.nnode + cc] : a.temb[gph * EMB + cc - a.nnode];
         } else {
-          if (a.mode == IN_LIGEDGE) {
+          if (mode == IN_LIGEDGE) {
             if (cc < a.nfeat) { v = bond >= 0 ? a.bond_feat[(size_t)bond * a.nfeat + cc] : 0.f; cc = -1; }
             else cc -= a.nfeat;
           }
           if (cc >= 0) {
-            if (a.mode != IN_G && cc < EMB) v = a.temb[gph * EMB + cc];
+            if (mode != IN_G && cc < EMB) v = a.temb[gph * EMB + cc];
             else {
-              const int k = a.mode == IN_G ? cc : cc - EMB;
+              const int k = mode == IN_G ? cc : cc - EMB;
               const float d = dcl - s_gs[k];
               v = expf(coeff * (d * d));
             }
@@ -888,13 +938,13 @@ void launch_mlp(const MlpArgs& a, hipStream_t st) {
   if (a.n_rows_max <= 0) return;
   const int tiles = (a.n_rows_max + MLP_ROWS - 1) / MLP_ROWS;
   const dim3 grid(tiles < 1024 ? tiles : 1024);     // 33 KB of LDS and under 128 registers: four workgroups per CU, every tile sequence resident
-  switch (a.w.hid == NS && a.w.out == NS ? a.w.in : 0) {
-    case 32: hipLaunchKernelGGL(k_mlp<8>, grid, dim3(256), 0, st, a); break;     // [gauss]
-    case 59: hipLaunchKernelGGL(k_mlp<15>, grid, dim3(256), 0, st, a); break;    // [lig_node(27) | temb]
-    case 64: hipLaunchKernelGGL(k_mlp<16>, grid, dim3(256), 0, st, a); break;    // [temb | gauss]
-    case 74: hipLaunchKernelGGL(k_mlp<19>, grid, dim3(256), 0, st, a); break;    // [bond_feat(10) | temb | gauss]
-    default: hipLaunchKernelGGL(k_mlp<0>, grid, dim3(256), 0, st, a);            // 58 KB of LDS: two workgroups per CU
-  }
+  // the four (mode, width) pairs of the score network; any other pairing of mode, width and feature counts takes the run-time form
+  const bool ns = a.w.hid == NS && a.w.out == NS;
+  if (ns && a.mode == IN_G && a.w.in == EMB) hipLaunchKernelGGL((k_mlp<8, IN_G>), grid, dim3(256), 0, st, a);                                                             // [gauss]
+  else if (ns && a.mode == IN_LIGNODE && a.nnode == MLP_NNODE && a.w.in == MLP_NNODE + EMB) hipLaunchKernelGGL((k_mlp<15, IN_LIGNODE>), grid, dim3(256), 0, st, a);       // [lig_node(27) | temb]
+  else if (ns && a.mode == IN_TG && a.w.in == 2 * EMB) hipLaunchKernelGGL((k_mlp<16, IN_TG>), grid, dim3(256), 0, st, a);                                                 // [temb | gauss]
+  else if (ns && a.mode == IN_LIGEDGE && a.nfeat == MLP_NFEAT && a.w.in == MLP_NFEAT + 2 * EMB) hipLaunchKernelGGL((k_mlp<19, IN_LIGEDGE>), grid, dim3(256), 0, st, a);   // [bond_feat(10) | temb | gauss]
+  else hipLaunchKernelGGL((k_mlp<0, -1>), grid, dim3(256), 0, st, a);                                                                                                    // 58 KB of LDS: two workgroups per CU
 }
 
 // AtomEncoder (equibind_encoder.py:68-88): sum of 5 categorical embeddings, then

@@ -656,10 +656,12 @@ void launch_acc_executed(const int* n_edges, double flops_per_edge, double* coun
 // step the profile is taken of
 __global__ void k_acc_batch(AccBatch b) {
   const int i = threadIdx.x;
-  if (i < b.count) atomicAdd(b.dst[i], b.coef[i] * (double)*b.n[i]);
+  if (i >= b.count) return;
+  const double n = (b.wide >> i) & 1 ? (double)*static_cast<const long long*>(b.n[i]) : (double)*static_cast<const int*>(b.n[i]);
+  atomicAdd(b.dst[i], b.coef[i] * n);
 }
 void launch_acc_batch(const AccBatch& b, hipStream_t st) {
-  if (b.count > 0) hipLaunchKernelGGL(k_acc_batch, dim3(1), dim3(32), 0, st, b);
+  if (b.count > 0) hipLaunchKernelGGL(k_acc_batch, dim3(1), dim3(64), 0, st, b);
 }
 void launch_acc_flops(const int* n_edges, double flops_per_edge, double bytes_per_edge, double fused_bytes_per_edge, double* counter, hipStream_t st) {
   hipLaunchKernelGGL(k_acc_flops, dim3(1), dim3(1), 0, st, n_edges, flops_per_edge, bytes_per_edge, fused_bytes_per_edge, counter);

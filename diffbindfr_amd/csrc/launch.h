@@ -15,7 +15,7 @@ void launch_conv(const ConvArgs& a, hipStream_t st);
 void launch_conv_layer(const ConvArgs* c4, hipStream_t st);
 void launch_conv2(const Conv2Args& a, hipStream_t st);
 void launch_conv2h(const Conv2Args& a, hipStream_t st);
-void launch_convz(const ConvZArgs& a, hipStream_t st);
+void launch_convz(const ConvZArgs& a, hipStream_t st, bool useful_pass = false);   // useful_pass: k_convz_useful in front (callers without the edge set's segment sum)
 void launch_reduce_ln(const float* msg, const int* row_start, const int* row_cnt, int N, int D, const LNDesc& ln,
                       const float* old, int D_old, float* out, int ldo, int mode, hipStream_t st, const uint8_t* first = nullptr, unsigned long long sc_lanes = 0);
 struct ReduceLayerArgs {
@@ -47,6 +47,9 @@ struct GraphArgs {
   int n_chunk;            // EDGE_CHUNK-target chunks per graph every set is split into (own workgroup each)
   int lanes;              // lanes per target of the edge builder (1 | 4); n_chunk and lanes are chosen ONCE per call (dbfr_edge_form) and
                           // shared by every launcher below: the g_cnt / g_base layout depends on both
+  long long* chunk_segs;  // profiling, else null: [N_SETS] per edge set the summed segment counts of this step's chunks (k_graph_chunks clears them,
+                          // k_chunk_fill adds).  With the set's edge count -- every edge lies in exactly one chunk -- that is what the profile counters of
+                          // every k_convz launch on the set are linear in
 };
 void dbfr_edge_form(const dbfr_batch& b, int* n_chunk, int* lanes);
 void launch_edges(const GraphArgs& A, bool heads_only, hipStream_t st);
@@ -124,5 +127,7 @@ void launch_select_pocket(int n_prot, int n_res_total, const int* res_ptr, int m
                           const float* ref, float cut2, int max_neighbors, float* d2, unsigned char* out, hipStream_t st);
 void launch_acc_flops(const int* n_edges, double flops_per_edge, double bytes_per_edge, double fused_bytes_per_edge, double* counter, hipStream_t st);
 void launch_acc_executed(const int* n_edges, double flops_per_edge, double* counter, hipStream_t st);
-struct AccBatch { const int* n[32]; double coef[32]; double* dst[32]; int count; };   // up to 32 counter updates of one k_acc_batch launch
+#define ACC_BATCH_MAX 48
+struct AccBatch { const void* n[ACC_BATCH_MAX]; double coef[ACC_BATCH_MAX]; double* dst[ACC_BATCH_MAX]; unsigned long long wide; int count; };   // up to 48 counter
+                          // updates of one k_acc_batch launch: dst += coef * *n, n an int, or a long long where the update's bit of `wide` is set
 void launch_acc_batch(const AccBatch& b, hipStream_t st);

@@ -22,5 +22,6 @@ from . import hydrogens  # noqa: F401
 from . import decompose  # noqa: F401
 from . import cavity  # noqa: F401
 from . import pocketstates  # noqa: F401
+from . import shapesim  # noqa: F401
 
 register_into_druglib()

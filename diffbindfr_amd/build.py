@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdbfr.so")
-SOURCES = ["api.cpp", "pack.cpp", "so3_host.cpp", "conv.hip", "conv2.hip", "conv2h.hip", "convz.hip", "graph.hip", "heads.hip", "export.hip", "mdn.hip", "probe.hip", "vina.hip", "modes.hip", "posecheck.hip", "xtc.hip", "sites.hip", "interactions.hip", "pocketcheck.hip", "sasa.hip", "apoholo.hip", "hetero.hip", "hydrogens.hip", "decompose.hip", "cavity.hip", "pocketstates.hip"]
+SOURCES = ["api.cpp", "pack.cpp", "so3_host.cpp", "conv.hip", "conv2.hip", "conv2h.hip", "convz.hip", "graph.hip", "heads.hip", "export.hip", "mdn.hip", "probe.hip", "vina.hip", "modes.hip", "posecheck.hip", "xtc.hip", "sites.hip", "interactions.hip", "pocketcheck.hip", "sasa.hip", "apoholo.hip", "hetero.hip", "hydrogens.hip", "decompose.hip", "cavity.hip", "pocketstates.hip", "shapesim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 if os.environ.get("DBFR_BUILD_DEV") == "1":      # developer build: the timing-only kernel variants behind DBFR_CONV*_ABL / _VAR (wrong results)
     FLAGS.append("-DDBFR_DEV_VARIANTS")
@@ -66,6 +66,9 @@ FILE_FLAGS["cavity.hip"] = FILE_FLAGS["vina.hip"]
 # pocketstates: the same (a pair's serial sums round every step, as the float64 restatement assumes); no scratch,
 # see docs/pocketstates.md
 FILE_FLAGS["pocketstates.hip"] = FILE_FLAGS["vina.hip"]
+# shapesim: the same (the pair term rounds every step, so that it has the same bits with its two points swapped); no scratch,
+# see docs/shapesim.md
+FILE_FLAGS["shapesim.hip"] = FILE_FLAGS["vina.hip"]
 
 
 def source_hash(dev=False):

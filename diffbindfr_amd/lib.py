@@ -304,6 +304,21 @@ class PocketStatesOut(C.Structure):
                                           "ref_count", "mob_max", "mob_sq", "dev_ref_max", "n_used", "frame_ok")]
 
 
+class ShapeIn(C.Structure):
+    _fields_ = [("n_mol", C.c_int32), ("n_cloud", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("mol_atom_ptr", "alpha", "flags", "color_alpha", "mol_grp_ptr", "grp", "cloud_mol", "cloud_pos_off",
+                                          "pos", "a_ptr", "a_cloud", "b_ptr", "b_cloud", "pair_off")] + \
+               [("n_set", C.c_int32), ("max_a", C.c_int32), ("max_b", C.c_int32), ("n_pos_row", C.c_int64), ("host", C.c_void_p)]
+
+
+class ShapeOpts(C.Structure):
+    _fields_ = [("color_weight", C.c_float), ("b_tile", C.c_int32)]
+
+
+class ShapeOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("self_fixed", "pair_fixed", "tanimoto", "dist")]
+
+
 class PdbLigand(C.Structure):
     _fields_ = [("n_atoms", i32), ("head", C.c_char_p), ("atom_line", C.POINTER(C.c_char_p)), ("tail", C.c_char_p)]
 
@@ -353,6 +368,7 @@ STRUCTS = {
     "dbfr_vina_decompose_in": VinaDecomposeIn, "dbfr_vina_decompose_opts": VinaDecomposeOpts,
     "dbfr_vina_decompose_out": VinaDecomposeOut,
     "dbfr_pocket_states_in": PocketStatesIn, "dbfr_pocket_states_opts": PocketStatesOpts, "dbfr_pocket_states_out": PocketStatesOut,
+    "dbfr_shape_in": ShapeIn, "dbfr_shape_opts": ShapeOpts, "dbfr_shape_out": ShapeOut,
     "dbfr_xtc_in": XtcIn, "dbfr_xtc_opts": XtcOpts, "dbfr_sites_opts": SitesOpts, "dbfr_sites_in": SitesIn, "dbfr_sites_out": SitesOut,
 }
 
@@ -453,6 +469,7 @@ PROTOTYPES = {
     "dbfr_pose_cavity_workspace_bytes": [P(CavityIn), P(sz)],
     "dbfr_pose_cavity": [P(CavityIn), P(CavityOpts), P(CavityOut), vp],
     "dbfr_pocket_states": [P(PocketStatesIn), P(PocketStatesOpts), P(PocketStatesOut), vp],
+    "dbfr_shape_overlap": [P(ShapeIn), P(ShapeOpts), P(ShapeOut), vp],
 }
 # the return types that are not int
 RESTYPES = {"dbfr_last_error": cp, "dbfr_build_id": cp, "dbfr_model_destroy": None, "dbfr_mdn_model_destroy": None,

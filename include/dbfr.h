@@ -55,7 +55,8 @@ extern "C" {
                                    dbfr_vina_flex_search_workspace_bytes, dbfr_vina_flex_search,
                                    dbfr_test_pack_conv,
                                    dbfr_cavity_in, dbfr_cavity_opts, dbfr_cavity_out, dbfr_pose_cavity_workspace_bytes, dbfr_pose_cavity,
-                                   dbfr_pocket_states_in, dbfr_pocket_states_opts, dbfr_pocket_states_out, dbfr_pocket_states */
+                                   dbfr_pocket_states_in, dbfr_pocket_states_opts, dbfr_pocket_states_out, dbfr_pocket_states,
+                                   dbfr_shape_in, dbfr_shape_opts, dbfr_shape_out, dbfr_shape_overlap */
 
 typedef enum {
   DBFR_OK = 0,
@@ -1227,6 +1228,79 @@ typedef struct {                 /* device arrays, all required                 
  * (pair tile, group) (the matrices and the mobility statistics, which the call zeroes first).  opts NULL = defaults.             */
 int dbfr_pocket_states(const dbfr_pocket_states_in* in, const dbfr_pocket_states_opts* opts, const dbfr_pocket_states_out* out,
                        void* hip_stream);
+
+/* ---- In-place Gaussian shape and feature overlap of conformations (csrc/shapesim.hip; docs/shapesim.md): a pose against a known
+ * ligand, or the poses of different ligands against each other, with no atom correspondence.  A molecule m has N_m heavy atoms, each
+ * with a Gaussian width alpha and flag bits (1 donor, 2 acceptor, 4 hydrophobe), LG_m groups in the lgrp layout of the
+ * interaction fingerprints: kind 0 ring / 1 cation / 2 anion, six local atom indices padded with -1, then 0; and one width
+ * color_alpha for its feature points.  A cloud c is molecule cloud_mol[c] at the N_m position rows from cloud_pos_off[c] on, expanded into points
+ * (x, y, z, alpha, kind):
+ *   kind 0 shape      every atom, its own alpha           kind 3 cation / 4 anion / 5 ring   the centroid of every group of that
+ *   kind 1 donor      every atom with bit 1, color_alpha                                     kind (serial float32 sum in list order,
+ *   kind 2 acceptor   every atom with bit 2, color_alpha                                     divided by the count), color_alpha
+ *   kind 6 hydrophobe every atom with bit 4, color_alpha
+ * Two points of the same kind contribute (float32, every operation rounded)
+ *     dx = xa - xb (dy, dz alike), d2 = (dx dx + dy dy) + dz dz, s = aa + ab, q = (aa ab) / s, c = PI_F / s,
+ *     v = ((8 c) sqrtf(c)) expf(-(q d2)),      term = llrint((double)v 4294967296.0)      (int64, units of 2^-32 A^3)
+ * which has the same bits with the two points swapped; points of different kinds contribute nothing and there is no cutoff.
+ * O[a, b, k] is the integer sum of the terms of kind k over all point pairs of the clouds a and b:
+ *   self_fixed [n_cloud, 7]  O[c, c, .]
+ *   pair_fixed [n_pair, 7]   set s is the block A_s x B_s of clouds (a_cloud[a_ptr[s] ..], b_cloud[b_ptr[s] ..]; b_ptr NULL: B_s = A_s for
+ *                            every set); the pair (i, j) of set s is row pair_off[s] + i |B_s| + j
+ *   tanimoto   [n_pair, 2]   with S = channel 0, C = the channels 1..6 summed as integers, in double and rounded once:
+ *                            S_ab / ((S_aa + S_bb) - S_ab), and the same on C (NaN when C_aa + C_bb == 0)
+ *   dist       [n_pair]      1 - sim, sim = T_shape when C_aa == 0 or C_bb == 0, else (1 - w) T_shape + w T_color in double, w =
+ *                            (double)color_weight; an exact 0 at i == j of a set with B_s = A_s
+ * Every sum is an integer sum: a pair's bits do not depend on the batch, its position, the tiling (b_tile) or the side a cloud is on.
+ * A cloud with a non-finite coordinate or one beyond 1e4 A gets INT64_MIN in its self row and in every pair row it takes part in, and
+ * NaN in the floats; nothing else is touched.  tanimoto and dist read self_fixed, which must then be given.  Limits (DBFR_ERR_ARG):
+ * 1..256 atoms and at most 32 groups per molecule, at most 1 024 points per cloud, alpha and color_alpha in [0.1, 1e4], at most 4 096
+ * clouds on either side of a set, at most 65 535 sets.                                                                            */
+#define DBFR_SHAPE_KINDS 7
+#define DBFR_SHAPE_MAX_ATOMS 256
+#define DBFR_SHAPE_MAX_GROUPS 32
+#define DBFR_SHAPE_MAX_POINTS 1024
+#define DBFR_SHAPE_MAX_SIDE 4096
+typedef struct {
+  int32_t        n_mol;
+  int32_t        n_cloud;
+  const int32_t* mol_atom_ptr;   /* [n_mol+1] first atom of every molecule in alpha / flags                                  */
+  const float*   alpha;          /* [mol_atom_ptr[n_mol]] kappa / r^2                                                        */
+  const uint8_t* flags;          /* [mol_atom_ptr[n_mol]] bit 0 donor, 1 acceptor, 2 hydrophobe                              */
+  const float*   color_alpha;    /* [n_mol] the width of the molecule's feature points                                       */
+  const int32_t* mol_grp_ptr;    /* [n_mol+1] first group of every molecule                                                  */
+  const int32_t* grp;            /* [mol_grp_ptr[n_mol], 8]: kind, 6 local atom indices (-1 padded, at least 1), 0             */
+  const int32_t* cloud_mol;      /* [n_cloud] the molecule of every cloud                                                    */
+  const int64_t* cloud_pos_off;  /* [n_cloud] first row of the cloud in pos                                                  */
+  const float*   pos;            /* [n_pos_row, 3]                                                                           */
+  const int32_t* a_ptr;          /* [n_set+1] into a_cloud                                                                   */
+  const int32_t* a_cloud;        /* [a_ptr[n_set]] cloud indices                                                             */
+  const int32_t* b_ptr;          /* [n_set+1] into b_cloud; NULL: B = A for every set (b_cloud is not read)                    */
+  const int32_t* b_cloud;
+  const int64_t* pair_off;       /* [n_set] sum_{t<s} |A_t| |B_t|                                                            */
+  int32_t        n_set;
+  int32_t        max_a;          /* host-known maxima of |A_s| and |B_s| (<= 4 096)                                          */
+  int32_t        max_b;
+  int64_t        n_pos_row;      /* rows of pos                                                                              */
+  const void*    host;           /* required: a dbfr_shape_in whose pointers are HOST copies of every array but pos: every count and
+                                    index is validated before the launches                                                    */
+} dbfr_shape_in;
+
+typedef struct {
+  float   color_weight;          /* w in [0, 1] (default 0.5)                                                                */
+  int32_t b_tile;                /* clouds of B per workgroup, 0 = 32 (same bits whatever the value; for tests)               */
+} dbfr_shape_opts;
+
+typedef struct {                 /* device arrays, any may be NULL (tanimoto / dist need self_fixed)                          */
+  int64_t* self_fixed;           /* [n_cloud, 7]                                                                             */
+  int64_t* pair_fixed;           /* [n_pair, 7]                                                                              */
+  float*   tanimoto;             /* [n_pair, 2] shape, colour                                                                */
+  float*   dist;                 /* [n_pair]                                                                                 */
+} dbfr_shape_out;
+
+/* Two launches for the whole batch on the stream: every cloud (self_fixed), every (tile of B, cloud of A, set).  opts NULL =
+ * defaults.                                                                                                                   */
+int dbfr_shape_overlap(const dbfr_shape_in* in, const dbfr_shape_opts* opts, const dbfr_shape_out* out, void* hip_stream);
 
 /* ---- Checks of poses against cofactors, metal ions and waters (csrc/hetero.hip; docs/hetero.md).  A batch of G groups (one
  * group = the frames of one ligand in one complex), group g holding F_g frames of N_g ligand heavy atoms (L), H_g hetero atoms

@@ -58,7 +58,7 @@ FILE_FLAGS["hetero.hip"] = FILE_FLAGS["vina.hip"]
 # hydrogens: the same (placements, distances and cosines round every step, as the float64 restatement's eps assumes); no scratch,
 # see docs/hydrogens.md
 FILE_FLAGS["hydrogens.hip"] = FILE_FLAGS["vina.hip"]
-# decompose: the same (the pair terms must round like k_vina's, whose expressions they restate); no scratch, see docs/decompose.md
+# decompose: the same (the pair terms of csrc/vina_terms.h must round as they do in k_vina); no scratch, see docs/decompose.md
 FILE_FLAGS["decompose.hip"] = FILE_FLAGS["vina.hip"]
 # cavity: the same (q - x and every square round separately, as the float64 restatement's exactness argument assumes); no scratch,
 # see docs/cavity.md

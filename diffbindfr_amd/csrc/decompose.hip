@@ -10,35 +10,26 @@
 #include "../../include/dbfr.h"
 #include "common.h"
 #include "frames.h"
+#define VINA_XS_RAD d_rad
+#define VINA_XS_FLAGS d_flags
+#include "vina_terms.h"
 
 // One workgroup per frame.  The ligand (x, y, z, XS type) is staged in LDS with its bounding box.  The receptor (the frame's
 // pocket atoms, then the group's static atoms: the rest of the protein and the hetero atoms) goes past in tiles of one atom per
 // thread; the typed atoms inside the box grown by the cutoff are compacted in index order into an LDS list, and every full tile
 // of 256 candidates (and the remainder at the end) is worked off twice: a thread per candidate walks the ligand and adds its
 // five sums to its column, a thread per ligand atom walks the tile and keeps its five sums in registers.
-// A pair's five fp32 terms are the expressions of k_vina (csrc/vina.hip: pair_terms; tests/test_decompose_gpu.py holds the two
-// kernels together).  Each term is rounded once to a 64-bit integer in units of 2^-36 kcal/mol and every sum is an integer sum:
+// A pair's five fp32 terms are k_vina's: both kernels call pair_terms of csrc/vina_terms.h, which also holds the XS table and the
+// typed predicate (tests/test_decompose_gpu.py compares the two kernels' totals).
+// Each term is rounded once to a 64-bit integer in units of 2^-36 kcal/mol and every sum is an integer sum:
 // exact in any order, so the column sums go through integer atomics on the frame's own rows, the bits of a frame do not depend on
 // the launch it is part of, and sum(columns) == sum(atoms) == totals holds exactly in the integer outputs.
 #define VD_THREADS FR_THREADS
 #define VD_WAVES FR_WAVES
 #define VD_MAX_LIG 256
 #define VD_MAX_COL 16384
-#define VD_DUMMY 16
-#define VD_NTYPES 18               // XS types 0..15 and Met_D (17); 16 and anything outside 0..17 takes part in no term
 #define VD_FIXED 68719476736.0     // 2^36 units per kcal/mol: 1.5e-11 resolution, sums up to 1.3e8 kcal/mol
 #define VD_BAD_FIXED ((long long)0x8000000000000000ull)
-
-// the XS table of csrc/vina.hip: radius; 1 hydrophobic, 2 donor, 4 acceptor
-//                                    C_H  C_P  N_P  N_D  N_A  N_DA O_P  O_D  O_A  O_DA S_P  P_P  F_H  Cl_H Br_H I_H  DUMMY Met_D
-__constant__ float d_rad[VD_NTYPES] = {1.9f, 1.9f, 1.8f, 1.8f, 1.8f, 1.8f, 1.7f, 1.7f, 1.7f, 1.7f, 2.0f, 2.1f, 1.5f, 1.8f, 2.0f, 2.2f, 0.f, 1.2f};
-__constant__ int d_flags[VD_NTYPES] = {1, 0, 0, 2, 4, 6, 0, 2, 4, 6, 0, 0, 1, 1, 1, 1, 0, 2};
-
-#define W_GAUSS1 (-0.035579f)
-#define W_GAUSS2 (-0.005156f)
-#define W_REPULSION 0.840245f
-#define W_HYDROPHOBIC (-0.035069f)
-#define W_HBOND (-0.587439f)
 
 struct VdArgs {
   dbfr_vina_decompose_in in;
@@ -46,37 +37,13 @@ struct VdArgs {
   float cutoff;
 };
 
-__device__ __forceinline__ bool vd_typed(int t) { return t >= 0 && t < VD_NTYPES && t != VD_DUMMY; }
-
-// One pair: the five weighted terms, as k_vina's pair_terms computes them (without the derivative).
-__device__ __forceinline__ void vd_pair_terms(int ti, int tj, float r, float* t5) {
-  const float d = r - d_rad[ti] - d_rad[tj];
-  const int fi = d_flags[ti], fj = d_flags[tj];
-  const float q1 = d * 2.f;
-  const float g1 = expf(-q1 * q1);
-  const float q2 = (d - 3.f) * 0.5f;
-  const float g2 = expf(-q2 * q2);
-  t5[0] = W_GAUSS1 * g1;
-  t5[1] = W_GAUSS2 * g2;
-  t5[2] = 0.f; t5[3] = 0.f; t5[4] = 0.f;
-  if (d < 0.f) t5[2] = W_REPULSION * (d * d);
-  if ((fi & 1) && (fj & 1)) {
-    if (d < 0.5f) t5[3] = W_HYDROPHOBIC;
-    else if (d < 1.5f) t5[3] = W_HYDROPHOBIC * (1.5f - d);
-  }
-  if (((fi & 2) && (fj & 4)) || ((fi & 4) && (fj & 2))) {
-    if (d < -0.7f) t5[4] = W_HBOND;
-    else if (d < 0.f) t5[4] = W_HBOND * (-d / 0.7f);
-  }
-}
-
 // the pair (ligand atom l, receptor atom c; w = the type as int bits) added to acc[0..4] when it lies within the cutoff
 __device__ __forceinline__ void vd_add_pair(const float4& l, const float4& c, float cut2, long long* acc) {
   const float dx = l.x - c.x, dy = l.y - c.y, dz = l.z - c.z;
   const float r2 = dx * dx + dy * dy + dz * dz;
   if (r2 >= cut2) return;
   float t5[5];
-  vd_pair_terms(__float_as_int(l.w), __float_as_int(c.w), sqrtf(r2), t5);
+  pair_terms<false>(__float_as_int(l.w), __float_as_int(c.w), sqrtf(r2), t5);
 #pragma unroll
   for (int k = 0; k < 5; ++k) acc[k] += __double2ll_rn((double)t5[k] * VD_FIXED);
 }
@@ -130,8 +97,8 @@ __global__ __launch_bounds__(VD_THREADS) void k_vina_decompose(VdArgs a) {
       const float x = lp[3 * i], y = lp[3 * i + 1], z = lp[3 * i + 2];
       const int t = in.lig_type[l0 + i];
       bad_atom |= !atom_ok(x, y, z);
-      lx[i] = make_float4(x, y, z, __int_as_float(vd_typed(t) ? t : -1));
-      if (vd_typed(t)) box.add(x, y, z, 0.f);
+      lx[i] = make_float4(x, y, z, __int_as_float(v_typed(t) ? t : -1));
+      if (v_typed(t)) box.add(x, y, z, 0.f);
     }
   }
   long long* cacc = reinterpret_cast<long long*>(out.col_fixed) + 5 * crow;
@@ -154,7 +121,7 @@ __global__ __launch_bounds__(VD_THREADS) void k_vina_decompose(VdArgs a) {
         const bool ok = atom_ok(y[0], y[1], y[2]) && col >= 0 && col < NC;
         bad_atom |= !ok;
         c = make_float4(y[0], y[1], y[2], __int_as_float(t));
-        keep = ok && vd_typed(t) && box.touches(c.x, c.y, c.z, a.cutoff);
+        keep = ok && v_typed(t) && box.touches(c.x, c.y, c.z, a.cutoff);
       }
       int slot, tot;
       block_compact(keep, nc, wcnt, lane, wave, slot, tot);
@@ -265,7 +232,7 @@ extern "C" int dbfr_vina_decompose(const dbfr_vina_decompose_in* in, const dbfr_
   if (in->n_group < 0 || in->n_frame < 0) return arg_err(fn, "negative n_group / n_frame");
   if (in->max_lig < 0 || in->max_lig > VD_MAX_LIG) return limit_err(fn, "max_lig (ligand atoms)", in->max_lig, 0, VD_MAX_LIG);
   if (in->max_col < 0 || in->max_col > VD_MAX_COL) return limit_err(fn, "max_col (columns)", in->max_col, 0, VD_MAX_COL);
-  dbfr_vina_decompose_opts o = {8.f};
+  dbfr_vina_decompose_opts o = {V_CUTOFF};
   if (opts) o = *opts;
   if (!(o.cutoff > 0.f && o.cutoff <= 16.f)) return arg_err(fn, "cutoff must lie in (0, 16] A");
   if (in->n_frame == 0) return DBFR_OK;

@@ -20,7 +20,7 @@
 // ligand's, every fixed end of a flexible torsion's axis (CA, CB) a DUMMY-typed anchor slot behind those that nothing moves; the
 // flexible torsions follow the ligand's in q.  The pair matrix carries ligand-flexible pairs (E_inter) and the allowed
 // flexible-flexible pairs (E_rec); flexible atoms are left out of the candidate list, and a candidate carries its receptor index
-// so that a flexible atom skips the partners on its exclusion list.  Nothing here knows an amino acid: diffbindfr_amd/vina.py
+// so that a flexible atom skips the partners on its exclusion list.  Nothing here knows an amino acid: diffbindfr_amd/vina_flex.py
 // (flex_topology) turns residues into these lists.  Everything flexible sits behind `if constexpr (SH::kFlex)`: the rigid
 // instantiation keeps its LDS, its occupancy and, bit for bit, its results (its register allocation moved a little:
 // profiles/r17_vinaflex_resource_usage.txt).
@@ -34,6 +34,9 @@
 // the flexible minimiser's variables: the base of `rebuild` and the best pose cover all slots, a step may redraw a flexible torsion,
 // and two accumulators per flexible torsion keep the angles that re-basing would forget.
 #include "common.h"
+#define VINA_XS_RAD c_rad
+#define VINA_XS_FLAGS c_flags
+#include "vina_terms.h"
 #include <algorithm>
 
 #define V_MAX_NL 256
@@ -41,26 +44,9 @@
 #define V_FLEX_MAX_TOR 122            // the flexible instantiation: 6 + 122 = 128 variables, a 64 KB inverse Hessian in dynamic LDS
 #define V_FLEX_MAX_EXCL 32            // receptor atoms within 3 bonds of a flexible atom (pocketcheck's limit)
 #define V_FLEX_MAX_NA 8192            // pocket atoms of a pose (the flexible-atom bit set)
-#define V_DUMMY 16
 #define V_THREADS 256
 #define V_WAVES (V_THREADS / 64)
-#define V_CUTOFF 8.0f
 #define V_MAX_STEP 0.3f              // largest first-trial change of one variable (A or rad): keeps the minimisation in its basin
-#define V_NTYPES 18                   // XS types 0..15 and Met_D (17); 16 and anything outside 0..17 is DUMMY
-
-// XS type table: radius, hydrophobic, donor, acceptor (row 16, DUMMY, is never read: v_typed)
-//                       C_H  C_P  N_P  N_D  N_A  N_DA O_P  O_D  O_A  O_DA S_P  P_P  F_H  Cl_H Br_H I_H  DUMMY Met_D
-__constant__ float c_rad[V_NTYPES] = {1.9f, 1.9f, 1.8f, 1.8f, 1.8f, 1.8f, 1.7f, 1.7f, 1.7f, 1.7f, 2.0f, 2.1f, 1.5f, 1.8f, 2.0f, 2.2f, 0.f, 1.2f};
-__constant__ int c_flags[V_NTYPES] = {1, 0, 0, 2, 4, 6, 0, 2, 4, 6, 0, 0, 1, 1, 1, 1, 0, 2};   // 1 hydrophobic, 2 donor, 4 acceptor
-
-__device__ __forceinline__ bool v_typed(int t) { return t >= 0 && t < V_NTYPES && t != V_DUMMY; }
-
-#define W_GAUSS1 (-0.035579f)
-#define W_GAUSS2 (-0.005156f)
-#define W_REPULSION 0.840245f
-#define W_HYDROPHOBIC (-0.035069f)
-#define W_HBOND (-0.587439f)
-#define W_NROT 0.05846f
 
 struct VinaBatch {        // the fields of dbfr_batch / dbfr_vina_in the kernel reads (a slim kernel argument)
   const int32_t *lig_ptr, *bond_src, *bond_dst, *tor_ptr, *tor_bond, *atm_ptr;
@@ -157,30 +143,6 @@ template <class SH> __device__ void block_sum6(SH& S, const float* v, float* out
   __syncthreads();
 }
 
-// One pair: the five unweighted inter terms' weighted sum split into e[0..4] and dE/dd.
-__device__ __forceinline__ float pair_terms(int ti, int tj, float r, float* t5) {
-  const float d = r - c_rad[ti] - c_rad[tj];
-  const int fi = c_flags[ti], fj = c_flags[tj];
-  const float q1 = d * 2.f;                              // d / 0.5
-  const float g1 = expf(-q1 * q1);
-  const float q2 = (d - 3.f) * 0.5f;
-  const float g2 = expf(-q2 * q2);
-  float de = W_GAUSS1 * g1 * (-2.f * q1 * 2.f) + W_GAUSS2 * g2 * (-2.f * q2 * 0.5f);
-  t5[0] = W_GAUSS1 * g1;
-  t5[1] = W_GAUSS2 * g2;
-  t5[2] = 0.f; t5[3] = 0.f; t5[4] = 0.f;
-  if (d < 0.f) { t5[2] = W_REPULSION * (d * d); de += W_REPULSION * 2.f * d; }
-  if ((fi & 1) && (fj & 1)) {
-    if (d < 0.5f) t5[3] = W_HYDROPHOBIC;
-    else if (d < 1.5f) { t5[3] = W_HYDROPHOBIC * (1.5f - d); de -= W_HYDROPHOBIC; }
-  }
-  if (((fi & 2) && (fj & 4)) || ((fi & 4) && (fj & 2))) {
-    if (d < -0.7f) t5[4] = W_HBOND;
-    else if (d < 0.f) { t5[4] = W_HBOND * (-d / 0.7f); de -= W_HBOND / 0.7f; }
-  }
-  return de;
-}
-
 // Candidate collection: fixed receptor atoms (pocket of graph g, then its extra atoms) within 8 A + margin of any of the ns slots
 // (the ligand atoms; with flexible side chains also their atoms, which are no candidates themselves).
 template <class SH> __device__ void collect(const VinaArgs& A, SH& S, int g, int ns) {
@@ -275,7 +237,7 @@ template <class SH> __device__ void evaluate(const VinaArgs& A, SH& S, int g, in
         }
         const float r = sqrtf(r2);
         float t5[5];
-        const float de = pair_terms(ti, tj, r, t5);
+        const float de = pair_terms<true>(ti, tj, r, t5);
         if (SH::kFlex && i >= nl) acc[NE - 1] += (double)t5[0] + (double)t5[1] + (double)t5[2] + (double)t5[3] + (double)t5[4];
         else for (int k = 0; k < 5; ++k) acc[k] += (double)t5[k];
         const float f = r > 0.f ? de / r : 0.f;
@@ -290,7 +252,7 @@ template <class SH> __device__ void evaluate(const VinaArgs& A, SH& S, int g, in
         if (r2 >= V_CUTOFF * V_CUTOFF) continue;
         const float r = sqrtf(r2);
         float t5[5];
-        const float de = pair_terms(ti, tj, r, t5);
+        const float de = pair_terms<true>(ti, tj, r, t5);
         if (SH::kFlex && (i >= nl || j >= nl)) {
           if (i < nl) { for (int k = 0; k < 5; ++k) acc[k] += (double)t5[k]; }
           else if (j >= nl && j > i) acc[NE - 1] += (double)t5[0] + (double)t5[1] + (double)t5[2] + (double)t5[3] + (double)t5[4];

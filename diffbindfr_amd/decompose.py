@@ -12,8 +12,9 @@ A frame is one pose of one complex.  Every ligand atom and every receptor atom (
 shared by the frames: the rest of the protein and the typed atoms of a ``hetero.HeteroRecord``, ``vina.hetero_types``) has an XS
 type code of ``vina.XS_NAMES``; DUMMY (16) and any code outside 0..17 takes part in no term.  Every receptor atom has a column:
 0 .. n_res - 1 are the protein's residues (the topology's rows), n_res .. n_col - 1 the hetero residues (chain, number, name) in
-file order.  For a pair with r^2 < cutoff^2 (8 A) the five weighted float32 terms are those of ``vina`` (the kernel restates the
-expressions of k_vina); each is rounded once to an integer in units of 2^-36 kcal/mol (``UNIT``) and every sum is an integer sum:
+file order.  For a pair with r^2 < cutoff^2 (8 A) the five weighted float32 terms are those of ``vina`` (the kernel shares
+csrc/vina_terms.h with k_vina); each is rounded once to an integer in units of 2^-36 kcal/mol (``UNIT``) and every sum is an
+integer sum:
 ``col_fixed`` [F, n_col, 5], ``atom_fixed`` [F, N, 5] and ``totals_fixed`` [sum F, 6] (the five terms and E_inter) are exact, do
 not depend on the batch a frame is part of, and the columns and the atoms of a frame both add up to its totals exactly.
 ``col_terms`` / ``atom_terms`` / ``totals`` are the same values in kcal/mol (float32).  A column without an atom in reach holds

@@ -34,7 +34,7 @@ import torch
 
 from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, HydrogensIn, HydrogensOpts, HydrogensOut
-from .vina import XS, ligand_types, parse_molblock
+from .vina_typing import XS, ligand_types, parse_molblock
 
 CARRY, BISECT, AMIDE, ROTOR = 0, 1, 2, 3
 DEFAULTS = dict(hb_dist=3.5, hb_h_dist=2.5, hb_dha_angle=120.0, hb_acc_angle=90.0)

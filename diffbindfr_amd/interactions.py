@@ -63,7 +63,7 @@ import torch
 
 from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, InteractionsIn, InteractionsOpts, InteractionsOut
-from .vina import _tables, ligand_types, parse_molblock, receptor_type_table
+from .vina_typing import _tables, ligand_types, parse_molblock, receptor_type_table
 
 KINDS = ["Hydrophobic", "HBDonor", "HBAcceptor", "Cationic", "Anionic", "CationPi", "PiCation", "FaceToFace", "EdgeToFace",
          "XBDonor"]

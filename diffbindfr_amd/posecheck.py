@@ -43,6 +43,7 @@ import torch
 
 from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, PoseCheckIn, PoseCheckOpts, PoseCheckOut
+from .vina_typing import _tables, parse_molblock
 
 RADII = {"H": 1.20, "C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "P": 1.80, "S": 1.80, "Cl": 1.75, "Br": 1.85, "I": 1.98}
 DEFAULT_RADIUS = 2.00
@@ -70,7 +71,6 @@ def radius(symbol):
 
 def receptor_radius_table():
     """float32 [21, 37]: the radius of atom37 slot k of residue type r, from the slot's element."""
-    from .vina import _tables
     T = _tables()
     by_elem = np.array([RADII["C"], RADII["N"], RADII["O"], RADII["S"]], np.float32)      # atom37_to_element: 0 C, 1 N, 2 O, 3 S
     row = by_elem[np.asarray(T["atom37_to_element"], np.int64)]
@@ -100,7 +100,6 @@ def ligand_chemistry(molblock, ref_pos=None):
     ``stereo`` int32 [n_stereo, 4] (s_u, u, v, s_v), ``stereo_sign`` int8 [n_stereo] (sign of cos(dihedral) in ref_pos),
     ``stereo_skipped`` [(u, v, reason)]."""
     from .ligand import _component, automorphisms
-    from .vina import parse_molblock
     sym_all, bonds_all, _ = parse_molblock(molblock)
     heavy = [i for i, s in enumerate(sym_all) if s != "H"]
     ren = {old: new for new, old in enumerate(heavy)}

@@ -34,6 +34,7 @@ import torch
 
 from . import entries as en, frames as fb, lib as L
 from .lib import DbfrError, SasaIn, SasaOpts, SasaOut
+from .vina_typing import _tables
 
 DEFAULTS = dict(probe=1.4)
 N_POINTS = 256
@@ -123,7 +124,6 @@ def burial(groups, cand_cap=0, n_points=N_POINTS, points=None, **opts):
 def receptor_arrays(r):
     """The per-atom arrays of ``burial`` for an ``entries.Receptor``: see ``entry_receptor``."""
     from .posecheck import RADII
-    from .vina import _tables
     T = _tables()
     elem = np.tile(np.asarray(T["atom37_to_element"], np.int64)[None], (len(T["restype_names3"]), 1))      # 0 C, 1 N, 2 O, 3 S
     pel, sel = r.lookup(elem)

@@ -24,7 +24,7 @@ import torch
 from . import entries as en, frames as fb, interactions, lib as L, modes
 from .lib import DbfrError, ShapeIn, ShapeOpts, ShapeOut
 from .posecheck import radius
-from .vina import XS
+from .vina_typing import XS
 
 KINDS = ["shape", "donor", "acceptor", "cation", "anion", "ring", "hydrophobe"]
 P_AMPLITUDE = 2.0 * math.sqrt(2.0)

@@ -539,6 +539,54 @@ static void gvp_run(const GvpW& G, const GvpVec& vec_in, const LinIn& s_in, int 
 }
 static GvpVec vec1(const float* p, int nv, const int* idx = nullptr) { GvpVec a; memset(&a, 0, sizeof a); a.ns = 1; a.s[0] = {p, nv, idx}; return a; }
 
+// The launchers below are shared by dbfr_mdn_forward and the dbfr_test_mdn_* hooks: a hook runs what the forward runs.
+static void launch_gvp_ln(const float* s_in, const float* ds, int ns, const float* v_in, const float* dv, int nv, const float* lw,
+                          const float* lb, int M, float* s_out, float* v_out, hipStream_t st) {
+  hipLaunchKernelGGL(k_gvp_ln, dim3((M + 3) / 4), dim3(256), 0, st, s_in, ds, ns, v_in, dv, nv, lw, lb, M, s_out, v_out);
+}
+static void launch_mean_in(const float* ms, int ns, const float* mv, int nv3, const int* ptr, int N, float* ds, float* dv, hipStream_t st) {
+  hipLaunchKernelGGL(k_mean_in, dim3((N * (ns + nv3) + 255) / 256), dim3(256), 0, st, ms, ns, mv, nv3, ptr, N, ds, dv);
+}
+static void launch_seq_concat(const float* node_s, const int* seq, const float* Ws, int NR, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(k_seq_concat, dim3((NR * 40 + 255) / 256), dim3(256), 0, st, node_s, seq, Ws, NR, out);
+}
+// attention of one graph-transformer layer: e_out == nullptr is the final layer's form (edge features are not updated)
+static void launch_gt_attn(const float* Q, const float* K, const float* V, const float* Ep, const int* src, const int* dst,
+                           const int* in_ptr, const int* in_edge, int NL, int EL, float* e_out, float* ax, float* h, hipStream_t st) {
+  if (EL > 0) hipLaunchKernelGGL(k_gt_edge, dim3((EL * 4 + 255) / 256), dim3(256), 0, st, Q, K, Ep, src, dst, EL, e_out, ax);
+  hipLaunchKernelGGL(k_gt_node, dim3((NL * 128 + 255) / 256), dim3(256), 0, st, V, ax, src, in_ptr, in_edge, NL, h);
+}
+
+// One layer of the ligand encoder, in place: x [NL,128] and (unless fin) e [EL,128] hold the layer's input and then its output; xn, en
+// are scratch of the same sizes.
+static void gt_layer_run(const GtLayer& G, bool fin, float* x, float* e, float* xn, float* en, const int* src, const int* dst,
+                         const int* in_ptr, const int* in_edge, int NL, int EL, const MWs& w, hipStream_t st) {
+  launch_lin(in1(x, 128, 128), G.q, NL, w.Q, 128, ACT_NONE, nullptr, 0, st);
+  launch_lin(in1(x, 128, 128), G.k, NL, w.K, 128, ACT_NONE, nullptr, 0, st);
+  launch_lin(in1(x, 128, 128), G.v, NL, w.V, 128, ACT_NONE, nullptr, 0, st);
+  launch_lin(in1(e, 128, 128), G.ep, EL, w.Ep, 128, ACT_NONE, nullptr, 0, st);
+  launch_gt_attn(w.Q, w.K, w.V, w.Ep, src, dst, in_ptr, in_edge, NL, EL, fin ? nullptr : w.eatt, w.ax, w.hatt, st);
+  launch_lin(in1(w.hatt, 128, 128), G.o_node, NL, xn, 128, ACT_NONE, x, 128, st);             // x1 = x + O(h)
+  launch_lin(in1(xn, 128, 128), G.mlp0, NL, w.t256, 256, ACT_SILU, nullptr, 0, st);
+  launch_lin(in1(w.t256, 256, 256), G.mlp3, NL, x, 128, ACT_NONE, xn, 128, st);               // x2 = x1 + MLP(bn2(x1)) -> back into x
+  if (!fin) {
+    launch_lin(in1(w.eatt, 128, 128), G.o_edge, EL, en, 128, ACT_NONE, e, 128, st);
+    launch_lin(in1(en, 128, 128), G.emlp0, EL, w.te256, 256, ACT_SILU, nullptr, 0, st);
+    launch_lin(in1(w.te256, 256, 256), G.emlp3, EL, e, 128, ACT_NONE, en, 128, st);
+  }
+}
+
+// The mixture-density head: the two halves of the split pair GEMM, the graph of every ligand atom, the pair sums, the per-graph sums.
+static void head_run(const dbfr_mdn_model* m, const float* lig_s, const float* pro_s, const float* lig_pos, const float* xyz_full,
+                     const int* lig_ptr, const int* res_ptr, int B, int NL, int NR, float dist_threshold, float* Al, float* At,
+                     double* part, int* lig_graph, float* score, hipStream_t st) {
+  launch_lin(in1(lig_s, 128, 128), m->mdn_l, NL, Al, 128, ACT_NONE, nullptr, 0, st);
+  launch_lin(in1(pro_s, 128, 128), m->mdn_t, NR, At, 128, ACT_NONE, nullptr, 0, st);
+  hipLaunchKernelGGL(k_graph_of, dim3(B), dim3(64), 0, st, lig_ptr, B, lig_graph);
+  hipLaunchKernelGGL(k_mdn_pairs, dim3(NL), dim3(128), 0, st, Al, At, m->Wz, m->bz, lig_pos, xyz_full, lig_ptr, res_ptr, lig_graph, dist_threshold > 0 ? dist_threshold : 5.0f, part);
+  hipLaunchKernelGGL(k_mdn_sum, dim3((B + 63) / 64), dim3(64), 0, st, part, lig_ptr, B, score);
+}
+
 extern "C" int dbfr_mdn_forward(dbfr_mdn_model* m, const dbfr_mdn_batch* B, float* score, float* lig_s_out, float* pro_s_out,
                                 void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!m || !B || !score || !workspace) { dbfr_set_error("null argument"); return DBFR_ERR_ARG; }
@@ -552,37 +600,18 @@ extern "C" int dbfr_mdn_forward(dbfr_mdn_model* m, const dbfr_mdn_batch* B, floa
   if (!lig_s) {
     launch_lin(in1(B->lig_node_s, 89, 89), m->node_enc, NL, w.x[0], 128, ACT_NONE, nullptr, 0, st);
     launch_lin(in1(B->lig_edge_s, 20, 20), m->edge_enc, EL, w.e[0], 128, ACT_NONE, nullptr, 0, st);
-    int cur = 0;
-    for (int l = 0; l < 6; ++l) {
-      const GtLayer& G = m->gt[l];
-      const bool fin = l == 5;
-      float *x = w.x[cur], *xn = w.x[cur ^ 1], *e = w.e[cur], *en = w.e[cur ^ 1];
-      launch_lin(in1(x, 128, 128), G.q, NL, w.Q, 128, ACT_NONE, nullptr, 0, st);
-      launch_lin(in1(x, 128, 128), G.k, NL, w.K, 128, ACT_NONE, nullptr, 0, st);
-      launch_lin(in1(x, 128, 128), G.v, NL, w.V, 128, ACT_NONE, nullptr, 0, st);
-      launch_lin(in1(e, 128, 128), G.ep, EL, w.Ep, 128, ACT_NONE, nullptr, 0, st);
-      if (EL > 0) hipLaunchKernelGGL(k_gt_edge, dim3((EL * 4 + 255) / 256), dim3(256), 0, st, w.Q, w.K, w.Ep, B->lig_edge_src, B->lig_edge_dst, EL, fin ? nullptr : w.eatt, w.ax);
-      hipLaunchKernelGGL(k_gt_node, dim3((NL * 128 + 255) / 256), dim3(256), 0, st, w.V, w.ax, B->lig_edge_src, B->lig_in_ptr, B->lig_in_edge, NL, w.hatt);
-      launch_lin(in1(w.hatt, 128, 128), G.o_node, NL, xn, 128, ACT_NONE, x, 128, st);             // x1 = x + O(h)
-      launch_lin(in1(xn, 128, 128), G.mlp0, NL, w.t256, 256, ACT_SILU, nullptr, 0, st);
-      launch_lin(in1(w.t256, 256, 256), G.mlp3, NL, x, 128, ACT_NONE, xn, 128, st);               // x2 = x1 + MLP(bn2(x1)) -> back into x
-      if (!fin) {
-        launch_lin(in1(w.eatt, 128, 128), G.o_edge, EL, en, 128, ACT_NONE, e, 128, st);
-        launch_lin(in1(en, 128, 128), G.emlp0, EL, w.te256, 256, ACT_SILU, nullptr, 0, st);
-        launch_lin(in1(w.te256, 256, 256), G.emlp3, EL, e, 128, ACT_NONE, en, 128, st);
-      }
-      (void)cur;                                                                                  // results stay in slot `cur`
-    }
+    for (int l = 0; l < 6; ++l)                                                                   // every layer leaves its result in slot 0
+      gt_layer_run(m->gt[l], l == 5, w.x[0], w.e[0], w.x[1], w.e[1], B->lig_edge_src, B->lig_edge_dst, B->lig_in_ptr, B->lig_in_edge, NL, EL, w, st);
     MCHECK(hipMemcpyAsync(w.lig_s, w.x[0], (size_t)NL * 128 * 4, hipMemcpyDeviceToDevice, st));
     lig_s = w.lig_s;
   }
   if (lig_s_out) MCHECK(hipMemcpyAsync(lig_s_out, lig_s, (size_t)NL * 128 * 4, hipMemcpyDeviceToDevice, st));
   // ---------------- pocket encoder
-  hipLaunchKernelGGL(k_seq_concat, dim3((NR * 40 + 255) / 256), dim3(256), 0, st, B->pro_node_s, B->pro_seq, m->W_s, NR, w.s40);
-  hipLaunchKernelGGL(k_gvp_ln, dim3((NR + 3) / 4), dim3(256), 0, st, w.s40, (const float*)nullptr, 40, B->pro_node_v, (const float*)nullptr, 3, m->ln_v.w, m->ln_v.b, NR, w.s40, w.v[1]);
+  launch_seq_concat(B->pro_node_s, B->pro_seq, m->W_s, NR, w.s40, st);
+  launch_gvp_ln(w.s40, nullptr, 40, B->pro_node_v, nullptr, 3, m->ln_v.w, m->ln_v.b, NR, w.s40, w.v[1], st);                 // scalars in place
   gvp_run(m->wv1, vec1(w.v[1], 3), in1(w.s40, 40, 40), NR, ACT_NONE, 0, w.vn_n, w.s[0], w.v[0], st);
   if (EP > 0) {
-    hipLaunchKernelGGL(k_gvp_ln, dim3((EP + 3) / 4), dim3(256), 0, st, B->pro_edge_s, (const float*)nullptr, 21, B->pro_edge_v, (const float*)nullptr, 1, m->ln_e.w, m->ln_e.b, EP, w.es0, w.ev0);
+    launch_gvp_ln(B->pro_edge_s, nullptr, 21, B->pro_edge_v, nullptr, 1, m->ln_e.w, m->ln_e.b, EP, w.es0, w.ev0, st);
     gvp_run(m->we1, vec1(w.ev0, 1), in1(w.es0, 21, 21), EP, ACT_NONE, 0, w.vn_e, w.es, w.ev, st);
   }
   const int *src = B->pro_edge_src, *dst = B->pro_edge_dst;
@@ -597,22 +626,151 @@ extern "C" int dbfr_mdn_forward(dbfr_mdn_model* m, const dbfr_mdn_batch* B, floa
       gvp_run(G.m1, vec1(w.mv[0], 16), in1(w.ms[0], 128, 128), EP, ACT_RELU, 1, w.vn_e, w.ms[1], w.mv[1], st);
       gvp_run(G.m2, vec1(w.mv[1], 16), in1(w.ms[1], 128, 128), EP, ACT_NONE, 0, w.vn_e, w.ms[0], w.mv[0], st);
     }
-    hipLaunchKernelGGL(k_mean_in, dim3((NR * 176 + 255) / 256), dim3(256), 0, st, w.ms[0], 128, w.mv[0], 48, B->pro_in_ptr, NR, w.ds, w.dv);
-    hipLaunchKernelGGL(k_gvp_ln, dim3((NR + 3) / 4), dim3(256), 0, st, s, w.ds, 128, v, w.dv, 16, G.n0.w, G.n0.b, NR, sn, vn);
+    launch_mean_in(w.ms[0], 128, w.mv[0], 48, B->pro_in_ptr, NR, w.ds, w.dv, st);
+    launch_gvp_ln(s, w.ds, 128, v, w.dv, 16, G.n0.w, G.n0.b, NR, sn, vn, st);
     gvp_run(G.f0, vec1(vn, 16), in1(sn, 128, 128), NR, ACT_RELU, 1, w.vn_f, w.fs, w.fv, st);
     gvp_run(G.f1, vec1(w.fv, 32), in1(w.fs, 512, 512), NR, ACT_NONE, 0, w.vn_f, w.ds, w.dv, st);
-    hipLaunchKernelGGL(k_gvp_ln, dim3((NR + 3) / 4), dim3(256), 0, st, sn, w.ds, 128, vn, w.dv, 16, G.n1.w, G.n1.b, NR, s, v);
+    launch_gvp_ln(sn, w.ds, 128, vn, w.dv, 16, G.n1.w, G.n1.b, NR, s, v, st);
     (void)cur;                                                                                    // layer output back in slot `cur`
   }
-  hipLaunchKernelGGL(k_gvp_ln, dim3((NR + 3) / 4), dim3(256), 0, st, w.s[0], (const float*)nullptr, 128, w.v[0], (const float*)nullptr, 16, m->ln_out.w, m->ln_out.b, NR, w.s[1], w.v[1]);
+  launch_gvp_ln(w.s[0], nullptr, 128, w.v[0], nullptr, 16, m->ln_out.w, m->ln_out.b, NR, w.s[1], w.v[1], st);
   gvp_run(m->wout, vec1(w.v[1], 16), in1(w.s[1], 128, 128), NR, ACT_RELU, 0, w.vn_n, w.pro_s, nullptr, st);
   if (pro_s_out) MCHECK(hipMemcpyAsync(pro_s_out, w.pro_s, (size_t)NR * 128 * 4, hipMemcpyDeviceToDevice, st));
   // ---------------- mixture-density head
-  launch_lin(in1(lig_s, 128, 128), m->mdn_l, NL, w.Al, 128, ACT_NONE, nullptr, 0, st);
-  launch_lin(in1(w.pro_s, 128, 128), m->mdn_t, NR, w.At, 128, ACT_NONE, nullptr, 0, st);
-  hipLaunchKernelGGL(k_graph_of, dim3(B->B), dim3(64), 0, st, B->lig_ptr, B->B, w.lig_graph);
-  hipLaunchKernelGGL(k_mdn_pairs, dim3(NL), dim3(128), 0, st, w.Al, w.At, m->Wz, m->bz, B->lig_pos, B->pro_xyz_full, B->lig_ptr, B->res_ptr, w.lig_graph, B->dist_threshold > 0 ? B->dist_threshold : 5.0f, w.part);
-  hipLaunchKernelGGL(k_mdn_sum, dim3((B->B + 63) / 64), dim3(64), 0, st, w.part, B->lig_ptr, B->B, score);
+  head_run(m, lig_s, w.pro_s, B->lig_pos, B->pro_xyz_full, B->lig_ptr, B->res_ptr, B->B, NL, NR, B->dist_threshold, w.Al, w.At, w.part, w.lig_graph, score, st);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ test hooks (ABI 9)
+// Each kernel of the scorer alone, through the launchers above (include/dbfr.h; tests/test_mdn_kernels_gpu.py).
+#define HOOK_ARG(fn, ok)                                                                             \
+  do {                                                                                               \
+    if (!(ok)) { dbfr_set_error(fn ": null, non-positive or out-of-range argument (" #ok ")"); return DBFR_ERR_ARG; } \
+  } while (0)
+
+extern "C" int dbfr_test_mdn_lin(const dbfr_mdn_seg* segs, int32_t n_seg, const float* W, int32_t ldw, const float* b, int32_t N, int32_t K,
+                                 int32_t M, float* out, int32_t ldo, int32_t act, const float* res, int32_t ldr, void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_lin", segs && W && out && n_seg >= 1 && n_seg <= 4 && N > 0 && K > 0 && M > 0);
+  HOOK_ARG("dbfr_test_mdn_lin", ldw >= K && ldo >= N && act >= ACT_NONE && act <= ACT_SILU && (!res || ldr >= N));
+  LinIn in; memset(&in, 0, sizeof in);
+  int k = 0;
+  for (int i = 0; i < n_seg; ++i) {
+    HOOK_ARG("dbfr_test_mdn_lin", segs[i].p && segs[i].w > 0 && segs[i].ld >= segs[i].w);
+    in = in_add(in, segs[i].p, segs[i].ld, segs[i].w, segs[i].idx);
+    k += segs[i].w;
+  }
+  HOOK_ARG("dbfr_test_mdn_lin", k == K);
+  Lin L; memset(&L, 0, sizeof L); L.W = W; L.ldw = ldw; L.b = b; L.N = N; L.K = K;
+  launch_lin(in, L, M, out, ldo, act, res, ldr, (hipStream_t)hip_stream);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_gt_attn(const float* Q, const float* K, const float* V, const float* Ep, const int32_t* src, const int32_t* dst,
+                                     const int32_t* in_ptr, const int32_t* in_edge, int32_t NL, int32_t EL, float* e_out, float* ax, float* h,
+                                     void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_gt_attn", Q && K && V && in_ptr && h && NL > 0 && EL >= 0);
+  HOOK_ARG("dbfr_test_mdn_gt_attn", EL == 0 || (Ep && src && dst && in_edge && ax));
+  launch_gt_attn(Q, K, V, Ep, src, dst, in_ptr, in_edge, NL, EL, e_out, ax, h, (hipStream_t)hip_stream);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_gvp(const dbfr_mdn_vseg* vsegs, int32_t n_vseg, const dbfr_mdn_seg* ssegs, int32_t n_sseg, const float* wh,
+                                 const float* wv, const float* ws_w, const float* ws_b, int32_t si, int32_t vi, int32_t so, int32_t vo,
+                                 int32_t act_s, int32_t gate, int32_t M, float* vn, float* s_out, float* v_out, void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_gvp", vsegs && ssegs && wh && ws_w && ws_b && vn && s_out && n_vseg >= 1 && n_vseg <= 3 && n_sseg >= 1 && n_sseg <= 3);
+  HOOK_ARG("dbfr_test_mdn_gvp", si > 0 && vi > 0 && vi <= GV_MAX && so > 0 && vo >= 0 && vo <= GV_MAX && M > 0 && (vo == 0 || (wv && v_out)));
+  HOOK_ARG("dbfr_test_mdn_gvp", act_s >= ACT_NONE && act_s <= ACT_SILU);
+  GvpVec a; memset(&a, 0, sizeof a);
+  int nv = 0, ns = 0;
+  for (int i = 0; i < n_vseg; ++i) {
+    HOOK_ARG("dbfr_test_mdn_gvp", vsegs[i].p && vsegs[i].nv > 0);
+    a.s[a.ns++] = {vsegs[i].p, vsegs[i].nv, vsegs[i].idx};
+    nv += vsegs[i].nv;
+  }
+  LinIn in; memset(&in, 0, sizeof in);
+  for (int i = 0; i < n_sseg; ++i) {
+    HOOK_ARG("dbfr_test_mdn_gvp", ssegs[i].p && ssegs[i].w > 0 && ssegs[i].ld >= ssegs[i].w);
+    in = in_add(in, ssegs[i].p, ssegs[i].ld, ssegs[i].w, ssegs[i].idx);
+    ns += ssegs[i].w;
+  }
+  HOOK_ARG("dbfr_test_mdn_gvp", nv == vi && ns == si);
+  GvpW G; memset(&G, 0, sizeof G);
+  G.si = si; G.vi = vi; G.so = so; G.vo = vo; G.h = std::max(vi, vo); G.wh = wh; G.wv = vo ? wv : nullptr;
+  G.ws.W = ws_w; G.ws.ldw = G.h + si; G.ws.b = ws_b; G.ws.N = so; G.ws.K = G.h + si;
+  gvp_run(G, a, in, M, act_s, gate ? 1 : 0, vn, s_out, v_out, (hipStream_t)hip_stream);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_gvp_ln(const float* s_in, const float* ds, int32_t ns, const float* v_in, const float* dv, int32_t nv,
+                                    const float* lw, const float* lb, int32_t M, float* s_out, float* v_out, void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_gvp_ln", s_in && lw && lb && s_out && ns > 0 && ns <= 128 && nv >= 0 && nv <= 64 && M > 0);
+  HOOK_ARG("dbfr_test_mdn_gvp_ln", nv == 0 || (v_in && v_out));
+  launch_gvp_ln(s_in, ds, ns, v_in, dv, nv, lw, lb, M, s_out, v_out, (hipStream_t)hip_stream);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_mean_in(const float* ms, int32_t ns, const float* mv, int32_t nv3, const int32_t* ptr, int32_t N, float* ds,
+                                     float* dv, void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_mean_in", ms && mv && ptr && ds && dv && ns > 0 && nv3 > 0 && N > 0);
+  launch_mean_in(ms, ns, mv, nv3, ptr, N, ds, dv, (hipStream_t)hip_stream);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_seq_concat(const float* node_s, const int32_t* seq, const float* Ws, int32_t NR, float* out, void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_seq_concat", node_s && seq && Ws && out && NR > 0);
+  launch_seq_concat(node_s, seq, Ws, NR, out, (hipStream_t)hip_stream);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+// the forward's own workspace plan for a batch of these sizes (EP = 0): the hooks below take their scratch from it
+static int hook_plan(const char* fn, int B, int NL, int EL, int NR, void* workspace, size_t workspace_bytes, MWs* w) {
+  dbfr_mdn_batch b; memset(&b, 0, sizeof b);
+  b.B = B; b.NL = NL; b.EL = EL; b.NR = NR;
+  const size_t need = mdn_plan(&b, (char*)workspace, w);
+  if (need > workspace_bytes) {
+    dbfr_set_error(std::string(fn) + ": workspace too small (" + std::to_string(need) + " bytes needed: dbfr_mdn_workspace_bytes of a batch with these sizes and EP = 0)");
+    return DBFR_ERR_ARG;
+  }
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_gt_layer(const dbfr_mdn_model* m, int32_t l, const float* x, const float* e, const int32_t* src, const int32_t* dst,
+                                      const int32_t* in_ptr, const int32_t* in_edge, int32_t NL, int32_t EL, float* x_out, float* e_out,
+                                      void* workspace, size_t workspace_bytes, void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_gt_layer", m && x && in_ptr && x_out && workspace && l >= 0 && l < 6 && NL > 0 && EL >= 0);
+  HOOK_ARG("dbfr_test_mdn_gt_layer", EL == 0 || (e && src && dst && in_edge && (l == 5 || e_out)));
+  MWs w;
+  if (int rc = hook_plan("dbfr_test_mdn_gt_layer", 1, NL, EL, 1, workspace, workspace_bytes, &w)) return rc;
+  hipStream_t st = (hipStream_t)hip_stream;
+  const bool fin = l == 5;
+  float* ew = w.e[0];                                              // the layer runs in place: on x_out, and on e_out (final layer: e is only read)
+  MCHECK(hipMemcpyAsync(x_out, x, (size_t)NL * 128 * 4, hipMemcpyDeviceToDevice, st));
+  if (EL > 0) {
+    ew = fin ? w.e[0] : e_out;
+    MCHECK(hipMemcpyAsync(ew, e, (size_t)EL * 128 * 4, hipMemcpyDeviceToDevice, st));
+  }
+  gt_layer_run(m->gt[l], fin, x_out, ew, w.x[1], w.e[1], src, dst, in_ptr, in_edge, NL, EL, w, st);
+  MCHECK(hipGetLastError());
+  return DBFR_OK;
+}
+
+extern "C" int dbfr_test_mdn_head(const dbfr_mdn_model* m, const float* lig_s, const float* pro_s, const float* lig_pos, const float* xyz_full,
+                                  const int32_t* lig_ptr, const int32_t* res_ptr, int32_t B, int32_t NL, int32_t NR, float dist_threshold,
+                                  float* Al_out, float* At_out, double* part_out, float* score_out, void* workspace, size_t workspace_bytes,
+                                  void* hip_stream) {
+  HOOK_ARG("dbfr_test_mdn_head", m && lig_s && pro_s && lig_pos && xyz_full && lig_ptr && res_ptr && part_out && score_out && workspace);
+  HOOK_ARG("dbfr_test_mdn_head", B > 0 && NL > 0 && NR > 0);
+  MWs w;
+  if (int rc = hook_plan("dbfr_test_mdn_head", B, NL, 0, NR, workspace, workspace_bytes, &w)) return rc;
+  head_run(m, lig_s, pro_s, lig_pos, xyz_full, lig_ptr, res_ptr, B, NL, NR, dist_threshold, Al_out ? Al_out : w.Al, At_out ? At_out : w.At,
+           part_out, w.lig_graph, score_out, (hipStream_t)hip_stream);
   MCHECK(hipGetLastError());
   return DBFR_OK;
 }

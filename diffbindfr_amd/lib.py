@@ -88,6 +88,14 @@ class MdnBatch(C.Structure):
                [("dist_threshold", C.c_float)]
 
 
+class MdnSeg(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("w", C.c_int32), ("idx", C.c_void_p)]
+
+
+class MdnVSeg(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("nv", C.c_int32), ("idx", C.c_void_p)]
+
+
 class SdfTemplate(C.Structure):
     _fields_ = [("n_atoms", C.c_int32), ("header", C.c_char_p), ("atom_tail", C.POINTER(C.c_char_p)), ("trailer", C.c_char_p)]
 
@@ -353,7 +361,7 @@ STRUCTS = {
     "dbfr_model_cfg": ModelCfg, "dbfr_tensor": Tensor, "dbfr_batch": Batch, "dbfr_limits": Limits, "dbfr_cond": Cond,
     "dbfr_scores": Scores, "dbfr_step": Step, "dbfr_noise": Noise, "dbfr_init_tape": InitTape,
     "dbfr_pose_metrics_in": PoseMetricsIn, "dbfr_pose_metrics_out": PoseMetricsOut, "dbfr_pdb_topology": PdbTopology,
-    "dbfr_pdb_ligand": PdbLigand, "dbfr_sdf_template": SdfTemplate, "dbfr_mdn_batch": MdnBatch,
+    "dbfr_pdb_ligand": PdbLigand, "dbfr_sdf_template": SdfTemplate, "dbfr_mdn_batch": MdnBatch, "dbfr_mdn_seg": MdnSeg, "dbfr_mdn_vseg": MdnVSeg,
     "dbfr_vina_in": VinaIn, "dbfr_vina_opts": VinaOpts, "dbfr_vina_search_opts": VinaSearchOpts, "dbfr_vina_flex_in": VinaFlexIn,
     "dbfr_pose_rmsd_in": PoseRmsdIn, "dbfr_modes_opts": ModesOpts,
     "dbfr_pose_check_in": PoseCheckIn, "dbfr_pose_check_opts": PoseCheckOpts, "dbfr_pose_check_out": PoseCheckOut,
@@ -434,6 +442,14 @@ PROTOTYPES = {
     "dbfr_mdn_workspace_bytes": [P(MdnBatch), P(sz)],
     "dbfr_mdn_pocket_features": [i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
     "dbfr_mdn_forward": [vp, P(MdnBatch), vp, vp, vp, vp, sz, vp],
+    "dbfr_test_mdn_lin": [P(MdnSeg), i32, vp, i32, vp, i32, i32, i32, vp, i32, i32, vp, i32, vp],
+    "dbfr_test_mdn_gt_attn": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
+    "dbfr_test_mdn_gvp": [P(MdnVSeg), i32, P(MdnSeg), i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+    "dbfr_test_mdn_gvp_ln": [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp],
+    "dbfr_test_mdn_mean_in": [vp, i32, vp, i32, vp, i32, vp, vp, vp],
+    "dbfr_test_mdn_seq_concat": [vp, vp, vp, i32, vp, vp],
+    "dbfr_test_mdn_gt_layer": [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp],
+    "dbfr_test_mdn_head": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, vp, sz, vp],
     "dbfr_vina_workspace_bytes": [P(VinaIn), P(sz)],
     "dbfr_vina_score": [P(VinaIn), vp, vp, vp, vp, sz, vp],
     "dbfr_vina_score_at": [P(VinaIn), vp, vp, vp, vp, vp, vp, vp, sz, vp],
@@ -475,7 +491,7 @@ PROTOTYPES = {
 RESTYPES = {"dbfr_last_error": cp, "dbfr_build_id": cp, "dbfr_model_destroy": None, "dbfr_mdn_model_destroy": None,
             "dbfr_pdb_format": i64, "dbfr_sdf_format": i64, "dbfr_pdb_atom_map": i64, "dbfr_complex_pdb_format": i64}
 SYMBOLS = list(PROTOTYPES)
-ABI_VERSION = 8                 # DBFR_ABI_VERSION
+ABI_VERSION = 9                 # DBFR_ABI_VERSION
 
 
 @lru_cache(maxsize=None)

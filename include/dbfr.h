@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define DBFR_ABI_VERSION 8   /* 2: + dbfr_sample_range, dbfr_capacity_report, dbfr_sdf_*, dbfr_mdn_*, dbfr_build_id, dbfr_test_conv2;
+#define DBFR_ABI_VERSION 9   /* 2: + dbfr_sample_range, dbfr_capacity_report, dbfr_sdf_*, dbfr_mdn_*, dbfr_build_id, dbfr_test_conv2;
                                 3: + dbfr_model_set_edge_log, dbfr_model_fallback_convs, dbfr_test_pack_f16_depth, dbfr_probe_mfma_f16 (additions only);
                                 4: + DBFR_GEMM_REDUCE_FIRST (the new default), dbfr_profile_executed_flops; dbfr_model_set_edge_log takes the graph capacity; DBFR_GEMM_SPLIT_BF16_L1 (k_conv2s) retired; dbfr_test_conv2's message rows in that mode hold segment sums;
                                 5: + dbfr_model_rowscaled_convs (per-row factors instead of the three-bf16-piece fall-back), dbfr_test_pack_f16_rows, dbfr_test_chunk_table; the reduce-first chunks hold <= 4 targets; DBFR_GEMM_SPLIT_BF16 (k_conv2r) retired;
@@ -56,7 +56,8 @@ extern "C" {
                                    dbfr_test_pack_conv,
                                    dbfr_cavity_in, dbfr_cavity_opts, dbfr_cavity_out, dbfr_pose_cavity_workspace_bytes, dbfr_pose_cavity,
                                    dbfr_pocket_states_in, dbfr_pocket_states_opts, dbfr_pocket_states_out, dbfr_pocket_states,
-                                   dbfr_shape_in, dbfr_shape_opts, dbfr_shape_out, dbfr_shape_overlap */
+                                   dbfr_shape_in, dbfr_shape_opts, dbfr_shape_out, dbfr_shape_overlap;
+                                9: + dbfr_mdn_seg, dbfr_mdn_vseg, dbfr_test_mdn_lin, dbfr_test_mdn_gt_attn, dbfr_test_mdn_gvp, dbfr_test_mdn_gvp_ln, dbfr_test_mdn_mean_in, dbfr_test_mdn_seq_concat, dbfr_test_mdn_gt_layer, dbfr_test_mdn_head (additions only) */
 
 typedef enum {
   DBFR_OK = 0,
@@ -1864,6 +1865,55 @@ int dbfr_test_trrot(const dbfr_model* m, const float* gp, const float* temb, con
 int dbfr_test_bond_attr(const dbfr_model* m, int32_t which, const float* nodes, int32_t ld, const int32_t* b0, const int32_t* b1,
                         const int32_t* bsel, int32_t n, float* attr_out, void* hip_stream);
 int dbfr_test_tor_final(const dbfr_model* m, int32_t which, const float* feat, const float* norm2, int32_t n, float* out, void* hip_stream);
+
+/* (ABI 9) Test hooks: the kernels of the MDN pose scorer alone (csrc/mdn.hip; tests/test_mdn_kernels_gpu.py).  Each runs the launcher
+ * dbfr_mdn_forward runs, on caller-supplied DEVICE buffers; each refuses a null, non-positive or out-of-range argument it needs with
+ * DBFR_ERR_ARG and synchronises nothing.  The raw hooks take the caller's own weights (the kernels are generic); the model hooks use the
+ * packed weights of a dbfr_mdn_model, BatchNorm folds included.
+ *
+ * dbfr_test_mdn_lin         k_lin: out[m, 0..N) = act(sum_k X[m,k] W[n,k] + b[n]) (+ res[m,n]), X the concatenation of n_seg <= 4 segments
+ *                           (row m of segment i = p[(idx ? idx[m] : m) * ld + 0..w), sum of the w = K); W rows of ldw >= K floats, b or NULL,
+ *                           out rows of ldo >= N floats, act 0 none / 1 ReLU / 2 SiLU, res (rows of ldr floats) or NULL.
+ * dbfr_test_mdn_gt_attn     k_gt_edge, then k_gt_node: Q, K, V [NL,128], Ep [EL,128], src / dst [EL] (attention over the edges into dst),
+ *                           in_ptr [NL+1] / in_edge [EL] (edge ids grouped by dst) -> e_out [EL,128] (NULL: the final layer's form),
+ *                           ax [EL,4], h [NL,128].  EL = 0: k_gt_node alone (the edge arrays may be NULL).
+ * dbfr_test_mdn_gvp         gvp_run = k_gvp_vec + the scalar k_lin of one GVP: n_vseg <= 3 vector segments (nv vectors of 3 per row, sum = vi),
+ *                           n_sseg <= 3 scalar segments (sum of the w = si), wh [h,vi] with h = max(vi, vo) <= 33, wv [vo,h] or NULL (vo = 0),
+ *                           ws_w [so, si+h] / ws_b [so] over [scalars | |Vh|] -> vn [M,h], s_out [M,so], v_out [M,vo,3]; act_s as above,
+ *                           gate != 0: v *= sigmoid(|v|).
+ * dbfr_test_mdn_gvp_ln      k_gvp_ln: s_out = LN(s_in + ds) (ns <= 128; weight lw, bias lb), v_out = (v_in + dv) / sqrt(mean max(|v|^2, 1e-8))
+ *                           (nv <= 64 vectors; nv = 0: scalars only); ds / dv NULL = no residual; s_out may equal s_in.
+ * dbfr_test_mdn_mean_in     k_mean_in: mean over each node's incoming edge rows ptr[n] .. ptr[n+1] of ms [E,ns] and mv [E,nv3] -> ds [N,ns],
+ *                           dv [N,nv3]; a node without rows gets zeros.
+ * dbfr_test_mdn_seq_concat  k_seq_concat: out [NR,40] = [node_s [NR,9] | Ws[seq[r]] (31 of a [31,31] table)].
+ * dbfr_test_mdn_gt_layer    layer l = 0..5 of the ligand encoder with the model's folded weights: x [NL,128], e [EL,128] -> x_out, e_out
+ *                           (e_out is ignored for l = 5).
+ * dbfr_test_mdn_head        the mixture-density head: lig_s [NL,128], pro_s [NR,128], lig_pos [NL,3], xyz_full [NR,14,3], lig_ptr / res_ptr
+ *                           [B+1] -> Al_out [NL,128] / At_out [NR,128] (either may be NULL), part_out [NL] (double: every ligand atom's sum
+ *                           over its graph's residues), score_out [B]; dist_threshold <= 0 = 5.0.
+ * The two model hooks take scratch from `workspace`: at least dbfr_mdn_workspace_bytes of a batch with the same B, NL, EL, NR (gt_layer:
+ * B = NR = 1; head: EL = 0) and EP = 0.                                                                                                     */
+typedef struct { const float* p; int32_t ld; int32_t w; const int32_t* idx; } dbfr_mdn_seg;
+typedef struct { const float* p; int32_t nv; const int32_t* idx; } dbfr_mdn_vseg;
+int dbfr_test_mdn_lin(const dbfr_mdn_seg* segs, int32_t n_seg, const float* W, int32_t ldw, const float* b, int32_t N, int32_t K, int32_t M,
+                      float* out, int32_t ldo, int32_t act, const float* res, int32_t ldr, void* hip_stream);
+int dbfr_test_mdn_gt_attn(const float* Q, const float* K, const float* V, const float* Ep, const int32_t* src, const int32_t* dst,
+                          const int32_t* in_ptr, const int32_t* in_edge, int32_t NL, int32_t EL, float* e_out, float* ax, float* h,
+                          void* hip_stream);
+int dbfr_test_mdn_gvp(const dbfr_mdn_vseg* vsegs, int32_t n_vseg, const dbfr_mdn_seg* ssegs, int32_t n_sseg, const float* wh, const float* wv,
+                      const float* ws_w, const float* ws_b, int32_t si, int32_t vi, int32_t so, int32_t vo, int32_t act_s, int32_t gate,
+                      int32_t M, float* vn, float* s_out, float* v_out, void* hip_stream);
+int dbfr_test_mdn_gvp_ln(const float* s_in, const float* ds, int32_t ns, const float* v_in, const float* dv, int32_t nv, const float* lw,
+                         const float* lb, int32_t M, float* s_out, float* v_out, void* hip_stream);
+int dbfr_test_mdn_mean_in(const float* ms, int32_t ns, const float* mv, int32_t nv3, const int32_t* ptr, int32_t N, float* ds, float* dv,
+                          void* hip_stream);
+int dbfr_test_mdn_seq_concat(const float* node_s, const int32_t* seq, const float* Ws, int32_t NR, float* out, void* hip_stream);
+int dbfr_test_mdn_gt_layer(const dbfr_mdn_model* m, int32_t l, const float* x, const float* e, const int32_t* src, const int32_t* dst,
+                           const int32_t* in_ptr, const int32_t* in_edge, int32_t NL, int32_t EL, float* x_out, float* e_out, void* workspace,
+                           size_t workspace_bytes, void* hip_stream);
+int dbfr_test_mdn_head(const dbfr_mdn_model* m, const float* lig_s, const float* pro_s, const float* lig_pos, const float* xyz_full,
+                       const int32_t* lig_ptr, const int32_t* res_ptr, int32_t B, int32_t NL, int32_t NR, float dist_threshold, float* Al_out,
+                       float* At_out, double* part_out, float* score_out, void* workspace, size_t workspace_bytes, void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -48,7 +48,7 @@ DOCTORED = {
     "struct-pointer target": ("int dbfr_sasa(", r"const dbfr_sasa_opts\*", "const dbfr_cavity_opts*", "function dbfr_sasa parameter 1:"),
     "new prototype": ("int dbfr_sasa(", "int dbfr_sasa", "int dbfr_new_thing(void);\nint dbfr_sasa", "function dbfr_new_thing:"),
     "new struct": ("int dbfr_sasa(", "int dbfr_sasa", "typedef struct { int32_t n; } dbfr_new_in;\nint dbfr_sasa", "struct dbfr_new_in:"),
-    "ABI number": ("#define", "DBFR_ABI_VERSION 8", "DBFR_ABI_VERSION 9", "constant DBFR_ABI_VERSION:"),
+    "ABI number": ("#define", "DBFR_ABI_VERSION 9", "DBFR_ABI_VERSION 10", "constant DBFR_ABI_VERSION:"),
     "status value": ("typedef enum", "DBFR_ERR_CAPACITY = -3", "DBFR_ERR_CAPACITY = -6", "constant DBFR_ERR_CAPACITY:"),
 }
 

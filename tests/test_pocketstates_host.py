@@ -277,7 +277,7 @@ def test_the_abi_tables_hold_the_new_structs_and_function():
                       ("dbfr_pocket_states_out", L.PocketStatesOut)):
         assert L.STRUCTS[name] is cls
     assert L.PROTOTYPES["dbfr_pocket_states"] == [C.POINTER(L.PocketStatesIn), C.POINTER(L.PocketStatesOpts), C.POINTER(L.PocketStatesOut), C.c_void_p]
-    assert "dbfr_pocket_states" not in L.RESTYPES and L.ABI_VERSION == 8
+    assert "dbfr_pocket_states" not in L.RESTYPES and L.ABI_VERSION == 9
     assert L.pointer_fields(L.PocketStatesIn) == ["frame_ptr", "res_ptr", "pocket_off", "pocket", "aatype", "atom14_mask", "res_mask", "ref_last",
                                                   "pair_off"]
     header = open(cases.GOLDEN + "/../../include/dbfr.h").read()

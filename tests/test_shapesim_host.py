@@ -251,6 +251,6 @@ def test_python_entry_points_refuse_the_cpu_bad_shapes_limits_and_options():
     header = open(ref.GOLDEN + "/../../include/dbfr.h").read()
     for name, v in (("KINDS", 7), ("MAX_ATOMS", shp.MAX_ATOMS), ("MAX_GROUPS", shp.MAX_GROUPS), ("MAX_POINTS", shp.MAX_POINTS), ("MAX_SIDE", shp.MAX_SIDE)):
         assert f"#define DBFR_SHAPE_{name} {v}\n" in header
-    assert L.STRUCTS["dbfr_shape_in"] is L.ShapeIn and L.PROTOTYPES["dbfr_shape_overlap"][0] == C.POINTER(L.ShapeIn) and L.ABI_VERSION == 8
+    assert L.STRUCTS["dbfr_shape_in"] is L.ShapeIn and L.PROTOTYPES["dbfr_shape_overlap"][0] == C.POINTER(L.ShapeIn) and L.ABI_VERSION == 9
     assert L.pointer_fields(L.ShapeIn) == ["mol_atom_ptr", "alpha", "flags", "color_alpha", "mol_grp_ptr", "grp", "cloud_mol", "cloud_pos_off",
                                            "pos", "a_ptr", "a_cloud", "b_ptr", "b_cloud", "pair_off"]

@@ -356,7 +356,9 @@ def measure():
 
 
 def _up(x):
-    """Three significant digits, rounded UP: a recorded row is never below what was measured."""
+    """Three significant digits, rounded UP: a recorded row is never below what was measured (an exact 0 stays 0)."""
+    if x == 0:
+        return "0.00e+00"
     e = math.floor(math.log10(x)) - 2
     return f"{math.ceil(x / 10 ** e) * 10 ** e:.2e}"
 
@@ -364,19 +366,20 @@ def _up(x):
 CPU_PATHS = ("default", "avx2", "avx512")
 
 
-if __name__ == "__main__":
-    # The float32 oracle is torch on the CPU, and torch's float32 results depend on the vector path it dispatches to: each is the
-    # reference's float32 arithmetic as some machine runs it.  A row is the largest figure over the paths.  `--one`: this process only.
+def measure_on_every_cpu_path(module, measure):
+    """`python -m <module>` (this module, or tests.mdn_cases with its own `measure`): the BOUNDS table, printed ready to paste.
+    The float32 oracle is torch on the CPU, and torch's float32 results depend on the vector path it dispatches to: each is the
+    reference's float32 arithmetic as some machine runs it.  A row is the largest figure over the paths.  `--one`: this process only."""
     import json
     import os
     import subprocess
     import sys
     if "--one" in sys.argv:
         print("ROWS " + json.dumps(measure()))
-        sys.exit(0)
+        return
     rows = {}
     for path in CPU_PATHS:
-        out = subprocess.run([sys.executable, "-m", "tests.walk_cases", "--one"], env=dict(os.environ, ATEN_CPU_CAPABILITY=path),
+        out = subprocess.run([sys.executable, "-m", module, "--one"], env=dict(os.environ, ATEN_CPU_CAPABILITY=path),
                              capture_output=True, text=True, check=True).stdout
         print(f"---- ATEN_CPU_CAPABILITY={path}\n" + out.split("ROWS ")[0], flush=True)
         for k, v in json.loads(out.split("ROWS ")[1]).items():
@@ -385,3 +388,7 @@ if __name__ == "__main__":
     for k, v in rows.items():
         print(f'    "{k}": (' + ", ".join(_up(x) for x in v) + ("," if len(v) == 1 else "") + "),")
     print("}")
+
+
+if __name__ == "__main__":
+    measure_on_every_cpu_path("tests.walk_cases", measure)

@@ -66,39 +66,48 @@ static int gemm_from_env() {
   return -1;
 }
 
+// Every packed layout of one conv, device resident.  A K=144 conv (an interaction-layer conv or a torsion conv) has all of them; the final conv
+// (K=96, k144 false) has `w` alone.
+struct ModelConv {
+  ConvW w = {};        // k_conv / k_conv_layer
+  ConvW2 w2 = {};      // k_conv2 / k_conv2h, every row
+  ConvW2 w2v = {};     // ... the l = 1 output rows alone (DBFR_GEMM_REDUCE_FIRST: the scalar outputs go through k_convz)
+  bool has_w2v = false;   // (false for the torsion convs: all their outputs are scalars)
+  ConvZ z = {};        // reduce-first form of the scalar-output paths (convz.hip)
+  bool k144 = false;
+};
+
 struct dbfr_model {
-  dbfr_model_cfg cfg;
+  dbfr_model_cfg cfg = {};
   std::vector<void*> allocs;
-  ConvW layer[8][4];   // [l][family]: 0 lig, 1 cross_al, 2 atom, 3 cross_la
-  ConvW final_conv, tor_conv, sc_conv;
-  ConvW2 layer2[8][4], tor_conv2, sc_conv2;   // k_conv2 layouts of the K=144 convs
-  ConvW2 layer2v[8][4];                       // ... of their l = 1 outputs alone (DBFR_GEMM_REDUCE_FIRST: the scalar outputs go through k_convz)
-  ConvZ layerz[8][4], tor_convz, sc_convz;    // reduce-first form of the scalar-output paths (convz.hip)
-  int use_conv2;
-  int gemm_split;      // DBFR_GEMM_*; non-zero: the 144 x W GEMM of the K=144 convs runs on the fp16 matrix pipe with two-piece operands (conv2h.hip; reduce_first:
+  ModelConv layer[8][4];   // [l][family]: 0 lig, 1 cross_al, 2 atom, 3 cross_la
+  ModelConv final_conv, tor, sc;
+  int use_conv2 = -1;
+  int gemm_split = 0;  // DBFR_GEMM_*; non-zero: the 144 x W GEMM of the K=144 convs runs on the fp16 matrix pipe with two-piece operands (conv2h.hip; reduce_first:
                        // + convz.hip), any batch size
-  int* queue;          // [2] unit queue of k_conv2 (re-armed by the kernel itself)
+  int* queue = nullptr;   // [2] unit queue of k_conv2 (re-armed by the kernel itself)
   std::string fallback_convs;   // ';'-separated names of the convs whose weights two fp16 pieces cannot hold (dbfr_model_fallback_convs)
   std::string rowscaled_convs;  // 'name:depth;' of the convs packed with per-row factors (dbfr_model_rowscaled_convs)
-  uint32_t layer_fallback;      // bit l: interaction layer l goes through the fp32-instruction kernel k_conv2 whatever the mode (a bias 2^48 above its row); bit 31: the torsion heads
-  int* edge_log; int edge_log_steps, edge_log_graphs;   // dbfr_model_set_edge_log: caller-owned device buffer [steps][6][graphs], or null
-  int* tie_log; int tie_log_steps, tie_log_graphs; float tie_tol;   // dbfr_model_set_tie_log: likewise, candidate pairs within tie_tol of a cutoff
-  Mlp2 lig_node_emb, lig_edge_emb, atom_edge_emb, la_edge_emb, center_edge_emb, tor_edge_emb, sc_edge_emb;
-  Mlp2 tr_final, rot_final, tor_final, sc_final;
-  const float* atom_emb[5]; int atom_dims[5];
-  const float* atom_lin_t;
-  const float *gs_lig_off, *gs_lig_c, *gs_atom_off, *gs_atom_c, *gs_cross_off, *gs_cross_c, *gs_center_off, *gs_center_c;
-  int* a14_group;
+  uint32_t layer_fallback = 0;  // bit l: interaction layer l goes through the fp32-instruction kernel k_conv2 whatever the mode (a bias 2^48 above its row); bit 31: the torsion heads
+  int* edge_log = nullptr; int edge_log_steps = 0, edge_log_graphs = 0;   // dbfr_model_set_edge_log: caller-owned device buffer [steps][6][graphs], or null
+  int* tie_log = nullptr; int tie_log_steps = 0, tie_log_graphs = 0; float tie_tol = 0.f;   // dbfr_model_set_tie_log: likewise, candidate pairs within tie_tol of a cutoff
+  Mlp2 lig_node_emb = {}, lig_edge_emb = {}, atom_edge_emb = {}, la_edge_emb = {}, center_edge_emb = {}, tor_edge_emb = {}, sc_edge_emb = {};
+  Mlp2 tr_final = {}, rot_final = {}, tor_final = {}, sc_final = {};
+  const float* atom_emb[5] = {}; int atom_dims[5] = {};
+  const float* atom_lin_t = nullptr;
+  const float *gs_lig_off = nullptr, *gs_lig_c = nullptr, *gs_atom_off = nullptr, *gs_atom_c = nullptr;
+  const float *gs_cross_off = nullptr, *gs_cross_c = nullptr, *gs_center_off = nullptr, *gs_center_c = nullptr;
+  int* a14_group = nullptr;
   // profiling of the dominant kernel
-  int profile;
+  int profile = 0;
   std::vector<hipEvent_t> ev;
-  size_t ev_used;
-  double* flops_dev;
-  double fused_bytes_last;   // third counter as of the last dbfr_profile_read (before its reset)
-  double executed_last;      // fourth counter (flops the matrix pipe executed in the K=144 conv launches), likewise
-  double useful_last;        // fifth: the executed flops that are not padding
-  double form_bytes_last;    // sixth: HBM bytes the form that runs has to move (DBFR_GEMM_REDUCE_FIRST: scalar-output message columns once per segment, inputs read by both kernels)
-  double conv_ms_acc; int64_t conv_launches_acc;
+  size_t ev_used = 0;
+  double* flops_dev = nullptr;
+  double fused_bytes_last = 0;   // third counter as of the last dbfr_profile_read (before its reset)
+  double executed_last = 0;      // fourth counter (flops the matrix pipe executed in the K=144 conv launches), likewise
+  double useful_last = 0;        // fifth: the executed flops that are not padding
+  double form_bytes_last = 0;    // sixth: HBM bytes the form that runs has to move (DBFR_GEMM_REDUCE_FIRST: scalar-output message columns once per segment, inputs read by both kernels)
+  double conv_ms_acc = 0; int64_t conv_launches_acc = 0;
 };
 
 template <typename T>
@@ -258,24 +267,25 @@ static int pack_upload(dbfr_model* m, D* o, F pack) {
   return rc;
 }
 
-// Every layout of one K=144 conv (an interaction-layer conv or a torsion conv): k_conv's, k_conv2 / k_conv2h's, the vector-output rows alone
-// (w2v; null for the torsion convs, whose outputs are all scalars) and k_convz's.  A conv that two fp16 pieces cannot hold sets `fallback_bit` of
-// layer_fallback and is named in fallback_convs, one packed with per-row factors in rowscaled_convs.
-static int pack_conv144(dbfr_model* m, const TMap& tm, const std::string& name, int kind, ConvW* w, ConvW2* w2, ConvW2* w2v, ConvZ* z, uint32_t fallback_bit) {
+// Every layout of one K=144 conv (an interaction-layer conv or a torsion conv) into its record: k_conv's, k_conv2 / k_conv2h's, the vector-output
+// rows alone (vector_rows; not for the torsion convs, whose outputs are all scalars) and k_convz's.  A conv that two fp16 pieces cannot hold sets
+// `fallback_bit` of layer_fallback and is named in fallback_convs, one packed with per-row factors in rowscaled_convs.
+static int pack_conv144(dbfr_model* m, const TMap& tm, const std::string& name, int kind, ModelConv* c, bool vector_rows, uint32_t fallback_bit) {
   const int rowscale = getenv("DBFR_F16_ROWSCALE") ? atoi(getenv("DBFR_F16_ROWSCALE")) : 1;   // (pack.h; read at every model creation: a test packs one model this way)
   ConvTensors t;
   int rc = conv_tensors(tm, name, kind, &t);
-  if (!rc) rc = pack_upload<PackedConv>(m, w, [&](PackedConv* p) { return pack_conv(t, kind, name, p); });
-  if (!rc) rc = pack_upload<PackedConv2>(m, w2, [&](PackedConv2* p) { return pack_conv2(t, kind, name, rowscale, false, p); });
+  if (!rc) rc = pack_upload<PackedConv>(m, &c->w, [&](PackedConv* p) { return pack_conv(t, kind, name, p); });
+  if (!rc) rc = pack_upload<PackedConv2>(m, &c->w2, [&](PackedConv2* p) { return pack_conv2(t, kind, name, rowscale, false, p); });
   if (rc) return rc;
-  w2->W1p = w->W1p; w2->b1 = w->b1;
-  if (w2->f16_depth > f16_depth_ok()) { m->layer_fallback |= fallback_bit; m->fallback_convs += name + ";"; }
-  if (w2->W2rinv || w2->W1rinv) m->rowscaled_convs += name + ":" + std::to_string(w2->f16_depth_run) + ";";
-  if (w2v) rc = pack_upload<PackedConv2>(m, w2v, [&](PackedConv2* p) { return pack_conv2(t, kind, name, rowscale, true, p); });
-  if (!rc) rc = pack_upload<PackedConvZ>(m, z, [&](PackedConvZ* p) { return pack_convz(t, kind, name, w2->k1, p); });
+  c->w2.W1p = c->w.W1p; c->w2.b1 = c->w.b1;
+  if (c->w2.f16_depth > f16_depth_ok()) { m->layer_fallback |= fallback_bit; m->fallback_convs += name + ";"; }
+  if (c->w2.W2rinv || c->w2.W1rinv) m->rowscaled_convs += name + ":" + std::to_string(c->w2.f16_depth_run) + ";";
+  if (vector_rows) rc = pack_upload<PackedConv2>(m, &c->w2v, [&](PackedConv2* p) { return pack_conv2(t, kind, name, rowscale, true, p); });
+  if (!rc) rc = pack_upload<PackedConvZ>(m, &c->z, [&](PackedConvZ* p) { return pack_convz(t, kind, name, c->w2.k1, p); });
   if (rc) return rc;
-  if (w2v) { w2v->W1p = w->W1p; w2v->b1 = w->b1; }
-  z->W1h = w2->W1h; z->W1rinv = w2->W1rinv;     // k_convz's hidden layer is k_conv2h's
+  if (vector_rows) { c->w2v.W1p = c->w.W1p; c->w2v.b1 = c->w.b1; }
+  c->z.W1h = c->w2.W1h; c->z.W1rinv = c->w2.W1rinv;     // k_convz's hidden layer is k_conv2h's
+  c->has_w2v = vector_rows; c->k144 = true;
   return DBFR_OK;
 }
 
@@ -293,9 +303,6 @@ static int model_create_impl(const dbfr_model_cfg* cfg, const dbfr_tensor* tenso
   for (int i = 0; i < n_tensors; ++i) tm[tensors[i].name] = &tensors[i];
   dbfr_model* m = new dbfr_model();
   m->cfg = *cfg;
-  m->profile = 0; m->ev_used = 0; m->flops_dev = nullptr; m->fused_bytes_last = 0; m->executed_last = 0; m->useful_last = 0; m->form_bytes_last = 0; m->conv_ms_acc = 0; m->conv_launches_acc = 0;
-  m->edge_log = nullptr; m->edge_log_steps = 0; m->edge_log_graphs = 0; m->layer_fallback = 0;
-  m->tie_log = nullptr; m->tie_log_steps = 0; m->tie_log_graphs = 0; m->tie_tol = 0.f;
   // which fused-conv kernel the K=144 convs use: k_conv2 (persistent, one launch per layer, tail split) wins while a layer
   // is only a few rounds of workgroups (predict.py-sized batches), k_conv (conv.hip) at bench-sized batches.
   // DBFR_CONV2 = 0 / 1 forces one of them, default -1 = by batch size
@@ -305,12 +312,12 @@ static int model_create_impl(const dbfr_model_cfg* cfg, const dbfr_tensor* tenso
   const char* fam[4] = {"lig_conv_layers", "cross_al_conv_layers", "atom_conv_layers", "cross_la_conv_layers"};
   for (int l = 0; l < cfg->num_conv_layers && !rc; ++l)
     for (int f = 0; f < 4 && !rc; ++f)
-      rc = pack_conv144(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), &m->layer[l][f], &m->layer2[l][f], &m->layer2v[l][f], &m->layerz[l][f], 1u << l);
+      rc = pack_conv144(m, tm, std::string(fam[f]) + "." + std::to_string(l), std::min(l, 3), &m->layer[l][f], true, 1u << l);
   ConvTensors final_t;
   if (!rc) rc = conv_tensors(tm, "final_conv", 4, &final_t);
-  if (!rc) rc = pack_upload<PackedConv>(m, &m->final_conv, [&](PackedConv* p) { return pack_conv(final_t, 4, "final_conv", p); });
-  if (!rc) rc = pack_conv144(m, tm, "tor_bond_conv", 5, &m->tor_conv, &m->tor_conv2, nullptr, &m->tor_convz, 1u << 31);
-  if (!rc && !cfg->no_sc_torsion) rc = pack_conv144(m, tm, "sc_tor_bond_conv", 5, &m->sc_conv, &m->sc_conv2, nullptr, &m->sc_convz, 1u << 31);
+  if (!rc) rc = pack_upload<PackedConv>(m, &m->final_conv.w, [&](PackedConv* p) { return pack_conv(final_t, 4, "final_conv", p); });
+  if (!rc) rc = pack_conv144(m, tm, "tor_bond_conv", 5, &m->tor, false, 1u << 31);
+  if (!rc && !cfg->no_sc_torsion) rc = pack_conv144(m, tm, "sc_tor_bond_conv", 5, &m->sc, false, 1u << 31);
   if (!rc) rc = pack_mlp(m, tm, "lig_node_embedding", cfg->lig_node_features + EMB, NS, NS, true, &m->lig_node_emb);
   if (!rc) rc = pack_mlp(m, tm, "lig_edge_embedding", cfg->lig_edge_features + 2 * EMB, NS, NS, true, &m->lig_edge_emb);
   if (!rc) rc = pack_mlp(m, tm, "atom_edge_embedding", 2 * EMB, NS, NS, true, &m->atom_edge_emb);
@@ -384,7 +391,7 @@ struct Ws {
   float *lig_x[2], *atom_x[2];
   EdgeSet set[N_SETS];
   // centre set
-  int *c_tgt, *c_gth, *c_row_start, *c_row_cnt, *c_n; float *c_dist, *c_sh, *c_emb;
+  int *c_tgt, *c_gth, *c_row_start, *c_row_cnt; float *c_dist, *c_sh, *c_emb;
   float* msg[4]; int conv2; float* gp; float *tor_attr, *sc_attr, *tor_feat, *sc_feat;
   float *xmax_l, *xmax_a;   // [G] largest |feature| of every graph's ligand / pocket nodes in the current layer (k_row_absmax; k_convz's y scale)
   int* n_edges6;  // [8] device counters
@@ -436,7 +443,6 @@ static int plan(const dbfr_model* m, const dbfr_batch* B, const dbfr_limits* lim
   }
   w->c_tgt = b.take<int>(NL); w->c_gth = b.take<int>(NL); w->c_dist = b.take<float>(NL); w->c_sh = b.take<float>((size_t)NL * SH_LD, "center.sh");
   w->c_emb = b.take<float>((size_t)NL * NS, "center.emb"); w->c_row_start = b.take<int>(G); w->c_row_cnt = b.take<int>(G);
-  w->c_n = w->n_edges6 ? w->n_edges6 + 6 : nullptr;
   // Which conv path a call takes (measured on MI355X, tools/latency_run.py):
   //   largest edge set <= 128 k edges (predict.py-sized batches: 1 complex x 4 poses, -bs 16): persistent k_conv2, one launch per layer;
   //   above: k_conv_layer (the four convs of a layer as one k_conv grid) -- faster than k_conv2 from ~40 poses on.
@@ -538,44 +544,9 @@ static ConvZDesc convz_desc(const ConvSite& s, const ConvZ& z, int D_out) {
   return o;
 }
 
-// one k_conv launch
-static void conv_call(dbfr_model* m, const ConvW& cw, const ConvSite& site, hipStream_t st) {
-  const ConvArgs a = conv_args(site, cw);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  // the dominant kernel k_conv<144> only (k_conv<96>: one short launch per step).  profile 1: HIP events around every launch + flop counter;
-  // profile 2: flop counter only
-  const bool prof = m->profile == 1 && cw.K == 144;
-  const bool count = m->profile && cw.K == 144;
-  if (prof) {
-    prof_events(m, &e0, &e1);
-    (void)hipEventRecord(e0, st);
-  }
-  launch_conv(a, st);
-  if (prof) (void)hipEventRecord(e1, st);
-  if (count) {
-    // algorithmic flops per edge: radial MLP 2K(K + W) + tensor-product contraction 2*(sum_paths mul1*mulo*dim_o)
-    // second counter: HBM bytes the reference's two-kernel form moves per edge (the [E,W] weights once,
-    // gathered irreps, harmonics, two int64 indices); the fused kernel never materialises them
-    launch_acc_flops(a.n_edges, 2.0 * cw.K * ((double)cw.K + cw.W), 4.0 * (cw.W + cw.D_in + 9) + 16.0, fused_bytes(cw.D_in, cw.D_out), m->flops_dev, st);
-  }
-}
-
-// one fused k_conv2 launch over up to four K=144 convs (an interaction layer, or the two torsion heads)
-// DBFR_GEMM_REDUCE_FIRST: `descs` hold the vector-output rows only (ConvW2 packed with vector_only) and `z` (same order) the reduce-first form of
-// the scalar-output rows: k_conv2h for the former (convs without l = 1 outputs are left out), k_convz for the latter, both writing the same message buffers.
-// `zsegs` (with z): per conv the segment sum of its edge set's chunks; null: k_convz_useful walks the chunk table in front of k_convz (the single-conv test hook).
-static void conv2_call(dbfr_model* m, const Conv2Desc* descs, const int* Ws, int n, hipStream_t st, bool f16_fallback = false, const ConvZDesc* z = nullptr,
-                       const int64_t* const* zsegs = nullptr) {
-  Conv2Args a;
-  memset(&a, 0, sizeof a);
-  for (int i = 0; i < n; ++i) a.c[i] = descs[i];
-  a.n_conv = n; a.queue = m->queue;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (m->profile == 1) {
-    prof_events(m, &e0, &e1);
-    (void)hipEventRecord(e0, st);
-  }
-  // developer clock read-out of k_conv2h: DBFR_CONV2_TRACE=<file>: the stamps of the LAST traced launch are written at exit
+// developer clock read-out of k_conv2h: DBFR_CONV2_TRACE=<file>: the stamps of the LAST traced launch are written at exit.  The device buffer, cleared
+// on `st` for the launch that follows, or null
+static unsigned long long* conv2_trace(hipStream_t st) {
   static unsigned long long* trace_dev = nullptr;
   static const char* trace_file = getenv("DBFR_CONV2_TRACE");
   if (trace_file && !trace_dev) {
@@ -587,63 +558,116 @@ static void conv2_call(dbfr_model* m, const Conv2Desc* descs, const int* Ws, int
       }
     });
   }
-  if (trace_dev) { (void)hipMemsetAsync(trace_dev, 0, 8 * C2_TRACE_CAP * sizeof(unsigned long long), st); a.trace = trace_dev; }
-  if (z) {
-    Conv2Args v = a;
-    v.n_conv = 0;
-    for (int i = 0; i < n; ++i)
-      if (descs[i].w.n_tiles > 0) v.c[v.n_conv++] = descs[i];
-    if (v.n_conv) launch_conv2h(v, st);
-    ConvZArgs za;
-    memset(&za, 0, sizeof za);
-    for (int i = 0; i < n; ++i) za.c[i] = z[i];
-    za.n_conv = n;
-    za.dbg = nullptr;
-    za.executed = m->profile ? m->flops_dev + 3 : nullptr;      // k_convz counts the matrix instructions it issues (one atomic per wave and unit)
-    launch_convz(za, st, !zsegs);
-  }
-  else if (m->gemm_split >= DBFR_GEMM_SPLIT_F16 && !f16_fallback) launch_conv2h(a, st);
-  else launch_conv2(a, st);   // DBFR_GEMM_F32, and a launch holding a conv that even per-row factors cannot fit into two fp16 pieces: the fp32 instruction
-  if (m->profile == 1) (void)hipEventRecord(e1, st);
-  if (m->profile) {
-    AccBatch ab; ab.count = 0;
-    ab.wide = 0;
-    auto acc = [&](const int* ne, double coef, double* dst) { if (ab.count < ACC_BATCH_MAX) { ab.n[ab.count] = ne; ab.coef[ab.count] = coef; ab.dst[ab.count] = dst; ++ab.count; } };
-    auto acc64 = [&](const int64_t* s, double coef, double* dst) { if (ab.count < ACC_BATCH_MAX) { ab.wide |= 1ull << ab.count; acc(reinterpret_cast<const int*>(s), coef, dst); } };
-    for (int i = 0; i < n; ++i) {
-      acc(descs[i].n_edges, 2.0 * 144 * (144.0 + Ws[i]), m->flops_dev);
-      acc(descs[i].n_edges, 4.0 * (Ws[i] + descs[i].w.D_in + 9) + 16.0, m->flops_dev + 1);
-      acc(descs[i].n_edges, fused_bytes(descs[i].w.D_in, descs[i].w.D_out), m->flops_dev + 2);
-      // what the matrix pipe executes in the per-edge kernel of this launch: `products` MFMA flops per flop of the hidden layer and of the W2 rows it walks
-      // (reduce-first: the vector-output rows only; the split kernels of round 2 keep the hidden layer on the fp32 instruction)
-      const double rows = 16.0 * descs[i].w.n_tiles;
-      const bool f16 = (m->gemm_split >= DBFR_GEMM_SPLIT_F16 && !f16_fallback) || z;
-      const double ex = f16 ? 3.0 * 2.0 * 144 * (144.0 + rows) : 2.0 * 144 * (144.0 + rows);
-      if (!z || descs[i].w.n_tiles > 0) acc(descs[i].n_edges, ex, m->flops_dev + 3);
-      // ... of which are not padding: everything in the per-edge kernels, except that the pair of DBFR_GEMM_REDUCE_FIRST computes the hidden layer twice
-      // (k_convz counts its own instructions and the useful ones among them itself, the hidden layer included)
-      if (!z) acc(descs[i].n_edges, ex, m->flops_dev + 4);
-      else if (descs[i].w.n_tiles > 0) acc(descs[i].n_edges, 3.0 * 2.0 * 144 * rows, m->flops_dev + 4);
-      // HBM bytes of the form that RUNS: the fused form's, except that the pair reads the edge record and the gathered rows twice and writes the
-      // scalar-output message columns once per SEGMENT (k_convz adds 4 x 48 per segment and irrep itself) and one flag byte per edge
-      const int D_in = descs[i].w.D_in, D_out = descs[i].w.D_out;
-      const double in_bytes = 4.0 * (48 + 9 + 3 + 48 + 48 + D_in);
-      if (!z) acc(descs[i].n_edges, fused_bytes(D_in, D_out), m->flops_dev + 5);
-      else acc(descs[i].n_edges, in_bytes + 1.0 + (descs[i].w.n_tiles > 0 ? in_bytes + 4.0 * (D_out - 48 * z[i].w.n_io) : 0.0), m->flops_dev + 5);
-      // k_convz's own share of the useful flops and of the form bytes, from the edges and the segments of the set's chunks (every edge lies in exactly one chunk:
-      // chunk_cap bounds their number, graph.hip k_graph_chunks, so none is cut off and the lengths sum to the edge count): per chunk the hidden layer
-      // of its edges; step A the edges x the (path, u) pairs that exist x 145 (the k tile 9: one column); step B one column per segment x (c, k) values x 48;
-      // three partial products each; 4 x 48 message bytes per segment and output irrep.  Integers times integer constants: exact in a double.
-      if (z && zsegs) {
-        double ncv = 0.0;
-        for (int io = 0; io < z[i].w.n_io; ++io) ncv += (double)z[i].w.nc_valid[io];
-        acc(descs[i].n_edges, 6.0 * (144.0 * 144.0 + 145.0 * ncv), m->flops_dev + 4);
-        acc64(zsegs[i], 6.0 * 145.0 * 48.0 * ncv, m->flops_dev + 4);
-        acc64(zsegs[i], 4.0 * 48.0 * z[i].w.n_io, m->flops_dev + 5);
-      }
+  if (trace_dev) (void)hipMemsetAsync(trace_dev, 0, 8 * C2_TRACE_CAP * sizeof(unsigned long long), st);
+  return trace_dev;
+}
+
+struct ConvJob { const ModelConv* c; ConvSite site; };
+
+// The one place that maps a group of up to four convs (an interaction layer, the torsion heads present, the final conv, the conv of a test hook) to
+// launches, with their profile bookkeeping:
+//   per-edge form (!w.conv2, and the K=96 final conv whatever w.conv2 says): a group of four as ONE k_conv_layer grid, any other group one k_conv per job;
+//   persistent form, one launch over the group: k_conv2 in DBFR_GEMM_F32 and for a launch that fell back (`fallback`: a conv that even per-row factors
+//     cannot fit into two fp16 pieces -- the fp32 instruction), else k_conv2h on every row (DBFR_GEMM_SPLIT_F16);
+//   pair form (DBFR_GEMM_REDUCE_FIRST): k_conv2h on the vector-output rows of the convs that have any, then k_convz on the scalar-output rows, both
+//     writing the same message buffers.  A site without chunk_segs (the test hook) gets k_convz_useful in front of k_convz.
+// profile 1: one HIP-event pair per K=144 launch (the pair form's two launches share one); profile 1 and 2: the counter updates, one k_acc_batch launch
+static void conv_group(dbfr_model* m, const Ws& w, const ConvJob* jobs, int n, bool fallback, hipStream_t st) {
+  AccBatch ab; ab.count = 0;
+  ab.wide = 0;
+  auto acc = [&](const int* ne, double coef, double* dst) { if (ab.count < ACC_BATCH_MAX) { ab.n[ab.count] = ne; ab.coef[ab.count] = coef; ab.dst[ab.count] = dst; ++ab.count; } };
+  auto acc64 = [&](const int64_t* s, double coef, double* dst) { if (ab.count < ACC_BATCH_MAX) { ab.wide |= 1ull << ab.count; acc(reinterpret_cast<const int*>(s), coef, dst); } };
+  // algorithmic flops per edge: radial MLP 2K(K + W) + tensor-product contraction 2*(sum_paths mul1*mulo*dim_o)
+  // second counter: HBM bytes the reference's two-kernel form moves per edge (the [E,W] weights once,
+  // gathered irreps, harmonics, two int64 indices); the fused kernels never materialise them.  Third: the fused form's bytes
+  auto acc_algorithm = [&](const ConvJob& j) {
+    const ConvW& cw = j.c->w;
+    acc(j.site.n_edges, 2.0 * cw.K * ((double)cw.K + cw.W), m->flops_dev);
+    acc(j.site.n_edges, 4.0 * (cw.W + cw.D_in + 9) + 16.0, m->flops_dev + 1);
+    acc(j.site.n_edges, fused_bytes(cw.D_in, cw.D_out), m->flops_dev + 2);
+  };
+  auto timed = [&](bool on, auto&& launch) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (on) {
+      prof_events(m, &e0, &e1);
+      (void)hipEventRecord(e0, st);
     }
+    launch();
+    if (on) (void)hipEventRecord(e1, st);
+  };
+  if (!w.conv2 || !jobs[0].c->k144) {
+    // the dominant kernel k_conv<144> only is timed and counted (k_conv<96>: one short launch per step)
+    if (n == 4) {   // bench-sized batches in f32 mode: the layer's four convs as ONE k_conv grid
+      ConvArgs c4[4];
+      for (int i = 0; i < 4; ++i) c4[i] = conv_args(jobs[i].site, jobs[i].c->w);
+      timed(m->profile == 1, [&] { launch_conv_layer(c4, st); });
+    } else {
+      for (int i = 0; i < n; ++i) timed(m->profile == 1 && jobs[i].c->k144, [&] { launch_conv(conv_args(jobs[i].site, jobs[i].c->w), st); });
+    }
+    for (int i = 0; i < n && m->profile; ++i)
+      if (jobs[i].c->k144) acc_algorithm(jobs[i]);
     launch_acc_batch(ab, st);
+    return;
   }
+  const bool f16 = m->gemm_split >= DBFR_GEMM_SPLIT_F16 && !fallback, pair = f16 && m->gemm_split == DBFR_GEMM_REDUCE_FIRST;
+  Conv2Args a;
+  memset(&a, 0, sizeof a);
+  a.queue = m->queue;
+  ConvZArgs za;
+  memset(&za, 0, sizeof za);
+  za.executed = m->profile ? m->flops_dev + 3 : nullptr;      // k_convz counts the matrix instructions it issues (one atomic per wave and unit)
+  bool useful_pass = false;
+  int n_tiles[4];   // W2 row tiles the per-edge kernel walks for job i (pair form: the vector-output rows; none for a conv whose outputs are all scalars)
+  for (int i = 0; i < n; ++i) {
+    const ModelConv& c = *jobs[i].c;
+    n_tiles[i] = !pair ? c.w2.n_tiles : c.has_w2v ? c.w2v.n_tiles : 0;
+    if (!pair || n_tiles[i] > 0) a.c[a.n_conv++] = conv2_desc(jobs[i].site, pair ? c.w2v : c.w2);
+    if (pair) {
+      za.c[za.n_conv++] = convz_desc(jobs[i].site, c.z, c.w.D_out);
+      useful_pass |= !jobs[i].site.chunk_segs;
+    }
+  }
+  timed(m->profile == 1, [&] {
+    a.trace = conv2_trace(st);
+    if (pair) {
+      if (a.n_conv) launch_conv2h(a, st);
+      launch_convz(za, st, useful_pass);
+    }
+    else if (f16) launch_conv2h(a, st);
+    else launch_conv2(a, st);
+  });
+  for (int i = 0; i < n && m->profile; ++i) {
+    const ConvZ& z = jobs[i].c->z;
+    const int* ne = jobs[i].site.n_edges;
+    acc_algorithm(jobs[i]);
+    // what the matrix pipe executes in the per-edge kernel of this launch: `products` MFMA flops per flop of the hidden layer and of the W2 rows it walks
+    // (reduce-first: the vector-output rows only; the split kernels of round 2 keep the hidden layer on the fp32 instruction)
+    const double rows = 16.0 * n_tiles[i];
+    const double ex = f16 ? 3.0 * 2.0 * 144 * (144.0 + rows) : 2.0 * 144 * (144.0 + rows);
+    if (!pair || n_tiles[i] > 0) acc(ne, ex, m->flops_dev + 3);
+    // ... of which are not padding: everything in the per-edge kernels, except that the pair of DBFR_GEMM_REDUCE_FIRST computes the hidden layer twice
+    // (k_convz counts its own instructions and the useful ones among them itself, the hidden layer included)
+    if (!pair) acc(ne, ex, m->flops_dev + 4);
+    else if (n_tiles[i] > 0) acc(ne, 3.0 * 2.0 * 144 * rows, m->flops_dev + 4);
+    // HBM bytes of the form that RUNS: the fused form's, except that the pair reads the edge record and the gathered rows twice and writes the
+    // scalar-output message columns once per SEGMENT (k_convz adds 4 x 48 per segment and irrep itself) and one flag byte per edge
+    const int D_in = jobs[i].c->w.D_in, D_out = jobs[i].c->w.D_out;
+    const double in_bytes = 4.0 * (48 + 9 + 3 + 48 + 48 + D_in);
+    if (!pair) acc(ne, fused_bytes(D_in, D_out), m->flops_dev + 5);
+    else acc(ne, in_bytes + 1.0 + (n_tiles[i] > 0 ? in_bytes + 4.0 * (D_out - 48 * z.n_io) : 0.0), m->flops_dev + 5);
+    // k_convz's own share of the useful flops and of the form bytes, from the edges and the segments of the set's chunks (every edge lies in exactly one chunk:
+    // chunk_cap bounds their number, graph.hip k_graph_chunks, so none is cut off and the lengths sum to the edge count): per chunk the hidden layer
+    // of its edges; step A the edges x the (path, u) pairs that exist x 145 (the k tile 9: one column); step B one column per segment x (c, k) values x 48;
+    // three partial products each; 4 x 48 message bytes per segment and output irrep.  Integers times integer constants: exact in a double.
+    if (pair && jobs[i].site.chunk_segs) {
+      double ncv = 0.0;
+      for (int io = 0; io < z.n_io; ++io) ncv += (double)z.nc_valid[io];
+      acc(ne, 6.0 * (144.0 * 144.0 + 145.0 * ncv), m->flops_dev + 4);
+      acc64(jobs[i].site.chunk_segs, 6.0 * 145.0 * 48.0 * ncv, m->flops_dev + 4);
+      acc64(jobs[i].site.chunk_segs, 4.0 * 48.0 * z.n_io, m->flops_dev + 5);
+    }
+  }
+  launch_acc_batch(ab, st);
 }
 
 static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, const dbfr_scores* out, Ws& w,
@@ -704,41 +728,21 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     const EdgeSet &LL = w.set[SET_LL], &AA = w.set[SET_AA], &AL = w.set[SET_AL], &LA = w.set[SET_LA];
     // the four convs of the layer, in family order: the radial MLP reads the target node's row and the source node's, the tensor product the source's;
     // all four read the OLD features
-    const ConvSite sites[4] = {conv_site(LL, G, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], w.xmax_l, w.counters + SET_LL),    // 0 ligand <- ligand
-                               conv_site(AL, G, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1], w.xmax_a, w.counters + SET_AL),    // 1 ligand <- pocket
-                               conv_site(AA, G, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2], w.xmax_a, w.counters + SET_AA),    // 2 pocket <- pocket
-                               conv_site(LA, G, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3], w.xmax_l, w.counters + SET_LA)};   // 3 pocket <- ligand
+    const ModelConv* mc = m->layer[l];
+    const ConvJob jobs[4] = {{&mc[0], conv_site(LL, G, lx, Di, LL.tgt, lx, Di, LL.gth, lx, Di, w.msg[0], w.xmax_l, w.counters + SET_LL)},    // 0 ligand <- ligand
+                             {&mc[1], conv_site(AL, G, lx, Di, AL.tgt, ax, Di, AL.gth, ax, Di, w.msg[1], w.xmax_a, w.counters + SET_AL)},    // 1 ligand <- pocket
+                             {&mc[2], conv_site(AA, G, ax, Di, AA.tgt, ax, Di, AA.gth, ax, Di, w.msg[2], w.xmax_a, w.counters + SET_AA)},    // 2 pocket <- pocket
+                             {&mc[3], conv_site(LA, G, ax, Di, LA.tgt, lx, Di, LA.gth, lx, Di, w.msg[3], w.xmax_l, w.counters + SET_LA)}};   // 3 pocket <- ligand
     const bool fallback = (m->layer_fallback >> l) & 1u;
-    const bool rf = w.conv2 && m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;
-    if (w.conv2) {   // all four convs of the layer in ONE persistent launch (conv2.hip), or the k_convz + k_conv2h pair
-      Conv2Desc ds[4]; ConvZDesc zs[4]; int Ws[4]; const int64_t* sums[4];
-      for (int i = 0; i < 4; ++i) {
-        sums[i] = sites[i].chunk_segs;
-        ds[i] = conv2_desc(sites[i], rf ? m->layer2v[l][i] : m->layer2[l][i]);
-        zs[i] = convz_desc(sites[i], m->layerz[l][i], Do);
-        Ws[i] = m->layer[l][i].W;
-      }
-      // the y scale of k_convz: largest |x| per graph and node set (x = the rows a conv gathers: LL, LA read ligand rows, AL, AA pocket rows)
-      if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, Di, Di, G, NA, st);
-      conv2_call(m, ds, Ws, 4, st, fallback, rf ? zs : nullptr, sums);
-    } else {   // bench-sized batches in f32 mode: the layer's four convs as ONE k_conv grid
-      ConvArgs c4[4];
-      for (int i = 0; i < 4; ++i) c4[i] = conv_args(sites[i], m->layer[l][i]);
-      hipEvent_t e0 = nullptr, e1 = nullptr;
-      if (m->profile == 1) {
-        prof_events(m, &e0, &e1);
-        (void)hipEventRecord(e0, st);
-      }
-      launch_conv_layer(c4, st);
-      if (m->profile == 1) (void)hipEventRecord(e1, st);
-      if (m->profile)
-        for (int i = 0; i < 4; ++i)
-          launch_acc_flops(c4[i].n_edges, 2.0 * 144 * (144.0 + m->layer[l][i].W), 4.0 * (m->layer[l][i].W + Di + 9) + 16.0, fused_bytes(Di, Do), m->flops_dev, st);
-    }
+    const bool rf = m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;   // the k_convz + k_conv2h pair serves the layer
+    // the y scale of k_convz: largest |x| per graph and node set (x = the rows a conv gathers: LL, LA read ligand rows, AL, AA pocket rows)
+    if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, Di, Di, G, NA, st);
+    conv_group(m, w, jobs, 4, fallback, st);
     ReduceLayerArgs ra;   // one reduction launch: LL then AL into the ligand rows, AA then LA into the pocket rows
     for (int i = 0; i < 4; ++i) {
-      ra.msg[i] = sites[i].msg; ra.row_start[i] = sites[i].row_start; ra.row_cnt[i] = sites[i].row_cnt; ra.ln[i] = m->layer[l][i].ln;
-      ra.first[i] = rf ? sites[i].seg_first : nullptr; ra.sc_lanes[i] = rf ? convz_sc_lanes(m->layerz[l][i]) : 0;
+      const ConvSite& s = jobs[i].site;
+      ra.msg[i] = s.msg; ra.row_start[i] = s.row_start; ra.row_cnt[i] = s.row_cnt; ra.ln[i] = mc[i].w.ln;
+      ra.first[i] = rf ? s.seg_first : nullptr; ra.sc_lanes[i] = rf ? convz_sc_lanes(mc[i].z) : 0;
     }
     ra.NL = NL; ra.NA = NA; ra.D = Do; ra.D_old = Di; ra.old_l = lx; ra.old_a = ax; ra.out_l = lnew; ra.out_a = anew;
     launch_reduce_ln_layer(ra, st);
@@ -755,8 +759,9 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     a.dist = w.c_dist; a.gs_offset = m->gs_center_off; a.gs_coeff = m->gs_center_c; a.out = w.c_emb;
     launch_mlp(a, st);
   }
-  conv_call(m, m->final_conv, flat_site(w.n_edges6 + 7, NL, w.c_tgt, w.c_gth, w.c_emb, w.c_sh, lx, D, w.c_gth, nullptr, 0, w.c_gth, lx, D, w.msg[0]), st);
-  launch_reduce_ln(w.msg[0], w.c_row_start, w.c_row_cnt, G, 12, m->final_conv.ln, nullptr, 0, w.gp, 12, 2, st);
+  const ConvJob final_job = {&m->final_conv, flat_site(w.n_edges6 + 7, NL, w.c_tgt, w.c_gth, w.c_emb, w.c_sh, lx, D, w.c_gth, nullptr, 0, w.c_gth, lx, D, w.msg[0])};
+  conv_group(m, w, &final_job, 1, false, st);
+  launch_reduce_ln(w.msg[0], w.c_row_start, w.c_row_cnt, G, 12, m->final_conv.w.ln, nullptr, 0, w.gp, 12, 2, st);
   {
     TrRotArgs a; a.gp = w.gp; a.temb = w.temb; a.tr_sigma = c->tr_sigma; a.rot_norm = c->rot_score_norm;
     a.tr = m->tr_final; a.rot = m->rot_final; a.G = G; a.scale_by_sigma = cfg.scale_by_sigma; a.tr_out = out->tr;
@@ -765,35 +770,32 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
   }
   // ---- the two torsion heads (ligand bonds, side-chain bonds): bond attributes + edge embedding, the conv, reduction + final MLP
   struct TorHead {
-    bool on; int n; const EdgeSet* S; ConvSite site;
+    bool on; int n; const EdgeSet* S; ConvJob job;
     const float* nodes; const int *b0, *b1, *bsel; int stride; float* attr;    // launch_bond_attr
     const Mlp2* emb; const float *gs_off, *gs_c;                               // the edge embedding
-    const ConvW* cw; const ConvW2* cw2; const ConvZ* cz;
     const Mlp2* fin; const float* norm2; float *feat, *out;                    // launch_tor_final
   };
   const EdgeSet &T = w.set[SET_TOR], &S = w.set[SET_SC];
-  // (one fused launch writes a message buffer per head; one k_conv per head re-uses msg[0])
+  // (a message buffer per head: both convs run before either reduction)
   TorHead heads[2];
   {
     TorHead& h = heads[0];   // ligand torsions: edges bond <- ligand atom
     h.on = B->NTOR > 0; h.n = B->NTOR; h.S = &T;
-    h.site = conv_site(T, G, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, w.msg[0], w.xmax_l, w.counters + SET_TOR);
+    h.job = {&m->tor, conv_site(T, G, lx, D, T.gth, w.tor_attr, NS, T.tgt, lx, D, w.msg[0], w.xmax_l, w.counters + SET_TOR)};
     h.nodes = lx; h.b0 = B->bond_src; h.b1 = B->bond_dst; h.bsel = B->tor_bond; h.stride = 0; h.attr = w.tor_attr;
     h.emb = &m->tor_edge_emb; h.gs_off = m->gs_lig_off; h.gs_c = m->gs_lig_c;
-    h.cw = &m->tor_conv; h.cw2 = &m->tor_conv2; h.cz = &m->tor_convz;
     h.fin = &m->tor_final; h.norm2 = c->tor_score_norm2; h.feat = w.tor_feat; h.out = out->tor;
   }
   {
     TorHead& h = heads[1];   // side-chain torsions: edges bond <- pocket atom
     h.on = !cfg.no_sc_torsion && B->NSC > 0; h.n = B->NSC; h.S = &S;
-    h.site = conv_site(S, G, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, w.msg[w.conv2 ? 1 : 0], w.xmax_a, w.counters + SET_SC);
+    h.job = {&m->sc, conv_site(S, G, ax, D, S.gth, w.sc_attr, NS, S.tgt, ax, D, w.msg[1], w.xmax_a, w.counters + SET_SC)};
     h.nodes = ax; h.b0 = B->sc_bond; h.b1 = nullptr; h.bsel = nullptr; h.stride = 2; h.attr = w.sc_attr;
     h.emb = &m->sc_edge_emb; h.gs_off = m->gs_atom_off; h.gs_c = m->gs_atom_c;
-    h.cw = &m->sc_conv; h.cw2 = &m->sc_conv2; h.cz = &m->sc_convz;
     h.fin = &m->sc_final; h.norm2 = c->sc_tor_score_norm2; h.feat = w.sc_feat; h.out = out->sc_tor;
   }
   const bool fallback = (m->layer_fallback >> 31) & 1u;
-  const bool rf = w.conv2 && m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;
+  const bool rf = m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !fallback;
   auto prologue = [&](const TorHead& h) {
     launch_bond_attr(h.nodes, D, h.b0, h.b1, h.bsel, h.stride, h.n, h.attr, st);
     MlpArgs a; memset(&a, 0, sizeof a);
@@ -802,33 +804,22 @@ static int run_score(dbfr_model* m, const dbfr_batch* B, const dbfr_cond* c, con
     launch_mlp(a, st);
   };
   auto epilogue = [&](const TorHead& h) {
-    if (rf) launch_reduce_ln(h.site.msg, h.site.row_start, h.site.row_cnt, h.n, 2 * NS, h.cw->ln, nullptr, 0, h.feat, 2 * NS, 2, st, h.site.seg_first, convz_sc_lanes(*h.cz));
-    else launch_reduce_ln(h.site.msg, h.site.row_start, h.site.row_cnt, h.n, 2 * NS, h.cw->ln, nullptr, 0, h.feat, 2 * NS, 2, st);
+    const ConvSite& s = h.job.site;
+    if (rf) launch_reduce_ln(s.msg, s.row_start, s.row_cnt, h.n, 2 * NS, h.job.c->w.ln, nullptr, 0, h.feat, 2 * NS, 2, st, s.seg_first, convz_sc_lanes(h.job.c->z));
+    else launch_reduce_ln(s.msg, s.row_start, s.row_cnt, h.n, 2 * NS, h.job.c->w.ln, nullptr, 0, h.feat, 2 * NS, 2, st);
     launch_tor_final(h.feat, *h.fin, h.norm2, cfg.scale_by_sigma, h.n, h.out, st);
   };
-  if (w.conv2) {   // both prologues, ONE fused launch over the heads present, both epilogues
-    Conv2Desc ds[2]; ConvZDesc zs[2]; int Ws[2]; const int64_t* sums[2]; int nd = 0;
-    if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, D, D, G, NA, st);
-    for (const TorHead& h : heads) {
-      if (!h.on) continue;
-      prologue(h);
-      ds[nd] = conv2_desc(h.site, *h.cw2);
-      if (rf) ds[nd].w.n_tiles = 0;   // (all outputs of a torsion conv are scalars: k_convz serves every row)
-      zs[nd] = convz_desc(h.site, *h.cz, 2 * NS);
-      sums[nd] = h.site.chunk_segs;
-      Ws[nd++] = h.cw->W;
-    }
-    if (nd) conv2_call(m, ds, Ws, nd, st, fallback, rf ? zs : nullptr, sums);
-    for (const TorHead& h : heads)
-      if (h.on) epilogue(h);
-  } else {         // one k_conv per head
-    for (const TorHead& h : heads) {
-      if (!h.on) continue;
-      prologue(h);
-      conv_call(m, *h.cw, h.site, st);
-      epilogue(h);
-    }
+  // both prologues, the convs of the heads present as ONE group, both epilogues
+  if (rf) launch_row_absmax(lx, B->lig_ptr, w.xmax_l, ax, B->atm_ptr, w.xmax_a, D, D, G, NA, st);
+  ConvJob jobs[2]; int nj = 0;
+  for (const TorHead& h : heads) {
+    if (!h.on) continue;
+    prologue(h);
+    jobs[nj++] = h.job;
   }
+  if (nj) conv_group(m, w, jobs, nj, fallback, st);
+  for (const TorHead& h : heads)
+    if (h.on) epilogue(h);
   return DBFR_OK;
 }
 
@@ -1062,20 +1053,13 @@ extern "C" int dbfr_workspace_layout(const dbfr_model* m, const dbfr_batch* b, c
 }
 
 // ------------------------------------------------------------------------------------------------ unit-test hooks
-static const ConvW* pick_conv(const dbfr_model* m, int layer, int family) {
+// the record of a conv by the hooks' (layer, family) address: an interaction-layer conv, -1 the final conv, -2 / -3 the torsion convs; or null
+static const ModelConv* pick_conv(const dbfr_model* m, int layer, int family) {
   if (layer >= 0 && layer < m->cfg.num_conv_layers && family >= 0 && family < 4) return &m->layer[layer][family];
   if (layer == -1) return &m->final_conv;
-  if (layer == -2) return &m->tor_conv;
-  if (layer == -3 && !m->cfg.no_sc_torsion) return &m->sc_conv;
+  if (layer == -2) return &m->tor;
+  if (layer == -3 && !m->cfg.no_sc_torsion) return &m->sc;
   return nullptr;
-}
-// ... and the k_conv2 / k_convz layouts of the same conv (a K=144 conv: not the final one).  w2v, the vector-output rows alone, is null for the
-// torsion convs: all their outputs are scalars.
-struct Conv144 { const ConvW2* w2; const ConvW2* w2v; const ConvZ* z; };
-static Conv144 pick_conv144(const dbfr_model* m, int layer, int family) {
-  if (layer >= 0) return {&m->layer2[layer][family], &m->layer2v[layer][family], &m->layerz[layer][family]};
-  if (layer == -2) return {&m->tor_conv2, nullptr, &m->tor_convz};
-  return {&m->sc_conv2, nullptr, &m->sc_convz};
 }
 
 static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t family, int32_t n_edges, const int32_t* n_edges_dev,
@@ -1084,16 +1068,15 @@ static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t fami
                           float* msg, void* hip_stream) {
   if (!m) return fail(DBFR_ERR_ARG, "null model");
   g_launch_err = false;
-  const ConvW* cw = pick_conv(m, layer, family);
-  if (!cw) return fail(DBFR_ERR_ARG, "no such conv");
-  ConvSite site = flat_site(n_edges_dev, n_edges, tgt, gth, emb, sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg);
+  const ModelConv* c = pick_conv(m, layer, family);
+  if (!c) return fail(DBFR_ERR_ARG, "no such conv");
+  hipStream_t st = (hipStream_t)hip_stream;
+  ConvJob job = {c, flat_site(n_edges_dev, n_edges, tgt, gth, emb, sh, tab1, ld1, idx1, tab2, ld2, idx2, x, ldx, msg)};
+  bool deep = false;
   if (conv2) {
-    if (cw->K != 144) return fail(DBFR_ERR_ARG, "k_conv2 serves the K=144 convs");
-    const Conv144 c2 = pick_conv144(m, layer, family);
-    const bool deep = c2.w2->f16_depth > f16_depth_ok();
+    if (!c->k144) return fail(DBFR_ERR_ARG, "k_conv2 serves the K=144 convs");
+    deep = c->w2.f16_depth > f16_depth_ok();   // (the hook decides per conv; a fused launch of run_score by its layer's bit of layer_fallback)
     const bool rf = m->gemm_split == DBFR_GEMM_REDUCE_FIRST && !deep;   // (the message buffer then holds segment sums in the segments' first rows: include/dbfr.h)
-    Conv2Desc d = conv2_desc(site, rf && c2.w2v ? *c2.w2v : *c2.w2);
-    if (rf && !c2.w2v) d.w.n_tiles = 0;
     // k_convz's chunk table for this flat edge list, in a scratch buffer the hook keeps (test hook: one caller at a time): the list is cut every
     // 2048 edges as if those were graphs (parallel walk)
     static int* scratch_dev[16] = {nullptr}; static size_t scratch_dev_ints[16] = {0};   // (per device: the hook may be driven on several)
@@ -1110,18 +1093,18 @@ static int test_conv_impl(dbfr_model* m, bool conv2, int32_t layer, int32_t fami
         HIPCHECK(hipMalloc(&scratch, need * sizeof(int)));
         scratch_ints = need;
       }
-      launch_flat_chunks(tgt, n_edges_dev, n_edges, span, n_span, scratch, ccap, scratch + n_span + 1, scratch + n_span + 1 + ccap, (hipStream_t)hip_stream);
+      launch_flat_chunks(tgt, n_edges_dev, n_edges, span, n_span, scratch, ccap, scratch + n_span + 1, scratch + n_span + 1 + ccap, st);
     }
+    ConvSite& site = job.site;   // (no chunk_segs: the hook has no segment sums, k_convz_useful walks the chunk table in front of k_convz)
     if (scratch) { site.chunk_es = scratch + n_span + 1; site.chunk_gl = scratch + n_span + 1 + ccap; site.n_chunks = scratch + n_span; }
     site.max_chunks = ccap;
-    const ConvZDesc z = convz_desc(site, *c2.z, cw->D_out);
-    const int W = cw->W;
     // (k_convz writes the scalar-output columns of a segment's first row only; the hook's documented layout has zeros in the other rows)
-    if (rf) HIPCHECK(hipMemsetAsync(msg, 0, (size_t)n_edges * cw->D_out * sizeof(float), (hipStream_t)hip_stream));
-    conv2_call(m, &d, &W, 1, (hipStream_t)hip_stream, deep, rf ? &z : nullptr);
-  } else {
-    conv_call(m, *cw, site, (hipStream_t)hip_stream);
+    if (rf) HIPCHECK(hipMemsetAsync(msg, 0, (size_t)n_edges * c->w.D_out * sizeof(float), st));
   }
+  Ws w;
+  memset(&w, 0, sizeof w);
+  w.conv2 = conv2;   // dbfr_test_conv: the per-edge form; dbfr_test_conv2: the form the GEMM mode and `deep` select
+  conv_group(m, w, &job, 1, deep, st);
   HIPCHECK(hipGetLastError());
   return take_launch_error();
 }
@@ -1175,14 +1158,14 @@ extern "C" int dbfr_test_conv2(dbfr_model* m, int32_t layer, int32_t family, int
 extern "C" int dbfr_test_reduce_ln2(dbfr_model* m, int32_t layer, int32_t family, const float* msg, const int32_t* row_start, const int32_t* row_cnt,
                                     int32_t n_nodes, const float* old, int32_t d_old, float* out, int32_t mode, const uint8_t* seg_first, void* hip_stream) {
   if (!m) return fail(DBFR_ERR_ARG, "null model");
-  const ConvW* cw = pick_conv(m, layer, family);
-  if (!cw) return fail(DBFR_ERR_ARG, "no such conv");
+  const ModelConv* c = pick_conv(m, layer, family);
+  if (!c) return fail(DBFR_ERR_ARG, "no such conv");
   unsigned long long lanes = 0;
   if (seg_first) {
-    if (layer == -1 || cw->K != 144) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln2: seg_first with a conv that has no reduce-first form");
-    lanes = convz_sc_lanes(*pick_conv144(m, layer, family).z);
+    if (!c->k144) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln2: seg_first with a conv that has no reduce-first form");
+    lanes = convz_sc_lanes(c->z);
   }
-  launch_reduce_ln(msg, row_start, row_cnt, n_nodes, cw->D_out, cw->ln, old, d_old, out, cw->D_out, mode, (hipStream_t)hip_stream, seg_first, lanes);
+  launch_reduce_ln(msg, row_start, row_cnt, n_nodes, c->w.D_out, c->w.ln, old, d_old, out, c->w.D_out, mode, (hipStream_t)hip_stream, seg_first, lanes);
   HIPCHECK(hipGetLastError());
   return DBFR_OK;
 }
@@ -1191,9 +1174,9 @@ extern "C" int dbfr_test_reduce_ln(dbfr_model* m, int32_t layer, int32_t family,
                                    const int32_t* row_start, const int32_t* row_cnt, int32_t n_nodes, const float* old,
                                    int32_t d_old, float* out, int32_t mode, void* hip_stream) {
   if (!m) return fail(DBFR_ERR_ARG, "null model");
-  const ConvW* cw = pick_conv(m, layer, family);
-  if (!cw) return fail(DBFR_ERR_ARG, "no such conv");
-  launch_reduce_ln(msg, row_start, row_cnt, n_nodes, cw->D_out, cw->ln, old, d_old, out, cw->D_out, mode,
+  const ModelConv* c = pick_conv(m, layer, family);
+  if (!c) return fail(DBFR_ERR_ARG, "no such conv");
+  launch_reduce_ln(msg, row_start, row_cnt, n_nodes, c->w.D_out, c->w.ln, old, d_old, out, c->w.D_out, mode,
                    (hipStream_t)hip_stream);
   HIPCHECK(hipGetLastError());
   return DBFR_OK;
@@ -1258,10 +1241,10 @@ extern "C" int dbfr_test_reduce_ln_layer(const dbfr_model* m, int32_t layer, con
   ReduceLayerArgs ra;
   for (int i = 0; i < 4; ++i) {
     if (!msg[i] || !row_start[i] || !row_cnt[i] || (seg_first && !seg_first[i])) return fail(DBFR_ERR_ARG, "dbfr_test_reduce_ln_layer: null edge-set argument");
-    ra.msg[i] = msg[i]; ra.row_start[i] = row_start[i]; ra.row_cnt[i] = row_cnt[i]; ra.ln[i] = m->layer[layer][i].ln;
-    ra.first[i] = seg_first ? seg_first[i] : nullptr; ra.sc_lanes[i] = seg_first ? convz_sc_lanes(m->layerz[layer][i]) : 0;
+    ra.msg[i] = msg[i]; ra.row_start[i] = row_start[i]; ra.row_cnt[i] = row_cnt[i]; ra.ln[i] = m->layer[layer][i].w.ln;
+    ra.first[i] = seg_first ? seg_first[i] : nullptr; ra.sc_lanes[i] = seg_first ? convz_sc_lanes(m->layer[layer][i].z) : 0;
   }
-  ra.NL = NL; ra.NA = NA; ra.D = m->layer[layer][0].D_out; ra.D_old = m->layer[layer][0].D_in;
+  ra.NL = NL; ra.NA = NA; ra.D = m->layer[layer][0].w.D_out; ra.D_old = m->layer[layer][0].w.D_in;
   ra.old_l = old_l; ra.old_a = old_a; ra.out_l = out_l; ra.out_a = out_a;
   launch_reduce_ln_layer(ra, (hipStream_t)hip_stream);
   HIPCHECK(hipGetLastError());

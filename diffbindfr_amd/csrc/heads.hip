@@ -642,16 +642,6 @@ void launch_fill(float* p, float v, int n, hipStream_t st) {
 }
 __global__ void k_set_int(int* p, int v) { *p = v; }
 void launch_set_int(int* p, int v, hipStream_t st) { hipLaunchKernelGGL(k_set_int, dim3(1), dim3(1), 0, st, p, v); }
-__global__ void k_acc_flops(const int* n_edges, double flops_per_edge, double bytes_per_edge, double fused_bytes_per_edge, double* counter) {
-  // atomics: in profile mode 2 the four convs of a layer run on four streams
-  atomicAdd(&counter[0], flops_per_edge * (double)*n_edges);
-  atomicAdd(&counter[1], bytes_per_edge * (double)*n_edges);
-  atomicAdd(&counter[2], fused_bytes_per_edge * (double)*n_edges);
-}
-__global__ void k_acc_executed(const int* n_edges, double flops_per_edge, double* counter) { atomicAdd(counter, flops_per_edge * (double)*n_edges); }
-void launch_acc_executed(const int* n_edges, double flops_per_edge, double* counter, hipStream_t st) {
-  hipLaunchKernelGGL(k_acc_executed, dim3(1), dim3(1), 0, st, n_edges, flops_per_edge, counter);
-}
 // (profiling) all the counter updates of one conv launch in ONE kernel: a launch per update was 66 one-thread launches per denoise step, ~1 % of the
 // step the profile is taken of
 __global__ void k_acc_batch(AccBatch b) {
@@ -662,7 +652,4 @@ __global__ void k_acc_batch(AccBatch b) {
 }
 void launch_acc_batch(const AccBatch& b, hipStream_t st) {
   if (b.count > 0) hipLaunchKernelGGL(k_acc_batch, dim3(1), dim3(64), 0, st, b);
-}
-void launch_acc_flops(const int* n_edges, double flops_per_edge, double bytes_per_edge, double fused_bytes_per_edge, double* counter, hipStream_t st) {
-  hipLaunchKernelGGL(k_acc_flops, dim3(1), dim3(1), 0, st, n_edges, flops_per_edge, bytes_per_edge, fused_bytes_per_edge, counter);
 }

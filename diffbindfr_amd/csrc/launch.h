@@ -125,8 +125,6 @@ void launch_extract_templates(int n_res, const int* aatype, const float* pos14, 
                               float* rigid, float* angle, hipStream_t st);
 void launch_select_pocket(int n_prot, int n_res_total, const int* res_ptr, int m, const float* pos, const float* mask, const int* ref_ptr,
                           const float* ref, float cut2, int max_neighbors, float* d2, unsigned char* out, hipStream_t st);
-void launch_acc_flops(const int* n_edges, double flops_per_edge, double bytes_per_edge, double fused_bytes_per_edge, double* counter, hipStream_t st);
-void launch_acc_executed(const int* n_edges, double flops_per_edge, double* counter, hipStream_t st);
 #define ACC_BATCH_MAX 48
 struct AccBatch { const void* n[ACC_BATCH_MAX]; double coef[ACC_BATCH_MAX]; double* dst[ACC_BATCH_MAX]; unsigned long long wide; int count; };   // up to 48 counter
                           // updates of one k_acc_batch launch: dst += coef * *n, n an int, or a long long where the update's bit of `wide` is set

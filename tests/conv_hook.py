@@ -80,8 +80,8 @@ def run(fn, h, layer, fam, c, E, dev):
 
 def chunks(tgt, E=None, span=SPAN, max_edges=32, max_targets=4):
     """(first edge, edges, segments) of every chunk the single-conv hooks cut the first E edges of a flat, target-sorted edge list (a tensor,
-    an array or a list) into for DBFR_GEMM_REDUCE_FIRST (docs/kernels/conv_reduce_first.md; graph.hip chunk_len, api.cpp test_conv_impl): the
-    list is cut every `span` edges as if those were graphs; inside a span a chunk takes consecutive edges until it holds 32 of them or the 5th
+    an array or a list) into for DBFR_GEMM_REDUCE_FIRST (docs/kernels/conv_reduce_first.md; graph.hip chunk_len, api.cpp test_conv_impl,
+    which builds the table and hands the conv to the dispatcher conv_group as one job): the list is cut every `span` edges as if those were graphs; inside a span a chunk takes consecutive edges until it holds 32 of them or the 5th
     target would begin (CZ_MAXSEG = 4)."""
     t = tgt.tolist() if hasattr(tgt, "tolist") else list(tgt)
     E, out, es = len(t) if E is None else E, [], 0

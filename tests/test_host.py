@@ -328,7 +328,7 @@ def test_score_network_kernel_interface_is_declared_once():
                 out.append(m.group(2))
         return out
 
-    assert len(prototypes(text["launch.h"])) >= 30                       # the scan does see prototypes
+    assert len(prototypes(text["launch.h"])) >= 29                       # the scan does see prototypes (all 29 of them)
     assert len(set(prototypes(text["launch.h"]))) == len(prototypes(text["launch.h"]))
     stray = {f: p for f, s in text.items() if f != "launch.h" for p in [prototypes(s)] if p}
     assert not stray, stray

@@ -1,7 +1,9 @@
 """The host walk of the score network (csrc/api.cpp: run_score, plan, the conv packing of dbfr_model_create) describes every conv site
-once and keeps two layer forms and one torsion-head walk.  Rewriting it moves no kernel, no kernel argument and no launch order, so
-no output bit, no workspace offset and no profiling count may move: everything below equals tests/golden/score_walk_hashes.json,
-recorded with this file's recorder from the library of the commit BEFORE the walk was rewritten:
+once, keeps every packed layout of a conv in one record (ModelConv) and sends every group of convs -- a layer's four, the torsion heads
+present, the final conv -- through one dispatcher (conv_group), which alone picks the kernel form and does the profile bookkeeping.
+Rewriting it moves no kernel and no kernel argument, and reorders launches only where they are independent, so no output bit, no
+workspace offset and no profiling count may move: everything below equals tests/golden/score_walk_hashes.json, recorded with this
+file's recorder from the library of the commit BEFORE the walk was rewritten:
 
     python tests/test_score_walk_pinned_gpu.py --record tests/golden/score_walk_hashes.json
     (on an MI355X, in a checkout of that commit -- its Python modules and its freshly built libdbfr.so -- with only this file copied
@@ -33,7 +35,14 @@ profiling mode 2: the library's six device counters (conv_flops and ref_form_byt
 executed_flops, useful_flops, form_bytes from the three read-outs next to it) and the number of timed launches `dbfr_profile_read`
 reports (0 in mode 2, which records no events).  The counters are integer-valued sums far below 2^53, so equality is exact; conv_ms, a
 time, is not pinned.  The rowscale2 case also asserts that the model lists all 26 convs as packed with per-row factors and none as
-fallen back: its hashes alone equal the reduce_first case's (the factors are powers of two taken off again)."""
+fallen back: its hashes alone equal the reduce_first case's (the factors are powers of two taken off again).
+
+Pinned too, for the cases reduce_first, f32 and f32_conv2_0: `timed_launches_mode1`, the number of HIP-event pairs `dbfr_profile_read`
+reports after one `dbfr_score` on the same batch in profiling mode 1 -- the dispatcher owns how many launches are timed.  Recorded, like
+the rest, with this file's recorder, from the commit before the dispatcher was written (the second build id in the golden file's text).
+From the code: the batch is far below DBFR_CONV2_EDGES, so reduce_first and f32 run the persistent forms, one timed launch (the pair's two
+kernels share an event pair) per interaction layer and one fused launch over both heads: 6 + 1 = 7; the final conv (K=96, k_conv) is not
+timed.  With DBFR_CONV2=0 the six k_conv_layer launches are timed and each head's own k_conv<144>: 6 + 2 = 8."""
 import copy
 import ctypes as C
 import functools
@@ -70,6 +79,7 @@ CASES = {"reduce_first": ({}, False, "reduce_first"),
          "no_sc_f32_conv2_0": ({"DBFR_CONV2": "0"}, True, "f32")}
 NO_TOR_CASES = ("reduce_first", "f32_conv2_0")       # ... with the batch whose ligands have no rotatable bond
 PROFILE_CASES = ("reduce_first", "f32_conv2_0")
+MODE1_CASES = ("reduce_first", "f32", "f32_conv2_0")  # ... with the number of timed launches in profiling mode 1
 MODES = ("reduce_first", "split_f16", "f32")
 
 
@@ -168,6 +178,20 @@ def _profile(model):
             "useful_flops": us.value, "form_bytes": form.value, "timed_launches": float(nl.value)}
 
 
+def _timed_launches_mode1(model):
+    """The number of event pairs dbfr_profile_read reports after one dbfr_score in profiling mode 1."""
+    lib, h = L.load(), model.handle(DEV)
+    L.check(lib.dbfr_profile_read(h, None, None, None, None, 1))
+    L.check(lib.dbfr_profile_enable(h, 1))
+    try:
+        model(namespace_to(_at_step(_batch()[0]), DEV))
+        nl = C.c_int64()
+        L.check(lib.dbfr_profile_read(h, None, C.byref(nl), None, None, 1))
+    finally:
+        L.check(lib.dbfr_profile_enable(h, 0))
+    return {"timed_launches_mode1": float(nl.value)}
+
+
 def _workspace(model):
     """{mode: [bytes, sha256 of the layout's names and offsets]} for the cfg2 batch."""
     lib = L.load()
@@ -193,6 +217,8 @@ def _case(case, setenv):
         got = {"sha256": _outputs(model, case)}
         if case in PROFILE_CASES:
             got["profile"] = _profile(model)
+        if case in MODE1_CASES:
+            got["profile_mode1"] = _timed_launches_mode1(model)
         if case in ("f32", "f32_conv2_0"):
             got["workspace"] = _workspace(model)
     return got
